@@ -1,21 +1,26 @@
 #!/usr/bin/env python3
 """bench.py -- Groth16 proofs/s of the HIP backend on the reference's headline workload.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps of the headline leg and prints its line.  --full adds what takes runs of
+its own: the other witness hand-overs, the sharded legs at N > 1, the per-kernel sum of one proof run alone and the CPU
+baseline (with its parity check against the timed proof).  --dump-outputs DIR writes the proofs of the last timed step, as
+a caller receives them, to DIR/proof_{A,B,C}.npy (float64; see dump_outputs).
 
 A "step" is one full proof (witness -> QAP coefficients -> four multi-exponentiations -> proof) of the
 synthetic chain R1CS of SURVEY 8(d) with nC = 2^20 - 2 constraints (domain m = 2^20 exactly), nIn = 1,
 on a real proving key produced by this library's GPU key generator (seeded toxic waste).  Key and constraint
 system are resident in HBM; the WITNESS lies in pinned host memory when the timed region starts and every proof's
 33.5 MB H2D copy is inside it (SURVEY 8(d)'s metric: `value`; the prover pipeline copies a context's next witness on
-its copy stream while the current proof runs: zk_prove_stage_pinned / zk_prove_submit_staged).  The other ways to
-hand a witness over are timed on legs of the same length and reported under "witness_modes": resident in HBM (the
+its copy stream while the current proof runs: zk_prove_stage_pinned / zk_prove_submit_staged).  With --full the other ways
+to hand a witness over are timed on legs of the same length and reported under "witness_modes": resident in HBM (the
 PCIe-free rate, never `value`), pinned with the copy on the proof's own stream (zk_prove_submit_pinned), and a
 pageable host buffer with and without the double buffering (zk_prove_submit / zk_prove_stage).
 
 N > 1 (launched by torch.distributed.run, one rank per GPU): proofs are independent units, so the
 headline leg runs one prover per GPU with no data-path collective ("weak" scaling, value = all proofs of
-all ranks / max-over-ranks time).  The MSM-sharded prover of north_star / BASELINE config 5 is timed too
+all ranks / max-over-ranks time).  With --full the MSM-sharded prover of north_star / BASELINE config 5 is timed too
 and reported under "msm_sharded" (same circuit: the GPUs share each proof) and "msm_sharded_2p22"
 (config 5's size, 2^22 constraints): the base ranges of the key are split over the ranks, every rank
 proves its shard, the 640-byte partial results are exchanged with ONE RCCL all-gather on device buffers
@@ -26,7 +31,7 @@ bucket-reduction tails of the current one; every step still completes a full pro
 gives the one-proof-at-a-time latency figure.
 
 Rank 0 prints ONE JSON line.  `roofline` describes the dominant kernel (k_msm_accumulate over G2, the
-B-query) from HIP events recorded around it on its own stream in this run; `cpu_baseline` is the CPU
+B-query) from HIP events recorded around it on its own stream in this run; `cpu_baseline` (--full) is the CPU
 oracle (oracle/, a restatement of the reference prover -- libsnark itself cannot be built offline) timed
 on this host's cores.
 """
@@ -93,6 +98,11 @@ def main():
     ap.add_argument("--cpu-1t-logm", type=int, default=18, help="size of the one-thread CPU sample (a full 2^20 proof takes more than a minute on one core; 2^18: ~17 s)")
     ap.add_argument("--shard-logm", type=int, default=22, help="size of the config-5 sharded leg at N > 1")
     ap.add_argument("--extras-timeout", type=int, default=420, help="N > 1: seconds the secondary legs may take before the headline line is printed without them")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: the secondary legs (other witness hand-overs, sharded legs), the kernel sum of one "
+                         "proof run alone and the CPU baseline (--no-extras / --no-cpu-baseline still drop them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the proofs of the last timed step to DIR/proof_{A,B,C}.npy (float64 32-bit limbs of the affine coordinates)")
     args = ap.parse_args()
 
     import numpy as np
@@ -189,8 +199,9 @@ def main():
 
     all_acc_b = []          # every B-query accumulation this process launched (warm-ups and secondary legs too): what a profiler averages
 
-    def run_leg(pk, r1cs, wm, shard, steps, warmup, witness):
-        """`warmup` untimed + `steps` timed proofs in one parallelisation"""
+    def run_leg(pk, r1cs, wm, shard, steps, warmup, witness, keep_proofs=False):
+        """`warmup` untimed + `steps` timed proofs in one parallelisation; keep_proofs: also return the JSON of every proof of
+        the last timed step ("proofs"; a batch step proves kb witnesses, of which the timed path combines only the last)"""
         kb = max(1, args.batch) if not shard else 1
         ctxs = [P.ProverContext(pk, r1cs, multi_exp_c=args.multi_exp_c, device=local_rank,
                                 shard_rank=rank if shard else 0, shard_count=world if shard else 1, max_batch=kb, one_stream=args.one_stream)
@@ -213,6 +224,7 @@ def main():
                 proof, tm = sharded[slot].finish()
             elif kb > 1:
                 parts, tm = ctxs[slot].collect_batch(kb)
+                state["parts"] = (slot, parts)
                 proof = ctxs[slot].prove_combine(parts[kb - 1])
             else:
                 part, tm = ctxs[slot].collect()
@@ -271,9 +283,15 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed = float(tt.item())
         proofs = steps * kb * (world if (world > 1 and not shard) else 1)
+        last = None
+        if keep_proofs:
+            last = [js]
+            if kb > 1:
+                slot, parts = state["parts"]
+                last = [P.proof_to_json(ctxs[slot].prove_combine(parts[p]), wmk[p].reshape(-1, 4)[1:1 + r1cs.nIn]) for p in range(kb)]
         info = ctxs[0].info()
         ksum = None
-        if rank == 0 and not args.no_extras and not shard and kb == 1:
+        if rank == 0 and args.full and not args.no_extras and not shard and kb == 1:
             # one more (untimed) proof with every launch bracketed by HIP events: sum of kernel durations per proof
             P.profile_begin()
             ctxs[0].submit_resident(d_w.data_ptr()) if d_w is not None else ctxs[0].submit(wmk[0])
@@ -288,18 +306,20 @@ def main():
         if pinned is not None:
             pinned.free()
         return {"value": proofs / elapsed, "elapsed": elapsed, "acc_b": list(acc_b), "timings": state["t"], "json": js,
-                "launches_per_proof": launches, "info": info, "kernel_sum": ksum}
+                "launches_per_proof": launches, "info": info, "kernel_sum": ksum, "proofs": last}
 
     # N > 1: the headline leg runs independent provers per GPU ("weak": proofs are independent units, no data-path
-    # collective); the MSM-sharded legs (north_star / config 5) are timed as well and reported under named keys.
+    # collective); with --full the MSM-sharded legs (north_star / config 5) are timed as well and reported under named keys.
     mode = args.mode if world > 1 else "replicas"
     shard = world > 1 and mode == "shard"
-    head = run_leg(pk, r1cs, wm, shard, args.steps, args.warmup, args.witness)
+    head = run_leg(pk, r1cs, wm, shard, args.steps, args.warmup, args.witness, keep_proofs=bool(args.dump_outputs))
     value, elapsed, acc_b, last_t, js = head["value"], head["elapsed"], head["acc_b"], head["timings"], head["json"]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, head["proofs"])
     extras = {}
 
     def run_extras():
-        if args.no_extras:
+        if args.no_extras or not args.full:
             return
         if True:
             short = max(3, min(args.steps, 10))
@@ -426,7 +446,7 @@ def main():
             print(json.dumps(out), flush=True)
         os._exit(3)         # a process that has touched the GPU and bails out of a stalled collective must not look like a clean run
     watchdog = None
-    if world > 1 and not args.no_extras:
+    if world > 1 and args.full and not args.no_extras:
         import threading
         watchdog = threading.Timer(args.extras_timeout, bail)
         watchdog.daemon = True
@@ -438,14 +458,33 @@ def main():
         out.update(extras)
         if all_acc_b and not shard:
             out["roofline"]["all_launches"] = {"launches": len(all_acc_b), "avg_launch_ms": round(float(np.mean(all_acc_b)), 4),
-                                               "note": "every launch of the kernel in this process (warm-ups, secondary legs and the single-proof pass included): the average a `rocprofv3 --kernel-trace --stats` of this command reports"}
-        if world == 1 and not args.no_cpu_baseline:
+                                               "note": "every launch of the kernel in this process (warm-ups included; under --full the secondary legs and the single-proof pass too): the average a `rocprofv3 --kernel-trace --stats` of this command reports"}
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"], out["parity_vs_oracle"] = cpu_baseline(args, P, R, F, pk, r1cs, wm, js, logm, local_rank)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
         print(json.dumps(out), flush=True)
+
+
+def dump_outputs(path, proofs_json):
+    """The proofs of the last timed step as the caller receives them (ethsnarks proof JSON: affine coordinates, canonical form), one row
+    per proof of the step.  Every 254-bit coordinate is stored as its eight 32-bit limbs, least significant first, in float64 (exact):
+    proof_A.npy (k, 2, 8) [x, y], proof_B.npy (k, 2, 2, 8) [x, y] x [c0, c1] in the JSON's order, proof_C.npy (k, 2, 8)."""
+    import numpy as np
+
+    def limbs(h):
+        v = int(h, 16)
+        return [(v >> (32 * i)) & 0xFFFFFFFF for i in range(8)]
+
+    ps = [json.loads(j) for j in proofs_json]
+    os.makedirs(path, exist_ok=True)
+    arrays = {"proof_A": [[limbs(c) for c in p["A"]] for p in ps],
+              "proof_B": [[[limbs(c) for c in e] for e in p["B"]] for p in ps],
+              "proof_C": [[limbs(c) for c in p["C"]] for p in ps]}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.array(a, dtype=np.float64))
 
 
 def pmc_traffic(kernel, workload, logm, shards):

@@ -8,10 +8,10 @@ O=$R/gpurun_out/r04_prof
 mkdir -p $O
 cd $R
 set -e
-python bench.py --steps 20 --warmup 5 > $O/r04_bench.json 2> $O/bench.err
+python bench.py --full --steps 20 --warmup 5 > $O/r04_bench.json 2> $O/bench.err
 echo bench done
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --steps 20 --warmup 5 > $O/r04_bench_under_rocprofv3.json 2> $O/stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --steps 20 --warmup 5 > $O/r04_bench_under_rocprofv3.json 2> $O/stats.err
 echo stats done
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --steps 2 --warmup 1 --inflight 1 --no-extras --no-cpu-baseline > $O/pmc_fetch.json 2> $O/pmc_fetch.err
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -- python3 $R/bench.py --steps 2 --warmup 1 --inflight 1 --no-extras --no-cpu-baseline > $O/pmc_write.json 2> $O/pmc_write.err
