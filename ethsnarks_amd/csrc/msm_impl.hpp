@@ -497,7 +497,8 @@ int MsmWork<C>::alloc(uint32_t n, uint32_t c, typename C::Affine *shared_table, 
     }
     if (sort_only) return ZK_OK;
     const uint64_t n_pieces = sh.chunk.max_chunks(sh.max_entries() * B) + sh.nb * BS + 1;
-    ZK_HIP(hipMalloc(&heavy_list, sizeof(uint32_t) * (n_pieces / MSM_HEAVY + 2)));
+    // every bucket of every set, at most once per tail: a merged tail (enqueue_tail, also) counts the pieces of BOTH accumulations
+    ZK_HIP(hipMalloc(&heavy_list, sizeof(uint32_t) * sh.nb * BS));
     ZK_HIP(hipMalloc(&heavy_count, sizeof(uint32_t)));
     ZK_HIP(hipMalloc(&pieces, sizeof(typename C::XYZZ) * n_pieces));
     ZK_HIP(hipMalloc(&bucket, sizeof(typename C::XYZZ) * sh.nb * BS));

@@ -14,7 +14,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <mutex>
 #include <ucontext.h>
+#include <unordered_map>
 #include <time.h>
 #include <vector>
 
@@ -168,10 +170,65 @@ inline hipError_t hipGetDeviceCount(int *n) { *n = zk_emul::g_devices; return hi
 inline hipError_t hipSetDevice(int d) { if (d < 0 || d >= zk_emul::g_devices) return hipErrorInvalidValue; zk_emul::t_device = d; return hipSuccess; }
 inline hipError_t hipGetDevice(int *d) { *d = zk_emul::t_device; return hipSuccess; }
 inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
-template <class T> hipError_t hipMalloc(T **p, size_t n) { zk_emul::g_allocs[zk_emul::t_device]++; *p = (T *)calloc(n ? n : 1, 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
-inline hipError_t hipFree(void *p) { free(p); return hipSuccess; }
-template <class T> hipError_t hipHostMalloc(T **p, size_t n, unsigned = 0) { *p = (T *)calloc(n ? n : 1, 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
-inline hipError_t hipHostFree(void *p) { free(p); return hipSuccess; }
+// guard bands: every device / pinned allocation is followed by GUARD bytes of a fixed pattern, checked when the allocation is freed and by
+// zk_emul_guard_violations() (the suite asserts after every emulation test that no kernel or host path wrote past the end of a buffer).  The
+// AddressSanitizer build (make asan) sees exact bounds instead: there the allocations are plain.
+namespace zk_emul {
+#ifndef __SANITIZE_ADDRESS__
+constexpr size_t GUARD = 256;
+constexpr unsigned char GUARD_BYTE = 0xA5;
+inline std::mutex g_guard_mu;
+inline std::unordered_map<void *, size_t> g_live;          // allocation -> requested bytes
+inline uint64_t g_guard_freed_bad = 0;                     // violations found when the allocation was freed
+inline bool guard_intact(const void *p, size_t n) {
+    const unsigned char *g = (const unsigned char *)p + n;
+    for (size_t i = 0; i < GUARD; i++) if (g[i] != GUARD_BYTE) return false;
+    return true;
+}
+inline void *dev_alloc(size_t n) {
+    if (!n) n = 1;
+    void *p = calloc(n + GUARD, 1);                        // zero-filled, calloc's alignment
+    if (!p) return nullptr;
+    memset((char *)p + n, GUARD_BYTE, GUARD);
+    std::lock_guard<std::mutex> lk(g_guard_mu);
+    g_live[p] = n;
+    return p;
+}
+inline void dev_free(void *p) {
+    if (!p) return;
+    {
+        std::lock_guard<std::mutex> lk(g_guard_mu);
+        auto it = g_live.find(p);
+        if (it != g_live.end()) {
+            if (!guard_intact(p, it->second)) {
+                g_guard_freed_bad++;
+                fprintf(stderr, "hip_emul: write past the end of a %zu-byte allocation detected at free\n", it->second);
+            }
+            g_live.erase(it);
+        }
+    }
+    free(p);
+}
+#else
+inline void *dev_alloc(size_t n) { return calloc(n ? n : 1, 1); }
+inline void dev_free(void *p) { free(p); }
+#endif
+}  // namespace zk_emul
+// violations of the guard bands: those counted when an allocation was freed plus the live allocations whose guard is overwritten now
+extern "C" __attribute__((used, visibility("default"))) inline uint64_t zk_emul_guard_violations(void) {
+#ifndef __SANITIZE_ADDRESS__
+    std::lock_guard<std::mutex> lk(zk_emul::g_guard_mu);
+    uint64_t bad = zk_emul::g_guard_freed_bad;
+    for (const auto &a : zk_emul::g_live) bad += !zk_emul::guard_intact(a.first, a.second);
+    return bad;
+#else
+    return 0;
+#endif
+}
+template <class T> hipError_t hipMalloc(T **p, size_t n) { zk_emul::g_allocs[zk_emul::t_device]++; *p = (T *)zk_emul::dev_alloc(n); return *p ? hipSuccess : hipErrorOutOfMemory; }
+inline hipError_t hipFree(void *p) { zk_emul::dev_free(p); return hipSuccess; }
+template <class T> hipError_t hipHostMalloc(T **p, size_t n, unsigned = 0) { *p = (T *)zk_emul::dev_alloc(n); return *p ? hipSuccess : hipErrorOutOfMemory; }
+inline hipError_t hipHostFree(void *p) { zk_emul::dev_free(p); return hipSuccess; }
 inline hipError_t hipMemGetInfo(size_t *f, size_t *t) { *f = zk_emul::g_free[zk_emul::t_device]; *t = (size_t)1 << 40; return hipSuccess; }
 enum { hipHostRegisterDefault = 0 };
 inline hipError_t hipHostRegister(void *, size_t, unsigned) { return hipSuccess; }

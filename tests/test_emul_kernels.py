@@ -520,3 +520,179 @@ def test_msm_row_column_reduction_shapes(zk, oracle, monkeypatch, seg):
         for c, quad in ((2, "0"), (3, "1"), (8, "0"), (9, "1"), (9, "0")):
             monkeypatch.setenv("ZK_MSM_QUAD", quad)
             assert np.array_equal(zk.msm(bases, s, g2=g2, c=c), expect), (g2, c, quad)
+
+
+# ---- heavy buckets under skew: how many buckets the bucket reduction can send to the workgroup reducer (k_msm_heavy), and whether the
+# buffers are sized for it.  Every emulation test runs with guard bands behind every device buffer (tests/emul/hip_emul.h).
+
+@pytest.fixture(autouse=True)
+def no_guard_violations(zk):
+    """no kernel or host path of the test wrote past the end of a device or pinned buffer"""
+    import ctypes as C
+    zk._lib.zk_emul_guard_violations.restype = C.c_uint64
+    yield
+    bad = int(zk._lib.zk_emul_guard_violations())
+    assert bad == 0, "%d device buffers were written past their end" % bad
+
+
+_MERGED_CHILD = r'''
+import ctypes as C, json, os, sys
+sys.path[:0] = [sys.argv[2], os.path.join(sys.argv[2], "tests"), os.path.join(sys.argv[2], "oracle")]
+import numpy as np
+import oracle_lib as O
+from ethsnarks_amd import prover as P, fields as F
+from helpers import wide_sum_circuit
+P.load_library(sys.argv[1])
+P._lib.zk_emul_guard_violations.restype = C.c_uint64
+spec = json.loads(sys.stdin.read())
+os.environ.update(spec["env"])
+r, w = wide_sum_circuit(**spec["circuit"])
+def variant(s):                                                # another witness of the same circuit
+    cc = dict(spec["circuit"], seed=s)
+    if cc.get("values"):
+        cc["values"] = cc["values"][s:] + cc["values"][:s]
+    return wide_sum_circuit(**cc)[1]
+ws = [F.fr_to_mont(w)] + [F.fr_to_mont(variant(s)) for s in spec.get("batch_seeds", [])]
+pk_o, _ = O.keygen(r, seed=7)
+expect = [O.prove(pk_o, r, x)[0] for x in ws]
+pk = P.ProvingKey.from_parts(**pk_o.parts())
+c = spec["c"]
+def queued(ctx, x):
+    ctx.submit(x); part, _ = ctx.collect()
+    return P.proof_to_json(ctx.prove_combine(part), x[1:2])
+for mode in spec["modes"]:
+    if mode == "nomerge":
+        os.environ["ZK_NO_MERGE_HL"] = "1"                      # read at context creation
+    ctx = P.ProverContext(pk, r, multi_exp_c=c, max_batch=len(ws) if mode == "batch" else 1)
+    if mode == "prove":
+        print("INFO " + json.dumps(ctx.info()), flush=True)
+        got = [P.prove(ctx, ws[0])]
+    elif mode in ("submit", "nomerge"):
+        got = [queued(ctx, ws[0])]
+    elif mode == "batch":
+        got = P.prove_batch(ctx, np.stack(ws))
+    else:                                                       # shardG: G base-range shards (their tails always merge), folded on the host
+        G = int(mode[5:])
+        parts = []
+        for k in range(G):
+            sc = P.ProverContext(pk, r, multi_exp_c=c, shard_rank=k, shard_count=G)
+            parts.append(sc.prove_partial(ws[0])); sc.close()
+        got = [P.proof_to_json(ctx.prove_combine(np.stack(parts)), ws[0][1:2])]
+    ctx.close()
+    os.environ.pop("ZK_NO_MERGE_HL", None)
+    assert got == expect[:len(got)], mode
+    assert int(P._lib.zk_emul_guard_violations()) == 0, mode
+    print(mode, "equal", flush=True)
+print("ok")
+'''
+
+
+def _run_merged_child(emul, spec):
+    """the proofs of `spec` in a child process: before the heavy list was sized for merged tails its overflow corrupted the heap, which must
+    fail the test instead of killing the test session; returns the context info the child printed"""
+    import json, os, subprocess, sys
+    from conftest import ROOT
+    env = {k: v for k, v in os.environ.items() if not k.startswith(("ZK_SEG_", "ZK_MSM_", "ZK_NO_MERGE_HL"))}
+    out = subprocess.run([sys.executable, "-c", _MERGED_CHILD, emul, ROOT], input=json.dumps(spec), capture_output=True, text=True, env=env, timeout=900)
+    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout + out.stderr[-3000:]
+    return json.loads(next(l[5:] for l in out.stdout.splitlines() if l.startswith("INFO ")))
+
+
+def _emul_threads(waves):
+    return 32 * waves                   # msm_machine_threads of the emulation build
+
+
+def _l_sort(r, w, info):
+    """scalars of the bucket sort that drives the L accumulation of an unsharded context: the shared witness sort, or the L scalars"""
+    return w if info["share_L"] else w[r.nIn + 1:]
+
+
+def _one_digit_values(n, P):
+    """n witness values from P scalars whose 8-bit digits repeat one value in all 31 windows below 2^248: each scalar feeds one bucket
+    31 times, so a few hundred scalars make buckets of thousands of entries -- heavy at the default chunk lengths (up to 48 entries)"""
+    pool = [sum(((j * 13) % 127 + 1) << (8 * w) for w in range(31)) for j in range(P)]
+    return [pool[(i * 5 + i // 7) % P] for i in range(n)]
+
+
+_SEG4 = {"ZK_SEG_MIN": "4", "ZK_SEG_MAX": "4"}
+_MERGED = {       # wide rows (sum of `width` fresh variables) * ONE: an L-query 20 - 60 x the domain, forced window c = 8 (2^7 buckets)
+    "default-knobs": dict(circuit=dict(rows=30, width=60, values=_one_digit_values(30 * 60, 8), seed=3), c=8, env={}, modes=["prove", "submit"]),
+    "seg4-all-paths": dict(circuit=dict(rows=14, width=20, values=_one_digit_values(14 * 20, 16), seed=4), c=8, env=_SEG4, batch_seeds=[5, 6],
+                           modes=["prove", "submit", "batch", "shard2", "shard3", "nomerge"]),
+}
+
+
+@pytest.mark.parametrize("quad", ["0", "1"], ids=["tail1", "tail4"])
+@pytest.mark.parametrize("shape", sorted(_MERGED))
+def test_merged_hl_tail_with_more_heavy_buckets_than_the_h_query_has_pieces_for(emul, shape, quad):
+    """ADVICE r4 (medium): the merged H + L tail counts a bucket heavy from the pieces of BOTH accumulations, but the heavy list was sized
+    from the H-query's pieces alone.  An L-query far larger than the domain, at a forced window: synchronous proof, queued proof (merged
+    tail), a batch of three witnesses (heavy buckets in sets >= 1), 2- and 3-way shards, and ZK_NO_MERGE_HL -- all equal to the oracle.
+    The premise -- more heavy buckets than the old list held -- is recomputed from the digits, so the case cannot quietly become easy."""
+    spec = dict(_MERGED[shape], env=dict(_MERGED[shape]["env"], ZK_MSM_QUAD=quad))
+    info = _run_merged_child(emul, spec)
+    from helpers import wide_sum_circuit, ChunkRule, msm_digit_counts, bucket_pieces, old_heavy_capacity, MSM_HEAVY
+    r, w = wide_sum_circuit(**spec["circuit"])
+    c, m, env = spec["c"], r.domain_size, spec["env"]
+    assert info["H"]["c"] == info["L"]["c"] == c and info["m"] == m
+    rule_l = ChunkRule.of_shape(len(_l_sort(r, w, info)), c, _emul_threads, env=env)
+    heavy_from_l = int((bucket_pieces(msm_digit_counts(_l_sort(r, w, info), c), rule_l) > MSM_HEAVY).sum())
+    cap = old_heavy_capacity(m - 1, c, ChunkRule.of_shape(m - 1, c, _emul_threads, env=env))
+    assert heavy_from_l > cap, (heavy_from_l, cap)
+
+
+@pytest.mark.parametrize("side", ["L-only", "H-only"])
+def test_merged_tail_heavy_bucket_fed_by_one_side(emul, oracle, side):
+    """a heavy bucket of the merged tail whose pieces all come from one accumulation: the H-query's range empty and the L-query's large
+    (window 12: the 31 H scalars leave most of the 2^11 buckets empty, the L digits come from four values), and the reverse (a 2^10 domain
+    whose H digits fill every bucket of window 7, an L-query of one repeated value that leaves most of them empty)"""
+    from helpers import wide_sum_circuit, ChunkRule, msm_digit_counts, bucket_pieces, MSM_HEAVY
+    if side == "L-only":
+        spec = dict(circuit=dict(rows=30, width=60, pool=4, seed=8), c=12, env=_SEG4, modes=["prove", "submit"])
+    else:
+        spec = dict(circuit=dict(rows=1022, width=1, pool=1, seed=9), c=7, env=_SEG4, modes=["prove", "submit"])
+    info = _run_merged_child(emul, spec)
+    r, w = wide_sum_circuit(**spec["circuit"])
+    c, m, env = spec["c"], r.domain_size, spec["env"]
+    h = F.fr_from_mont(oracle.witness_map(r, F.fr_to_mont(w)))[:m - 1]
+    cnt_h, cnt_l = msm_digit_counts(h, c), msm_digit_counts(_l_sort(r, w, info), c)
+    pcs_h = bucket_pieces(cnt_h, ChunkRule.of_shape(m - 1, c, _emul_threads, env=env))
+    pcs_l = bucket_pieces(cnt_l, ChunkRule.of_shape(len(_l_sort(r, w, info)), c, _emul_threads, env=env))
+    if side == "L-only":
+        assert ((cnt_h == 0) & (pcs_l > MSM_HEAVY)).any()
+    else:
+        assert ((cnt_l == 0) & (pcs_h > MSM_HEAVY)).any()
+
+
+@pytest.mark.parametrize("quad", ["0", "1"], ids=["tail1", "tail4"])
+@pytest.mark.parametrize("g2", [False, True], ids=["G1", "G2"])
+def test_msm_more_heavy_buckets_than_the_heavy_grid(zk, oracle, monkeypatch, g2, quad):
+    """more heavy buckets than k_msm_heavy has workgroups (MSM_HEAVY_GRID = 256): the grid-stride loop over the heavy list, G1 and G2, one
+    and four lanes per logical thread.  11 values x 25 windows own 275 buckets of 264 entries each: 66 pieces of 4 entries (ZK_SEG_*)"""
+    from helpers import ChunkRule, msm_digit_counts, bucket_pieces, tiled_bases, digit_pool, MSM_HEAVY
+    monkeypatch.setenv("ZK_SEG_MIN", "4"); monkeypatch.setenv("ZK_SEG_MAX", "4"); monkeypatch.setenv("ZK_MSM_QUAD", quad)
+    c, P, per = 10, 11, 264
+    pool = digit_pool(P, c, 25)
+    sc = [pool[i % P] for i in range(P * per)]
+    sc[7] = F.FR - 1; sc[8] = 0                                        # one scalar with carries, one without entries
+    n = len(sc)
+    heavy = int((bucket_pieces(msm_digit_counts(sc, c), ChunkRule.of_shape(n, c, _emul_threads)) > MSM_HEAVY).sum())
+    assert heavy > 256, heavy
+    bases = tiled_bases(oracle, n, g2=g2, distinct=97)
+    s = F.fr_to_mont(sc)
+    assert np.array_equal(zk.msm(bases, s, g2=g2, c=c), oracle.msm(bases, s, g2=g2))
+
+
+@pytest.mark.parametrize("plog", [1, 2])
+def test_msm_heavy_buckets_in_frugal_planes(zk, oracle, monkeypatch, plog):
+    """frugal table layout (ZK_TEST_PLANES_LOG): heavy bucket ids in planes >= 1 (bucket set = window mod 2^plog)"""
+    from helpers import ChunkRule, msm_digit_counts, bucket_pieces, MSM_HEAVY
+    monkeypatch.setenv("ZK_TEST_PLANES_LOG", str(plog)); monkeypatch.setenv("ZK_SEG_MIN", "4"); monkeypatch.setenv("ZK_SEG_MAX", "4")
+    n, P, c = 1000, 8, 6
+    vals = rand_scalars(P, 40 + plog)
+    sc = [vals[(i * 7 + i // 3) % P] for i in range(n)]
+    pcs = bucket_pieces(msm_digit_counts(sc, c, plog), ChunkRule.of_shape(n, c, _emul_threads))
+    assert (pcs[1 << (c - 1):] > MSM_HEAVY).any()
+    bases = oracle.batch_mul(F.fr_to_mont(rand_scalars(n, 41)))
+    s = F.fr_to_mont(sc)
+    assert np.array_equal(zk.msm(bases, s, c=c), oracle.msm(bases, s))

@@ -767,3 +767,68 @@ def test_sharded_device_exchange_over_rccl_one_rank(hip):
     here = os.path.dirname(os.path.abspath(__file__))
     p = subprocess.run([sys.executable, os.path.join(here, "rccl_one_rank.py")], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0 and "RCCL_ONE_RANK_OK" in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
+
+
+def _device_threads(hip):
+    cus = hip.device_info()["compute_units"]
+    return lambda waves: cus * 4 * waves * 64          # msm_machine_threads on the device
+
+
+def test_merged_hl_tail_with_thousands_of_heavy_buckets(hip, oracle, monkeypatch):
+    """ADVICE r4 (medium) at device scale: the merged H + L tail counts a bucket heavy from the pieces of both accumulations, and the heavy
+    list must hold them all.  Window 16 forced (multi_exp_c), a 2^12 domain, ~2^20 L variables whose values come from 256 scalars: the L
+    digits fill ~4k buckets of ~95 pieces each, against ~1.6k entries the list held when it was sized from the H-query's pieces.  Queued
+    proof (merged tail), a batch of two witnesses, a sharded pair and ZK_NO_MERGE_HL all give the oracle's bytes."""
+    from helpers import wide_sum_circuit, ChunkRule, msm_digit_counts, bucket_pieces, old_heavy_capacity, MSM_HEAVY
+    c, rows, width = 16, 4094, 256
+    r, w = wide_sum_circuit(rows, width, pool=256, seed=12)
+    _, w2 = wide_sum_circuit(rows, width, pool=256, seed=13)
+    m = r.domain_size
+    assert m == 1 << 12
+    wm, wm2 = F.fr_to_mont(w), F.fr_to_mont(w2)
+    pk, _ = hip.keygen(r, seed=16)
+    pk_o = oracle.pk_from_parts(pk.parts())
+    expect, expect2 = oracle.prove(pk_o, r, wm)[0], oracle.prove(pk_o, r, wm2)[0]
+    ctx = hip.ProverContext(pk, r, multi_exp_c=c, max_batch=2)
+    info = ctx.info()
+    assert info["H"]["c"] == info["L"]["c"] == c and info["share_L"]
+    mt = _device_threads(hip)
+    heavy = int((bucket_pieces(msm_digit_counts(w, c), ChunkRule.of_shape(r.V + 1, c, mt)) > MSM_HEAVY).sum())
+    cap = old_heavy_capacity(m - 1, c, ChunkRule.of_shape(m - 1, c, mt, batch=2), sets=2)
+    assert heavy > cap, (heavy, cap)                 # premise: more heavy buckets than the H-sized list of this context held
+    ctx.submit(wm)
+    part, _ = ctx.collect()
+    assert hip.proof_to_json(ctx.prove_combine(part), wm[1:2]) == expect
+    assert hip.prove_batch(ctx, np.stack([wm, wm2])) == [expect, expect2]
+    assert hip.prove(ctx, wm2) == expect2
+    parts = []
+    for k in range(2):
+        sc = hip.ProverContext(pk, r, multi_exp_c=c, shard_rank=k, shard_count=2)
+        parts.append(sc.prove_partial(wm)); sc.close()
+    assert hip.proof_to_json(ctx.prove_combine(np.stack(parts)), wm[1:2]) == expect
+    ctx.close()
+    monkeypatch.setenv("ZK_NO_MERGE_HL", "1")
+    sep = hip.ProverContext(pk, r, multi_exp_c=c)
+    sep.submit(wm)
+    part, _ = sep.collect()
+    assert hip.proof_to_json(sep.prove_combine(part), wm[1:2]) == expect
+    sep.close(); pk.close()
+
+
+@pytest.mark.parametrize("quad", ["0", "1"], ids=["tail1", "tail4"])
+@pytest.mark.parametrize("g2", [False, True], ids=["G1", "G2"])
+def test_msm_more_heavy_buckets_than_the_heavy_grid(hip, oracle, monkeypatch, g2, quad):
+    """more heavy buckets than k_msm_heavy has workgroups (MSM_HEAVY_GRID = 256), G1 and G2, one and four lanes per logical thread:
+    11 / 19 values x 25 / 23 windows own 275 / 437 buckets (window 10 / 11) of 264 / 600 entries, cut into chunks of 4 entries (ZK_SEG_*)"""
+    from helpers import ChunkRule, msm_digit_counts, bucket_pieces, digit_pool, MSM_HEAVY
+    monkeypatch.setenv("ZK_SEG_MIN", "4"); monkeypatch.setenv("ZK_SEG_MAX", "4"); monkeypatch.setenv("ZK_MSM_QUAD", quad)
+    for c, P, per in ((10, 11, 264), (11, 19, 600)):
+        pool = digit_pool(P, c, 25 if c == 10 else 23)
+        sc = [pool[i % P] for i in range(P * per)]
+        sc[7] = F.FR - 1; sc[8] = 0
+        n = len(sc)
+        heavy = int((bucket_pieces(msm_digit_counts(sc, c), ChunkRule.of_shape(n, c, _device_threads(hip))) > MSM_HEAVY).sum())
+        assert heavy > 256, (c, heavy)
+        bases = tiled_bases(oracle, n, g2=g2, distinct=997)
+        s = F.fr_to_mont(sc)
+        assert np.array_equal(hip.msm(bases, s, g2=g2, c=c), oracle.msm(bases, s, g2=g2)), (c, n)
