@@ -23,7 +23,10 @@
 #include "ntt.hpp"
 #include "msm.hpp"
 #include "keygen.hpp"
+#include "blind.hpp"
 #include "../../include/zkhip.h"
+#include <errno.h>
+#include <sys/random.h>
 
 namespace zk { thread_local char g_last_error[256] = ""; }
 using namespace zk;
@@ -221,6 +224,10 @@ struct zk_pk {
     std::vector<uint32_t> a_idx, b_idx;
     std::vector<G1::Affine> a_val, H, L;
     std::vector<G2::Affine> b_val;
+    // the G1 half of the B-query's knowledge commitments (full key stream, tcc:53-90): same length and indices as b_val.
+    // A key with it (zk_pk_load_raw_full, zk_keygen_full) can make zero-knowledge proofs; a nozk key leaves it empty.
+    bool full = false;
+    std::vector<G1::Affine> b1_val;
 };
 
 extern "C" int zk_pk_from_parts(const uint64_t *alpha_g1, const uint64_t *beta_g1, const uint64_t *beta_g2,
@@ -261,7 +268,7 @@ extern "C" const void *zk_pk_part(const zk_pk *pk, int which) {
     case 0: return &pk->alpha_g1; case 1: return &pk->beta_g1; case 2: return &pk->beta_g2;
     case 3: return &pk->delta_g1; case 4: return &pk->delta_g2;
     case 5: return pk->a_idx.data(); case 6: return pk->a_val.data(); case 7: return pk->b_idx.data(); case 8: return pk->b_val.data();
-    case 9: return pk->H.data(); case 10: return pk->L.data(); default: return nullptr;
+    case 9: return pk->H.data(); case 10: return pk->L.data(); case 11: return pk->b1_val.data(); default: return nullptr;
     }
 }
 namespace { void tables_drop_key(uint64_t pk_id); }
@@ -469,18 +476,50 @@ extern "C" int zk_pk_alt2mcl(const char *alt_pk_file, const char *mcl_pk_file) t
 } ZK_GUARD
 
 // pk_mcl2nozk (src/export.cpp:399-408) = loadFromFile<full key> + the nozk conversion of hpp:209-233
-extern "C" int zk_pk_mcl2nozk(const char *mcl_pk_file, const char *nozk_pk_file) try {
-    if (!mcl_pk_file || !nozk_pk_file) return fail(ZK_ERR_ARG, "null argument");
-    FullKey k;
-    ZK_TRY(full_load(mcl_pk_file, ZK_CODEC_MCL_BN128, k));
-    zk_pk pk;
+// the nozk conversion of hpp:209-233: the A-query keeps its non-zero entries, the B-query its G2 half
+static void nozk_from_full(const FullKey &k, zk_pk &pk) {
     pk.alpha_g1 = k.alpha_g1; pk.beta_g1 = k.beta_g1; pk.beta_g2 = k.beta_g2; pk.delta_g1 = k.delta_g1; pk.delta_g2 = k.delta_g2;
     pk.a_domain = (uint32_t)k.A.size();
     for (size_t i = 0; i < k.A.size(); i++) if (!G1::is_inf(k.A[i])) { pk.a_idx.push_back((uint32_t)i); pk.a_val.push_back(k.A[i]); }
     pk.b_domain = k.b_domain; pk.b_idx = k.b_idx; pk.b_val = k.Bg;
     pk.H = k.H; pk.L = k.L;
+}
+extern "C" int zk_pk_mcl2nozk(const char *mcl_pk_file, const char *nozk_pk_file) try {
+    if (!mcl_pk_file || !nozk_pk_file) return fail(ZK_ERR_ARG, "null argument");
+    FullKey k;
+    ZK_TRY(full_load(mcl_pk_file, ZK_CODEC_MCL_BN128, k));
+    zk_pk pk;
+    nozk_from_full(k, pk);
     return zk_pk_save_raw(&pk, nozk_pk_file, ZK_CODEC_MCL_BN128);
 } ZK_GUARD
+
+// ---- the full (zero-knowledge) key as a proving key: the nozk key zk_pk_mcl2nozk would make, plus the G1 half of the B-query
+extern "C" int zk_pk_load_raw_full(const char *path, int codec, zk_pk **out) try {
+    if (!path || !out) return fail(ZK_ERR_ARG, "null argument");
+    if (!codec_known(codec)) return fail(ZK_ERR_ARG, "unsupported codec (ZK_CODEC_ALT_BN128 or ZK_CODEC_MCL_BN128)");
+    FullKey k;
+    ZK_TRY(full_load(path, codec, k));
+    std::unique_ptr<zk_pk> pk(new zk_pk());
+    nozk_from_full(k, *pk);
+    pk->b1_val = std::move(k.Bh);
+    pk->full = true;
+    *out = pk.release();
+    return ZK_OK;
+} ZK_GUARD
+// the full stream again: the A-query re-densified over a_domain (absent entries are the point at infinity)
+extern "C" int zk_pk_save_raw_full(const zk_pk *pk, const char *path, int codec) try {
+    if (!pk || !path) return fail(ZK_ERR_ARG, "null argument");
+    if (!codec_known(codec)) return fail(ZK_ERR_ARG, "unsupported codec (ZK_CODEC_ALT_BN128 or ZK_CODEC_MCL_BN128)");
+    if (!pk->full) return fail(ZK_ERR_ARG, "zk_pk_save_raw_full: the key has no G1 half of the B-query (a nozk key; load it with zk_pk_load_raw_full or make it with zk_keygen_full)");
+    FullKey k;
+    k.alpha_g1 = pk->alpha_g1; k.beta_g1 = pk->beta_g1; k.beta_g2 = pk->beta_g2; k.delta_g1 = pk->delta_g1; k.delta_g2 = pk->delta_g2;
+    k.A.assign(pk->a_domain, G1::aff_infinity());
+    for (size_t i = 0; i < pk->a_idx.size(); i++) k.A[pk->a_idx[i]] = pk->a_val[i];
+    k.b_domain = pk->b_domain; k.b_idx = pk->b_idx; k.Bg = pk->b_val; k.Bh = pk->b1_val;
+    k.H = pk->H; k.L = pk->L;
+    return full_save(path, codec, k);
+} ZK_GUARD
+extern "C" int zk_pk_is_full(const zk_pk *pk) try { return pk && pk->full ? 1 : 0; } ZK_GUARD
 
 // ================================================================ context
 namespace {
@@ -575,6 +614,10 @@ struct DeviceTables {
     uint32_t cA = 0, cB = 0, cH = 0, cL = 0;           // resolved window bits of the four tables
     G1::Affine *tA = nullptr, *tH = nullptr, *tL = nullptr; G2::Affine *tB = nullptr;
     uint32_t *dA_idx = nullptr, *dB_idx = nullptr;
+    // zero-knowledge proofs (a full key, unsharded): the G1 half of the B-query tabulated with the B-query's window bits and
+    // rows -- its multi-exponentiation reads the B-query's sorted entries --, and the fixed-base tables of delta1 / delta2 (blind.hpp)
+    bool zk = false;
+    G1::Affine *tB1 = nullptr, *tD1 = nullptr; G2::Affine *tD2 = nullptr;
     // the A-, B- and L-query all read the witness: ONE bucket sort of all V+1 witness digits drives every query that
     // holds at least 7/8 of the variables (absent entries are skipped lane-locally); sparser queries and sharded
     // contexts sort their own scalars
@@ -592,9 +635,9 @@ struct DeviceTables {
     // caller is -- Python's garbage collector inside a torch process -- and an eviction runs it in the middle of ctx_build)
     void free_device() {
         DeviceScope on(device);
-        void *dev[] = {tA, tH, tL, tB, dA_idx, dB_idx, posA, posB};
+        void *dev[] = {tA, tH, tL, tB, dA_idx, dB_idx, posA, posB, tB1, tD1, tD2};
         for (void *p : dev) if (p) hipFree(p);
-        tA = tH = tL = nullptr; tB = nullptr; dA_idx = dB_idx = posA = posB = nullptr;
+        tA = tH = tL = nullptr; tB = nullptr; dA_idx = dB_idx = posA = posB = nullptr; tB1 = tD1 = nullptr; tD2 = nullptr;
     }
 };
 struct DeviceTablesDeleter { void operator()(DeviceTables *t) const { if (t) { t->free_device(); delete t; } } };
@@ -713,6 +756,14 @@ struct zk_ctx {
     fe *h_tail = nullptr;                      // pinned: h[m-1] for the degree check
     NttTables tab;
     MsmWork<G1> mA, mH, mL, mW; MsmWork<G2> mB;       // mW: sort-only, the shared witness-digit sort
+    // zero-knowledge proofs (a context of a full key, tables->zk): the G1 half of the B-query (driven by the B-query's sort) and the
+    // blinding buffers (blind.hpp), device and pinned host copy: [k x {r, s}][k x {A, C}][k x B] for k = max_batch, on the device followed by
+    // [k x {r delta1, s delta1, -rs delta1}].  cur_zk: the proof in flight is one.  ev_z1 / ev_z2: after k_zk_blind_g1 / _g2 (zk_timings.gpu_total)
+    MsmWork<G1> mB1;
+    uint8_t *d_zk = nullptr, *h_zk = nullptr;
+    G1::Affine beta_g1;
+    bool cur_zk = false;
+    hipEvent_t ev_z1 = nullptr, ev_z2 = nullptr, ev_zf = nullptr;          // ev_zf: after k_zk_blind_fixed
     hipStream_t s_main = nullptr, s_acc = nullptr, s_a = nullptr, s_b = nullptr, s_l = nullptr;
     hipStream_t s_h = nullptr;                 // the H pipeline (row evaluations, transforms, H sort and tail) beside the witness sorts; == s_main when not split
     hipEvent_t ev_up = nullptr, ev_sort_h = nullptr;
@@ -746,7 +797,12 @@ struct zk_ctx {
         if (h_tail) hipHostFree(h_tail);
         cA.release(); cB.release(); cC.release();
         ntt_tables_free(tab);
-        mA.release(); mH.release(); mL.release(); mB.release(); mW.release();
+        mA.release(); mH.release(); mL.release(); mB.release(); mW.release(); mB1.release();
+        if (d_zk) hipFree(d_zk);
+        if (ev_z1) hipEventDestroy(ev_z1);
+        if (ev_z2) hipEventDestroy(ev_z2);
+        if (ev_zf) hipEventDestroy(ev_zf);
+        if (h_zk) { memset(h_zk, 0, (BLIND_RS_BYTES + BLIND_G1_BYTES + BLIND_G2_BYTES) * max_batch); hipHostFree(h_zk); }
         tables_release(tables);
         if (serial) s_a = s_b = s_l = nullptr;
         if (s_acc == s_main) s_acc = nullptr;
@@ -784,6 +840,7 @@ static int ctx_build(zk_ctx *c, const zk_pk *pk, const zk_csr *A, const zk_csr *
             std::unique_ptr<DeviceTables, DeviceTablesDeleter> fresh(new DeviceTables());      // (an error or exception below frees what was uploaded)
             t = fresh.get();
             t->pk_id = pk->id; t->device = c->device; t->rank = r; t->count = G; t->cbits = c->cfg.multi_exp_c; t->max_batch = c->max_batch;
+            t->zk = pk->full && G == 1;                                 // (sharded contexts prove without zero knowledge only)
             // The A-, B- and L-query all read the witness: ONE bucket sort of the witness digits drives every query that is
             // dense in the window it covers.  Unsharded the window is the whole witness; a shard's window is the span of the
             // witness indices its three base ranges touch (base-range sharding cuts the three queries at about the same place).
@@ -812,12 +869,13 @@ static int ctx_build(zk_ctx *c, const zk_pk *pk, const zk_csr *A, const zk_csr *
                 // memory: a test aid, and a way to leave room for other tenants of the device.
                 auto rows_of = [&](uint32_t cb, uint32_t plog) { const uint32_t W = 254 / cb + 1, S = 1u << plog; return (uint64_t)((W + S - 1) >> plog); };
                 auto bytes_at = [&](uint32_t plog) {
-                    return 64ull * (rows_of(t->cA, plog) * c->rA.n() + rows_of(t->cH, plog) * c->rH.n() + rows_of(t->cL, plog) * c->rL.n()) + 128ull * rows_of(t->cB, plog) * c->rB.n();
+                    return 64ull * (rows_of(t->cA, plog) * c->rA.n() + rows_of(t->cH, plog) * c->rH.n() + rows_of(t->cL, plog) * c->rL.n()) + 128ull * rows_of(t->cB, plog) * c->rB.n()
+                           + (t->zk ? 64ull * rows_of(t->cB, plog) * c->rB.n() + (64ull + 128ull) * BLIND_ROWS : 0);   // a zero-knowledge context: B1, delta1, delta2
                 };
                 t->full_table_bytes = bytes_at(0);
                 // what a context needs beside the tables: sort scratch (12 B per entry, two sorts), chunk pieces, polynomials, CSR -- about 16 B per
                 // entry of the four queries plus 8 GB of slack (the figure the eviction loop always kept)
-                const uint64_t entries = 15ull * ((uint64_t)c->rA.n() + c->rB.n() + c->rH.n() + c->rL.n()) * c->max_batch;
+                const uint64_t entries = 15ull * ((uint64_t)c->rA.n() + c->rB.n() * (t->zk ? 2 : 1) + c->rH.n() + c->rL.n()) * c->max_batch;   // (B1: reduction buffers of its own)
                 const uint64_t reserve = (8ull << 30) + 16ull * entries;
                 size_t mem_free = 0, mem_total = 0;
                 while (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess && t->full_table_bytes + reserve > mem_free && tables_evict_idle_locked(c->device)) {}
@@ -849,6 +907,13 @@ static int ctx_build(zk_ctx *c, const zk_pk *pk, const zk_csr *A, const zk_csr *
             if (rc == ZK_OK) rc = build_table<G1>(&t->tH, pk->H.data() + c->rH.lo, c->rH.n(), t->cH, t->plog);
             if (rc == ZK_OK) rc = build_table<G1>(&t->tL, pk->L.data() + c->rL.lo, c->rL.n(), t->cL, t->plog);
             if (rc == ZK_OK) rc = build_table<G2>(&t->tB, pk->b_val.data() + c->rB.lo, c->rB.n(), t->cB, t->plog);
+            if (rc == ZK_OK && t->zk) {
+                if (pk->b1_val.size() != pk->b_val.size()) rc = fail(ZK_ERR_ARG, "full key: the G1 half of the B-query has another length than the G2 half");
+                if (rc == ZK_OK) rc = build_table<G1>(&t->tB1, pk->b1_val.data() + c->rB.lo, c->rB.n(), t->cB, t->plog);
+                std::vector<G1::Affine> d1; std::vector<G2::Affine> d2;
+                if (rc == ZK_OK) { blind_table_host<G1>(pk->delta_g1, d1); rc = dev_upload(&t->tD1, d1.data(), d1.size()); }
+                if (rc == ZK_OK) { blind_table_host<G2>(pk->delta_g2, d2); rc = dev_upload(&t->tD2, d2.data(), d2.size()); }
+            }
             if (rc != ZK_OK) return rc;
             g_tables.push_back(t);
             fresh.release();
@@ -865,6 +930,16 @@ static int ctx_build(zk_ctx *c, const zk_pk *pk, const zk_csr *A, const zk_csr *
     ZK_TRY(c->mH.alloc(c->rH.n(), t->cH, t->tH, nullptr, false, KB, t->plog));
     ZK_TRY(c->mL.alloc(c->rL.n(), t->cL, t->tL, t->share_L ? &c->mW.sh : nullptr, false, KB, t->plog));
     ZK_TRY(c->mB.alloc(c->rB.n(), t->cB, t->tB, t->share_B ? &c->mW.sh : nullptr, false, KB, t->plog));
+    if (t->zk) {       // B1: the B-query's shape and sort (the shared witness sort, or mB's own), G1 accumulation and tail; blinding buffers
+        ZK_TRY(c->mB1.alloc(c->rB.n(), t->cB, t->tB1, t->share_B ? &c->mW.sh : &c->mB.sh, false, KB, t->plog));
+        const size_t per = BLIND_RS_BYTES + BLIND_G1_BYTES + BLIND_G2_BYTES;
+        ZK_HIP(hipMalloc(&c->d_zk, (per + BLIND_FIX_BYTES) * KB));
+        ZK_HIP(hipHostMalloc(&c->h_zk, per * KB, hipHostMallocDefault));
+        memset(c->h_zk, 0, per * KB);
+        ZK_HIP(hipEventCreate(&c->ev_z1)); ZK_HIP(hipEventCreate(&c->ev_z2));
+        ZK_HIP(hipEventCreateWithFlags(&c->ev_zf, hipEventDisableTiming));
+        c->beta_g1 = pk->beta_g1;
+    }
     ZK_TRY(c->cA.upload(A, V, KB)); ZK_TRY(c->cB.upload(B, V, KB)); ZK_TRY(c->cC.upload(C, V, KB));
     ZK_HIP(hipMalloc(&c->d_w, 32 * (size_t)(V + 1) * KB));
     // A | B | C polynomials of all proofs of a batch: [A: KB x m][B: KB x m][C: KB x m], one batched NTT launch per pass
@@ -1041,8 +1116,9 @@ static void store_xyzz(uint64_t *dst, const G2::XYZZ &p) { memcpy(dst, &p, sizeo
 // PHASE_H = the H-query of a proof whose witness part is already queued (its coefficients come from d_h)
 enum { PHASE_ALL = 0, PHASE_WITNESS = 1, PHASE_H = 2 };
 static int prove_enqueue(zk_ctx *c, const uint64_t *witness, int canonical, int resident, const fe *d_h, int phase);
+static void zk_clear_rs(zk_ctx *c);
 static void drain(zk_ctx *c) {
-    c->mL.tail_pending = c->mH.tail_pending = false;            // (a dropped proof's chunk pieces are not folded into the next one's reduction)
+    c->mL.tail_pending = c->mH.tail_pending = c->mB1.tail_pending = false;            // (a dropped proof's chunk pieces are not folded into the next one's reduction)
     hipStreamSynchronize(c->s_main); hipStreamSynchronize(c->s_acc); hipStreamSynchronize(c->s_a); hipStreamSynchronize(c->s_b); hipStreamSynchronize(c->s_l); hipStreamSynchronize(c->s_h);
 }
 static int prove_submit_impl(zk_ctx *c, const uint64_t *witness, int canonical, int resident = 0, uint32_t k = 1, const fe *d_h = nullptr, int phase = PHASE_ALL) {
@@ -1066,7 +1142,17 @@ static int prove_submit_impl(zk_ctx *c, const uint64_t *witness, int canonical, 
 }
 // d_h != nullptr: the H polynomial was computed elsewhere (option 2); this shard's coefficients [rH.lo, rH.hi) lie at d_h
 static int prove_enqueue(zk_ctx *c, const uint64_t *witness, int canonical, int resident, const fe *d_h, int phase) {
+    const bool zk = c->cur_zk && phase == PHASE_ALL;
+    const size_t zk_g1_at = BLIND_RS_BYTES * c->max_batch, zk_g2_at = zk_g1_at + BLIND_G1_BYTES * c->max_batch,
+                 zk_fix_at = zk_g2_at + BLIND_G2_BYTES * c->max_batch;
+    if (zk) ZK_HIP(hipMemcpyAsync(c->d_zk, c->h_zk, BLIND_RS_BYTES * c->cur_batch, hipMemcpyHostToDevice, c->s_main));   // r, s: before the upload (ev_w) and every sort
     if (phase != PHASE_H) ZK_TRY(upload_witness(c, witness, canonical, resident));
+    if (zk) {       // r delta1, s delta1, -rs delta1 need no MSM result: on the B-tail stream, idle until the B-query's tail
+        ZK_HIP(hipStreamWaitEvent(c->s_b, c->ev_w, 0));
+        ZK_LAUNCH(k_zk_blind_fixed, zk_div_up((uint64_t)c->cur_batch * 3 * BLIND_Q, BLIND_BLOCK), BLIND_BLOCK, c->s_b, (const G1::Affine *)c->tables->tD1,
+                  (const fe *)c->d_zk, (G1::XYZZ *)(c->d_zk + zk_fix_at), c->cur_batch);
+        ZK_HIP(hipEventRecord(c->ev_zf, c->s_b));
+    }
     // sorts and the H pipeline on m (high priority), accumulations on q (low priority), tails on side streams; longest tail
     // (G2) first.  A sort that finishes on m releases its accumulation on q through ev_sort.
     hipStream_t m = c->s_main, q = c->s_acc;
@@ -1127,6 +1213,17 @@ static int prove_enqueue(zk_ctx *c, const uint64_t *witness, int canonical, int 
     ZK_HIP(hipEventRecord(c->ev_b0, q));
     ZK_TRY(c->mB.enqueue_reduce(t->share_B ? c->mW.view_for(t->offB, t->posB) : c->mB.view(), q, c->env_tails_on_acc ? q : c->s_b, c->env_b_tail_lanes ? (uint32_t)c->env_b_tail_lanes : tail_lanes));    // tcc:499-506
     ZK_HIP(hipEventRecord(c->ev_b1, c->s_b));
+    if (zk) {
+        // B = beta2 + Bt + s delta2 right behind the B-query's own tail (k_zk_blind_g2 needs nothing else)
+        BlindG2Args g2{c->mB.partial_b, c->mB.sh.planes(), c->mB.sh.c, c->beta_g2, t->tD2, (const fe *)c->d_zk, (G2::XYZZ *)(c->d_zk + zk_g2_at), k};
+        ZK_LAUNCH(k_zk_blind_g2, zk_div_up((uint64_t)k * BLIND_Q, BLIND_BLOCK), BLIND_BLOCK, c->s_b, g2);
+        ZK_HIP(hipEventRecord(c->ev_z2, c->s_b));
+        ZK_HIP(hipMemcpyAsync(c->h_zk + zk_g2_at, c->d_zk + zk_g2_at, BLIND_G2_BYTES * k, hipMemcpyDeviceToHost, c->s_b));
+        // B1t: the G1 half of the B-query reads the B-query's sorted entries.  Its accumulation follows the B-query's on the
+        // accumulation stream, so that it runs while the G2 tail does; its tail goes to the A-tail stream, ahead of the A-query's
+        ZK_TRY(c->mB1.enqueue_accumulate(t->share_B ? c->mW.view_for(t->offB, t->posB) : c->mB.view(), q));
+        ZK_TRY(c->mB1.enqueue_tail(c->env_tails_on_acc ? q : c->s_a, tail_lanes));
+    }
     if (!t->share_A) { ZK_TRY(c->mA.enqueue_sort(c->d_w, c->dA_idx, c->rA.n(), 0, m, k, ws)); ZK_TRY(release()); }
     ZK_HIP(hipEventRecord(c->ev_a0, q));
     ZK_TRY(c->mA.enqueue_reduce(t->share_A ? c->mW.view_for(t->offA, t->posA) : c->mA.view(), q, c->env_tails_on_acc ? q : c->s_a, tail_lanes));    // tcc:488-495
@@ -1155,6 +1252,16 @@ static int prove_enqueue(zk_ctx *c, const uint64_t *witness, int canonical, int 
     else if (c->cur_merge && !c->serial && c->env_hl_tail) ts = c->env_hl_tail == 'l' ? c->s_l : c->env_hl_tail == 'a' ? c->s_a : hs;
     ZK_TRY(c->mH.enqueue_tail(ts, tail_lanes, c->cur_merge ? &c->mL : nullptr));     // one bucket reduction for Ht + Lt
     ZK_HIP(hipEventRecord(c->ev_h1, ts));
+    if (zk) {       // A and C from every G1 result: on the A-tail stream (behind the B1 and A tails), once the H and L tails are done
+        hipStream_t bs = c->env_tails_on_acc ? q : c->s_a;
+        ZK_HIP(hipStreamWaitEvent(bs, c->ev_h1, 0)); ZK_HIP(hipStreamWaitEvent(bs, c->ev_l1, 0)); ZK_HIP(hipStreamWaitEvent(bs, c->ev_zf, 0));
+        BlindG1Args g1{c->mA.partial_b, c->mB1.partial_b, c->mH.partial_b, c->cur_merge ? nullptr : c->mL.partial_b,
+                       c->mA.sh.planes(), c->mA.sh.c, c->mB1.sh.c, c->mH.sh.c, c->mL.sh.c, c->alpha_g1, c->beta_g1, (const G1::XYZZ *)(c->d_zk + zk_fix_at),
+                       (const fe *)c->d_zk, (G1::XYZZ *)(c->d_zk + zk_g1_at), k};
+        ZK_LAUNCH(k_zk_blind_g1, zk_div_up((uint64_t)k * BLIND_Q, BLIND_BLOCK), BLIND_BLOCK, bs, g1);
+        ZK_HIP(hipEventRecord(c->ev_z1, bs));
+        ZK_HIP(hipMemcpyAsync(c->h_zk + zk_g1_at, c->d_zk + zk_g1_at, BLIND_G1_BYTES * k, hipMemcpyDeviceToHost, bs));
+    }
     return ZK_OK;
 }
 
@@ -1172,7 +1279,7 @@ static int prove_collect_impl(zk_ctx *c, zk_partials *out, zk_timings *tm) {    
     if (out) for (uint32_t p = 0; p < c->cur_batch; p++) {      // out: cur_batch records
         store_xyzz(out[p].At, c->mA.finish(p)); store_xyzz(out[p].Bt, c->mB.finish(p));
         store_xyzz(out[p].Ht, c->mH.finish(p)); store_xyzz(out[p].Lt, c->mL.finish(p));
-    } else if (c->tables->plog) {                               // device copy of a sharded context with frugal tables: the planes are folded here, on the host
+    } else if (c->tables->plog && !c->cur_zk) {                 // device copy of a sharded context with frugal tables: the planes are folded here, on the host
         std::vector<zk_partials> parts(c->cur_batch);
         for (uint32_t p = 0; p < c->cur_batch; p++) {
             store_xyzz(parts[p].At, c->mA.finish(p)); store_xyzz(parts[p].Bt, c->mB.finish(p));
@@ -1193,6 +1300,11 @@ static int prove_collect_impl(zk_ctx *c, zk_partials *out, zk_timings *tm) {    
         hipEventElapsedTime(&tl, c->ev_start, c->ev_l1); hipEventElapsedTime(&th, c->ev_start, c->ev_h1);
         tm->gpu_total = ta; if (tb > tm->gpu_total) tm->gpu_total = tb;
         if (tl > tm->gpu_total) tm->gpu_total = tl; if (th > tm->gpu_total) tm->gpu_total = th;
+        if (c->cur_zk) {                                        // a zero-knowledge proof ends with its blinding kernels
+            float z1 = 0, z2 = 0;
+            hipEventElapsedTime(&z1, c->ev_start, c->ev_z1); hipEventElapsedTime(&z2, c->ev_start, c->ev_z2);
+            if (z1 > tm->gpu_total) tm->gpu_total = z1; if (z2 > tm->gpu_total) tm->gpu_total = z2;
+        }
         tm->host_finish = (float)(now_ms() - t0);
         tm->acc_a = c->mA.accumulate_ms(); tm->acc_b = c->mB.accumulate_ms();
         tm->acc_h = c->mH.accumulate_ms(); tm->acc_l = c->mL.accumulate_ms();
@@ -1316,6 +1428,7 @@ extern "C" int zk_prove_abort(zk_ctx *c) try {
     ZK_TRY(use_device(c->device));
     drain(c);
     c->set_in_flight(false); c->awaiting_h = false;
+    if (c->cur_zk) zk_clear_rs(c);
     return ZK_OK;
 } ZK_GUARD
 
@@ -1324,6 +1437,7 @@ extern "C" int zk_prove_batch_submit(zk_ctx *ctx, const uint64_t *witnesses, uin
 extern "C" int zk_prove_batch_submit_resident(zk_ctx *ctx, const void *d_witnesses, uint32_t k, int canonical) try { return prove_submit_impl(ctx, (const uint64_t *)d_witnesses, canonical, 1, k); } ZK_GUARD
 extern "C" int zk_prove_batch_collect(zk_ctx *ctx, zk_partials *out, uint32_t k, zk_timings *t) try {
     if (!ctx || !out) return fail(ZK_ERR_ARG, "null argument");
+    if (ctx && ctx->in_flight && ctx->cur_zk) return fail(ZK_ERR_ARG, "a zero-knowledge proof is in flight: collect it with zk_prove_zk_batch_collect");
     if (ctx->in_flight && k != ctx->cur_batch) return fail(ZK_ERR_ARG, "collect: k differs from the submitted batch size");
     return prove_collect_impl(ctx, out, t);
 } ZK_GUARD
@@ -1352,6 +1466,7 @@ extern "C" int zk_ctx_table_info(const zk_ctx *c, uint64_t info[4]) try {
 } ZK_GUARD
 extern "C" int zk_prove_collect(zk_ctx *ctx, zk_partials *out, zk_timings *t) try {
     if (!ctx || !out) return fail(ZK_ERR_ARG, "null argument");
+    if (ctx && ctx->in_flight && ctx->cur_zk) return fail(ZK_ERR_ARG, "a zero-knowledge proof is in flight: collect it with zk_prove_zk_batch_collect");
     if (ctx->in_flight && ctx->cur_batch != 1) return fail(ZK_ERR_ARG, "a batch is in flight: use zk_prove_batch_collect");
     return prove_collect_impl(ctx, out, t);
 } ZK_GUARD
@@ -1359,6 +1474,7 @@ extern "C" int zk_prove_collect(zk_ctx *ctx, zk_partials *out, zk_timings *t) tr
 // loose Montgomery values), ready for an RCCL all-gather; zk_prove_combine_device takes the gathered device buffer
 extern "C" const void *zk_ctx_partials_device(const zk_ctx *ctx) { return ctx ? ctx->d_partials : nullptr; }
 extern "C" int zk_prove_collect_device(zk_ctx *ctx, zk_timings *t) try {
+    if (ctx && ctx->in_flight && ctx->cur_zk) return fail(ZK_ERR_ARG, "a zero-knowledge proof is in flight: collect it with zk_prove_zk_batch_collect");
     if (ctx && ctx->cfg.shard_count <= 1) return fail(ZK_ERR_ARG, "zk_prove_collect_device: only sharded contexts keep a device copy of their partial sums");
     return prove_collect_impl(ctx, nullptr, t);
 } ZK_GUARD
@@ -1428,6 +1544,98 @@ extern "C" int zk_prove(zk_ctx *ctx, const uint64_t *witness, int canonical, zk_
     return zk_prove_timed(ctx, witness, canonical, out, nullptr);
 } ZK_GUARD
 
+// ---- zero-knowledge proofs (libsnark's r1cs_gg_ppzksnark_prover): A + r delta1, B + s delta2, C + s A + r B1 - r s delta1, blinded
+// on the device (blind.hpp).  Contexts of a full key only (tables->zk), unsharded; r, s per proof from the caller or from getrandom(2).
+static bool fr_canonical(const uint64_t v[4]) {
+    for (int i = 3; i >= 0; i--) {
+        const uint64_t p = (uint64_t)FrParams::p(2 * i) | ((uint64_t)FrParams::p(2 * i + 1) << 32);
+        if (v[i] != p) return v[i] < p;
+    }
+    return false;                                               // v == r
+}
+// one uniform scalar: 64 bytes of the operating system's CSPRNG reduced mod r (bias below 2^-250)
+static int fr_draw(fe &out) {
+    uint8_t buf[64];
+    for (size_t got = 0; got < sizeof(buf);) {
+        const ssize_t n = getrandom(buf + got, sizeof(buf) - got, 0);
+        if (n < 0) { if (errno == EINTR) continue; return fail(ZK_ERR_INTERNAL, "getrandom(2) failed: no randomness for r, s"); }
+        got += (size_t)n;
+    }
+    fe lo, hi, r2;
+    memcpy(lo.l, buf, 32); memcpy(hi.l, buf + 32, 32);
+    for (int i = 0; i < 8; i++) r2.l[i] = FrParams::r2(i);
+    const fe a = Fr::mul(hi, r2);                               // hi R^2 / R = hi 2^256 mod r (any hi < 2^256)
+    const fe b = Fr::from_mont(Fr::mul(lo, r2));                // lo mod r
+    out = Fr::canon(Fr::add(a, b));
+    volatile uint8_t *v = buf; for (size_t i = 0; i < sizeof(buf); i++) v[i] = 0;
+    return ZK_OK;
+}
+static void zk_clear_rs(zk_ctx *c) {                           // the host and device copies of r, s of the proof that was collected or dropped
+    volatile uint8_t *v = c->h_zk;
+    for (size_t i = 0; i < BLIND_RS_BYTES * c->max_batch; i++) v[i] = 0;
+    (void)hipMemset(c->d_zk, 0, BLIND_RS_BYTES * c->max_batch);
+    c->cur_zk = false;
+}
+static int prove_zk_submit_impl(zk_ctx *c, const uint64_t *witness, int canonical, int resident, uint32_t k, const uint64_t *rs_canon) {
+    if (!c || !witness) return fail(ZK_ERR_ARG, "null argument");
+    if (c->cfg.shard_count > 1) return fail(ZK_ERR_ARG, "zero-knowledge proofs need an unsharded context (shard_count <= 1)");
+    if (!c->tables->zk) return fail(ZK_ERR_ARG, "zero-knowledge proofs need a context created from a full proving key (zk_pk_load_raw_full / zk_keygen_full)");
+    if (c->in_flight) return fail(ZK_ERR_ARG, "a proof is already in flight on this context (collect it first)");
+    if (!k || k > c->max_batch) return fail(ZK_ERR_ARG, "batch size exceeds zk_config.max_batch of this context");
+    fe *rs = (fe *)c->h_zk;
+    for (uint32_t p = 0; p < 2 * k; p++) {
+        if (!rs_canon) { const int rc = fr_draw(rs[p]); if (rc != ZK_OK) { zk_clear_rs(c); return rc; } continue; }
+        if (!fr_canonical(rs_canon + 4 * (size_t)p)) { zk_clear_rs(c); return fail(ZK_ERR_ARG, "r and s must be canonical scalars below the Fr modulus"); }
+        memcpy(rs[p].l, rs_canon + 4 * (size_t)p, 32);
+    }
+    c->cur_zk = true;
+    const int rc = prove_submit_impl(c, witness, canonical, resident, k);
+    if (rc != ZK_OK) zk_clear_rs(c);
+    return rc;
+}
+static int prove_zk_collect_impl(zk_ctx *c, zk_proof *out, uint32_t k, zk_timings *tm) {
+    if (!c || !out) return fail(ZK_ERR_ARG, "null argument");
+    if (c->in_flight && !c->cur_zk) return fail(ZK_ERR_ARG, "the proof in flight is not a zero-knowledge proof: collect it with zk_prove_collect / zk_prove_batch_collect");
+    if (c->in_flight && k != c->cur_batch) return fail(ZK_ERR_ARG, "collect: k differs from the submitted batch size");
+    const int rc = prove_collect_impl(c, nullptr, tm);          // (waits for every stream of the context)
+    if (!c->cur_zk) return rc;                                  // nothing was in flight
+    zk_clear_rs(c);
+    ZK_TRY(rc);
+    const double t0 = now_ms();
+    const G1::XYZZ *g1 = (const G1::XYZZ *)(c->h_zk + BLIND_RS_BYTES * c->max_batch);
+    const G2::XYZZ *g2 = (const G2::XYZZ *)(c->h_zk + (BLIND_RS_BYTES + BLIND_G1_BYTES) * c->max_batch);
+    for (uint32_t p = 0; p < k; p++) {
+        memset(&out[p], 0, sizeof(out[p]));
+        put_g1(g1[2 * p], out[p].a_x, out[p].a_y, &out[p].a_inf);
+        put_g2(g2[p], out[p].b_x_c0, out[p].b_x_c1, out[p].b_y_c0, out[p].b_y_c1, &out[p].b_inf);
+        put_g1(g1[2 * p + 1], out[p].c_x, out[p].c_y, &out[p].c_inf);
+    }
+    if (tm) tm->host_finish += (float)(now_ms() - t0);
+    return ZK_OK;
+}
+extern "C" int zk_prove_zk_batch_submit(zk_ctx *ctx, const uint64_t *witnesses, uint32_t k, int canonical, const uint64_t *rs_canon) try {
+    return prove_zk_submit_impl(ctx, witnesses, canonical, 0, k, rs_canon);
+} ZK_GUARD
+extern "C" int zk_prove_zk_batch_submit_resident(zk_ctx *ctx, const void *d_witnesses, uint32_t k, int canonical, const uint64_t *rs_canon) try {
+    return prove_zk_submit_impl(ctx, (const uint64_t *)d_witnesses, canonical, 1, k, rs_canon);
+} ZK_GUARD
+extern "C" int zk_prove_zk_batch_collect(zk_ctx *ctx, zk_proof *out, uint32_t k, zk_timings *t) try {
+    return prove_zk_collect_impl(ctx, out, k, t);
+} ZK_GUARD
+extern "C" int zk_prove_zk_batch(zk_ctx *ctx, const uint64_t *witnesses, uint32_t k, int canonical, const uint64_t *rs_canon, zk_proof *out) try {
+    if (!ctx || !out) return fail(ZK_ERR_ARG, "null argument");
+    ZK_TRY(prove_zk_submit_impl(ctx, witnesses, canonical, 0, k, rs_canon));
+    return prove_zk_collect_impl(ctx, out, k, nullptr);
+} ZK_GUARD
+extern "C" int zk_prove_zk(zk_ctx *ctx, const uint64_t *witness, int canonical, const uint64_t *rs_canon, zk_proof *out) try {
+    if (!ctx || !out) return fail(ZK_ERR_ARG, "null argument");
+    ctx->latency_call = true;                                   // synchronous: one proof, the caller waits for it
+    const int rc = prove_zk_submit_impl(ctx, witness, canonical, 0, 1, rs_canon);
+    ctx->latency_call = false;
+    ZK_TRY(rc);
+    return prove_zk_collect_impl(ctx, out, 1, nullptr);
+} ZK_GUARD
+
 
 // ================================================================ key generation
 // r1cs_gg_ppzksnark_zok_generator (tcc:277-449) with r1cs_to_qap_instance_map_with_evaluation
@@ -1469,8 +1677,9 @@ int batch_mul_host(const typename C::Affine &base, const std::vector<fe> &scalar
 }
 }  // namespace
 
-extern "C" int zk_keygen(const zk_csr *A, const zk_csr *B, const zk_csr *C, uint32_t nC, uint32_t nIn, uint32_t V,
-                         const uint64_t toxic_canon[20], int device, zk_pk **pk_out, zk_vk **vk_out) try {
+// full: the key keeps the G1 half of the B-query as well (b1_val[i] = Bt_i G1, the knowledge commitments of tcc:371-380)
+static int keygen_impl(const zk_csr *A, const zk_csr *B, const zk_csr *C, uint32_t nC, uint32_t nIn, uint32_t V,
+                       const uint64_t toxic_canon[20], int device, zk_pk **pk_out, zk_vk **vk_out, bool full) {
     if (!A || !B || !C || !toxic_canon || !pk_out || !vk_out) return fail(ZK_ERR_ARG, "null argument");
     if (A->n_rows != nC || B->n_rows != nC || C->n_rows != nC || nIn > V) return fail(ZK_ERR_ARG, "inconsistent constraint system");
     if ((uint64_t)nC + nIn + 1 > (1ull << 28)) return fail(ZK_ERR_ARG, "domain exceeds 2^28");
@@ -1529,6 +1738,7 @@ extern "C" int zk_keygen(const zk_csr *A, const zk_csr *B, const zk_csr *C, uint
         for (uint32_t j = 0; j + 1 < m; j++) { s1.push_back(Fr::mul(tj, zd)); tj = Fr::mul(tj, t); }
     }
     for (uint32_t i = nIn + 1; i <= V; i++) s1.push_back(abc[i]);
+    if (full) for (uint32_t i = 0; i <= V; i++) if (!Fr::is_zero(Bt[i])) s1.push_back(Bt[i]);   // the B-query's G1 half, after L
     G1::Affine g1; g1.x = Fq::from_u64(1); g1.y = Fq::from_u64(2);
     G2::Affine g2;
     g2.x.c0 = fq_from_canon32(G2_GEN_CANON[0]); g2.x.c1 = fq_from_canon32(G2_GEN_CANON[1]);
@@ -1542,12 +1752,21 @@ extern "C" int zk_keygen(const zk_csr *A, const zk_csr *B, const zk_csr *C, uint
     vk->gamma_abc.assign(o1.begin() + k, o1.begin() + k + nIn + 1); k += nIn + 1;
     pk->a_val.assign(o1.begin() + k, o1.begin() + k + pk->a_idx.size()); k += pk->a_idx.size();
     pk->H.assign(o1.begin() + k, o1.begin() + k + (m - 1)); k += m - 1;
-    pk->L.assign(o1.begin() + k, o1.end());
+    pk->L.assign(o1.begin() + k, o1.begin() + k + (V - nIn)); k += V - nIn;
+    if (full) { pk->b1_val.assign(o1.begin() + k, o1.end()); pk->full = true; }
     pk->beta_g2 = o2[0]; pk->delta_g2 = o2[2];
     pk->b_val.assign(o2.begin() + 3, o2.end());
     vk->alpha_g1 = pk->alpha_g1; vk->beta_g2 = o2[0]; vk->gamma_g2 = o2[1]; vk->delta_g2 = o2[2];
     *pk_out = pk.release(); *vk_out = vk.release();
     return ZK_OK;
+}
+extern "C" int zk_keygen(const zk_csr *A, const zk_csr *B, const zk_csr *C, uint32_t nC, uint32_t nIn, uint32_t V,
+                         const uint64_t toxic_canon[20], int device, zk_pk **pk_out, zk_vk **vk_out) try {
+    return keygen_impl(A, B, C, nC, nIn, V, toxic_canon, device, pk_out, vk_out, false);
+} ZK_GUARD
+extern "C" int zk_keygen_full(const zk_csr *A, const zk_csr *B, const zk_csr *C, uint32_t nC, uint32_t nIn, uint32_t V,
+                              const uint64_t toxic_canon[20], int device, zk_pk **pk_out, zk_vk **vk_out) try {
+    return keygen_impl(A, B, C, nC, nIn, V, toxic_canon, device, pk_out, vk_out, true);
 } ZK_GUARD
 
 // ================================================================ witness completion on the GPU

@@ -63,6 +63,8 @@ EXPORTS = [
     "zk_domain_size", "zk_ctx_create", "zk_ctx_create_sized", "zk_ctx_destroy",
     "zk_prove", "zk_prove_timed", "zk_prove_partial", "zk_prove_partial_timed", "zk_prove_combine", "zk_prove_submit", "zk_prove_collect", "zk_proof_to_json",
     "zk_prove_batch", "zk_prove_batch_submit", "zk_prove_batch_submit_resident", "zk_prove_batch_collect",
+    "zk_pk_load_raw_full", "zk_pk_save_raw_full", "zk_pk_is_full", "zk_keygen_full",
+    "zk_prove_zk", "zk_prove_zk_batch", "zk_prove_zk_batch_submit", "zk_prove_zk_batch_submit_resident", "zk_prove_zk_batch_collect",
     "zk_wplan_create", "zk_wplan_create_hinted", "zk_wplan_solve", "zk_wplan_free", "zk_dev_alloc", "zk_dev_free", "zk_dev_upload", "zk_dev_download",
     "zk_chain_submit", "zk_chain_device", "zk_h_from_chains_submit", "zk_h_device", "zk_chain_wait", "zk_prove_submit_with_h", "zk_prove_submit_defer_h", "zk_prove_submit_h", "zk_prove_abort",
     "zk_prove_submit_pinned", "zk_prove_batch_submit_pinned", "zk_host_alloc", "zk_host_free", "zk_host_register", "zk_host_unregister",
@@ -172,6 +174,19 @@ class ProvingKey:
         """writeToFile<ProvingKeyT> (src/utils.hpp:166-173)."""
         _check(_lib.zk_pk_save_raw(self._h, os.fsencode(path), codec))
 
+    def is_full(self):
+        """True for a key that holds the G1 half of the B-query (load_proving_key(full=True), keygen(full=True)): it can make
+        zero-knowledge proofs"""
+        return bool(_lib.zk_pk_is_full(self._h))
+
+    def b1_val(self):
+        """the G1 half of the B-query (nB x 8 u64, the indices of b_idx); empty for a nozk key"""
+        return self.part(11, (self.nB if self.is_full() else 0, 8))
+
+    def save_raw_full(self, path, codec=0):
+        """the full (zero-knowledge) key stream, tcc:53-90, the A-query re-densified over its domain; a nozk key is an error"""
+        _check(_lib.zk_pk_save_raw_full(self._h, os.fsencode(path), codec))
+
     def close(self):
         if self._h is not None and _lib is not None:
             _lib.zk_pk_free(self._h)
@@ -184,12 +199,13 @@ class ProvingKey:
             pass
 
 
-def load_proving_key(pk_file, codec=0):
+def load_proving_key(pk_file, codec=0, full=False):
     """ethsnarks::load_proving_key (src/stubs.cpp:36-39).  A missing file is an error here
-    (the reference asserts, src/utils.hpp:180)."""
+    (the reference asserts, src/utils.hpp:180).  full=True: the file is the FULL key stream (tcc:53-90); the key keeps the G1
+    half of the B-query and can make zero-knowledge proofs (ProverContext.prove_zk)."""
     lib = load_library(_lib_path_loaded)
     h = C.c_void_p()
-    _check(lib.zk_pk_load_raw(os.fsencode(pk_file), codec, C.byref(h)))
+    _check((lib.zk_pk_load_raw_full if full else lib.zk_pk_load_raw)(os.fsencode(pk_file), codec, C.byref(h)))
     return ProvingKey(h)
 
 
@@ -277,9 +293,10 @@ def _csr_structs(r1cs, keep):
     return csr(r1cs.A), csr(r1cs.B), csr(r1cs.C)
 
 
-def keygen(r1cs, toxic=None, seed=None, device=0):
+def keygen(r1cs, toxic=None, seed=None, device=0, full=False):
     """r1cs_gg_ppzksnark_zok_generator + nozk conversion (tcc:277-449, hpp:209-233) on the GPU.
-    toxic = (t, alpha, beta, gamma, delta) ints; or seed -> 5 SplitMix64 draws; default os.urandom."""
+    toxic = (t, alpha, beta, gamma, delta) ints; or seed -> 5 SplitMix64 draws; default os.urandom.
+    full=True: the key also keeps the G1 half of the B-query (zk_keygen_full), for zero-knowledge proofs."""
     lib = load_library(_lib_path_loaded)
     from .fields import FR, ints_to_limbs
     if toxic is None:
@@ -293,17 +310,21 @@ def keygen(r1cs, toxic=None, seed=None, device=0):
     keep = []
     a, b, c = _csr_structs(r1cs, keep)
     pk, vk = C.c_void_p(), C.c_void_p()
-    _check(lib.zk_keygen(C.byref(a), C.byref(b), C.byref(c), C.c_uint32(r1cs.nC), C.c_uint32(r1cs.nIn), C.c_uint32(r1cs.V),
-                         _p64(tox), device, C.byref(pk), C.byref(vk)))
+    _check((lib.zk_keygen_full if full else lib.zk_keygen)(C.byref(a), C.byref(b), C.byref(c), C.c_uint32(r1cs.nC), C.c_uint32(r1cs.nIn),
+                                                         C.c_uint32(r1cs.V), _p64(tox), device, C.byref(pk), C.byref(vk)))
     return ProvingKey(pk), VerificationKey(vk)
 
 
-def stub_genkeys_from_pb(r1cs, pk_file, vk_file, **kw):
-    """ethsnarks::stub_genkeys_from_pb (src/stubs.cpp:77-87): vk JSON + nozk .raw proving key."""
-    pk, vk = keygen(r1cs, **kw)
+def stub_genkeys_from_pb(r1cs, pk_file, vk_file, full=False, **kw):
+    """ethsnarks::stub_genkeys_from_pb (src/stubs.cpp:77-87): vk JSON + nozk .raw proving key (full=True: the full key stream,
+    for zero-knowledge proofs; load it with load_proving_key(pk_file, full=True))."""
+    pk, vk = keygen(r1cs, full=full, **kw)
     with open(vk_file, "wb") as f:                     # vk2json_file, src/export.cpp:148-155
         f.write(vk.to_json().encode())
-    pk.save_raw(pk_file)
+    if full:
+        pk.save_raw_full(pk_file)
+    else:
+        pk.save_raw(pk_file)
     return 0
 
 
@@ -425,6 +446,66 @@ class ProverContext:
     def submit_staged(self):
         """zk_prove_submit_staged: start the staged proof (no upload on its critical path); collect() / collect_batch(k) as usual"""
         _check(_lib.zk_prove_submit_staged(self._h))
+
+    # ---- zero-knowledge proofs (contexts of a full key): rs = list of (r, s) ints, a (k, 8) u64 array of canonical limbs
+    # (r then s), or None: drawn by the library from the operating system's CSPRNG
+    @staticmethod
+    def _rs(rs, k):
+        if rs is None:
+            return None
+        if isinstance(rs, np.ndarray):
+            a = _c64(rs).reshape(-1)
+        else:
+            from .fields import ints_to_limbs
+            a = np.ascontiguousarray(ints_to_limbs([int(v) for pair in rs for v in pair]), dtype=np.uint64).reshape(-1)
+        if a.size != 8 * k:
+            raise ValueError("rs must hold one (r, s) pair per proof (%d)" % k)
+        return a
+
+    def prove_zk_struct(self, witness, rs=None, canonical=False):
+        """zk_prove_zk: one zero-knowledge proof -> ZkProof; rs = [(r, s)] or None"""
+        w = self._w(witness)
+        r = self._rs(rs, 1)
+        proof = ZkProof()
+        _check(_lib.zk_prove_zk(self._h, _p64(w), int(canonical), _p64(r) if r is not None else None, C.byref(proof)))
+        return proof
+
+    def prove_zk(self, witness, rs=None, canonical=False):
+        """zero-knowledge proof JSON of one witness (r, s given as rs = [(r, s)] or (r, s), else drawn by the library)"""
+        if rs is not None and not isinstance(rs, np.ndarray) and len(rs) == 2 and not hasattr(rs[0], "__len__"):
+            rs = [rs]
+        w = _c64(witness).reshape(-1, 4)
+        return proof_to_json(self.prove_zk_struct(w, rs, canonical), w[1:1 + self.r1cs.nIn], canonical)
+
+    def prove_zk_batch_structs(self, witnesses, rs=None, canonical=False):
+        w, k = self._wk(witnesses)
+        r = self._rs(rs, k)
+        proofs = (ZkProof * k)()
+        _check(_lib.zk_prove_zk_batch(self._h, _p64(w), C.c_uint32(k), int(canonical), _p64(r) if r is not None else None, proofs))
+        return list(proofs)
+
+    def prove_zk_batch(self, witnesses, rs=None, canonical=False):
+        """zk_prove_zk_batch: k zero-knowledge proofs through one launch sequence -> list of proof JSON strings"""
+        w = _c64(witnesses).reshape(-1, self.r1cs.V + 1, 4)
+        return [proof_to_json(p, w[i, 1:1 + self.r1cs.nIn], canonical) for i, p in enumerate(self.prove_zk_batch_structs(w, rs, canonical))]
+
+    def submit_zk_batch(self, witnesses=None, rs=None, canonical=False, device_ptr=None, k=None):
+        """zk_prove_zk_batch_submit (or _resident with device_ptr + k): returns k; collect with collect_zk_batch(k)"""
+        if device_ptr is not None:
+            r = self._rs(rs, k)
+            _check(_lib.zk_prove_zk_batch_submit_resident(self._h, C.c_void_p(device_ptr), C.c_uint32(k), int(canonical),
+                                                          _p64(r) if r is not None else None))
+            return k
+        w, k = self._wk(witnesses)
+        r = self._rs(rs, k)
+        _check(_lib.zk_prove_zk_batch_submit(self._h, _p64(w), C.c_uint32(k), int(canonical), _p64(r) if r is not None else None))
+        return k
+
+    def collect_zk_batch(self, k):
+        """wait for the zero-knowledge batch in flight: (list of k ZkProof, timings dict); proof_to_json makes the JSON"""
+        proofs, t = (ZkProof * k)(), ZkTimings()
+        _check(_lib.zk_prove_zk_batch_collect(self._h, proofs, C.c_uint32(k), C.byref(t)))
+        return list(proofs), t.as_dict()
 
     def info(self):
         """window bits / windows / buckets per query, shared-sort flags, domain size (zk_ctx_info)"""

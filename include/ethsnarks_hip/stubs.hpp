@@ -4,6 +4,7 @@
 //   ethsnarks::load_proving_key(const char*)                      src/stubs.hpp:18,  src/stubs.cpp:36-39
 //   ethsnarks::get_domain(pb, pk, config)                         src/stubs.hpp:21,  src/stubs.cpp:61-75
 //   ethsnarks::prove(ProverContextT&, ProtoboardT&)               src/stubs.hpp:19,  src/stubs.cpp:42-47
+//   ethsnarks::load_proving_key_full / prove_zk                   zero-knowledge proofs from the full key (no counterpart in the fork)
 //   ethsnarks::stub_genkeys_from_pb(pb, pk_file, vk_file)         src/stubs.hpp:16,  src/stubs.cpp:77-87
 //   ethsnarks::stub_prove_from_pb(pb, pk_raw)                     upstream wrapper, src/pinocchio/main.cpp:10,41
 //   ethsnarks::stub_main_prove<GadgetT>(prog, argc, argv)         CLI helper shaped like stub_main_genkeys, src/stubs.hpp:36-55
@@ -296,6 +297,35 @@ inline std::string prove_const(ProverContextT &context, const ProtoboardT &pb) {
 }
 }  // namespace detail
 inline std::string prove(ProverContextT &context, ProtoboardT &pb) { return detail::prove_const(context, pb); }
+
+// Zero-knowledge proofs (libsnark's r1cs_gg_ppzksnark_prover, upstream ethsnarks; the fork's prove() above has no randomisation):
+// load_proving_key_full reads the FULL key stream (tcc:53-90), which keeps the G1 half of the B-query; prove_zk returns the proof JSON
+// of prove() with r, s drawn per proof from the operating system's CSPRNG.  The verifier is unchanged (stub_verify).
+inline ProvingKeyT load_proving_key_full(const char *pk_file) {
+    zk_pk *h = nullptr;
+#if defined(CURVE_MCL_BN128)
+    zk_check(zk_pk_load_raw_full(pk_file, ZK_CODEC_MCL_BN128, &h));
+#else
+    zk_check(zk_pk_load_raw_full(pk_file, ZK_CODEC_ALT_BN128, &h));
+#endif
+    return ProvingKeyT(h);
+}
+namespace detail {
+inline std::string prove_zk_const(ProverContextT &context, const ProtoboardT &pb) {
+    ensure_context(context, pb);
+    const Witness w(pb);
+    zk_proof proof;
+    zk_check(zk_prove_zk(context.ctx.get(), w.ptr, w.canonical, nullptr, &proof));
+    const uint32_t nIn = (uint32_t)pb.constraint_system.num_inputs();
+    size_t len = 0;
+    zk_proof_to_json(&proof, w.ptr + 4, nIn, w.canonical, nullptr, 0, &len);
+    std::string out(len + 1, '\0');
+    zk_check(zk_proof_to_json(&proof, w.ptr + 4, nIn, w.canonical, &out[0], out.size(), &len));
+    out.resize(len);
+    return out;
+}
+}  // namespace detail
+inline std::string prove_zk(ProverContextT &context, ProtoboardT &pb) { return detail::prove_zk_const(context, pb); }
 
 // Throughput form of prove() (no reference counterpart: the reference's ProverContext is one synchronous prover per thread,
 // hpp:279-291).  N contexts of ONE key and ONE constraint system stay in flight on the GPU; submit() hands over the values of a

@@ -142,6 +142,14 @@ int zk_pk_bellman2ethsnarks(const char *bellman_pk_json, const char *pk_raw);
  * pk_mcl2nozk (src/export.cpp:399-408: nozk conversion of hpp:209-233, written with the MCL codec) */
 int zk_pk_alt2mcl(const char *alt_pk_file, const char *mcl_pk_file);
 int zk_pk_mcl2nozk(const char *mcl_pk_file, const char *nozk_pk_file);
+/* the FULL key stream (tcc:53-90) as a proving key for zero-knowledge proofs (zk_prove_zk*):
+ *   zk_pk_load_raw_full  reads it (same codec rules as full_load): the key zk_pk_mcl2nozk would make (A-query sparsified, B-query's
+ *                        G2 half) plus the G1 half of the B-query (zk_pk_part 11); it proves without zero knowledge as well
+ *   zk_pk_save_raw_full  writes the full stream again, the A-query re-densified over its domain; ZK_ERR_ARG for a nozk key
+ *   zk_pk_is_full        1 for a key that holds the G1 half of the B-query, else 0 */
+int zk_pk_load_raw_full(const char *path, int codec, zk_pk **out);
+int zk_pk_save_raw_full(const zk_pk *pk, const char *path, int codec);
+int zk_pk_is_full(const zk_pk *pk);
 int zk_pk_from_parts(const uint64_t *alpha_g1, const uint64_t *beta_g1, const uint64_t *beta_g2,
                      const uint64_t *delta_g1, const uint64_t *delta_g2,
                      uint32_t a_domain, uint32_t nA, const uint32_t *a_idx, const uint64_t *a_val,
@@ -149,7 +157,8 @@ int zk_pk_from_parts(const uint64_t *alpha_g1, const uint64_t *beta_g1, const ui
                      uint32_t nH, const uint64_t *H, uint32_t nL, const uint64_t *L, zk_pk **out);
 /* sizes[0..5] = A.domain, nA, B.domain, nB, nH, nL */
 int zk_pk_sizes(const zk_pk *pk, uint32_t sizes[6]);
-/* which: 0 alpha_g1 1 beta_g1 2 beta_g2 3 delta_g1 4 delta_g2 5 A.idx 6 A.val 7 B.idx 8 B.val 9 H 10 L */
+/* which: 0 alpha_g1 1 beta_g1 2 beta_g2 3 delta_g1 4 delta_g2 5 A.idx 6 A.val 7 B.idx 8 B.val 9 H 10 L
+ *        11 B1.val: the G1 half of the B-query (nB x 8 u64, same indices as B.val; full keys only, else empty) */
 const void *zk_pk_part(const zk_pk *pk, int which);
 void zk_pk_free(zk_pk *pk);
 
@@ -159,6 +168,9 @@ void zk_pk_free(zk_pk *pk);
  * Fr::random_element(), tcc:283-287).  Generators: G1 (1, 2), G2 the standard alt_bn128 generator. */
 int zk_keygen(const zk_csr *A, const zk_csr *B, const zk_csr *C, uint32_t nC, uint32_t nIn, uint32_t V,
               const uint64_t toxic_canon[20], int device, zk_pk **pk_out, zk_vk **vk_out);
+/* the same key, full: it also holds B1.val[i] = Bt_i G1 (zk_pk_part 11), what zero-knowledge proofs need */
+int zk_keygen_full(const zk_csr *A, const zk_csr *B, const zk_csr *C, uint32_t nC, uint32_t nIn, uint32_t V,
+                   const uint64_t toxic_canon[20], int device, zk_pk **pk_out, zk_vk **vk_out);
 int zk_vk_to_json(const zk_vk *vk, char *buf, size_t cap, size_t *len);
 /* vk_from_json / proof_from_json (src/import.cpp:161-223): "0x" hex or decimal strings, Fq2 as [c1, c0].
  * zk_proof_from_json: the proof's public inputs come back canonical (4 x u64 each) in inputs_canon[0 .. *n_inputs);
@@ -204,6 +216,20 @@ int zk_prove_batch(zk_ctx *ctx, const uint64_t *witnesses, uint32_t k, int canon
 int zk_prove_batch_submit(zk_ctx *ctx, const uint64_t *witnesses, uint32_t k, int canonical);
 int zk_prove_batch_submit_resident(zk_ctx *ctx, const void *d_witnesses, uint32_t k, int canonical);
 int zk_prove_batch_collect(zk_ctx *ctx, zk_partials *out, uint32_t k, zk_timings *t);
+/* ---- zero-knowledge proofs (libsnark's r1cs_gg_ppzksnark_prover; upstream ethsnarks): with two random scalars r, s per proof
+ *   A = alpha1 + sum w_i A_i + r delta1,  B = beta2 + sum w_i B_i + s delta2,  C = sum h_j H_j + sum_{i>nIn} w_i L_i + s A + r B1 - r s delta1
+ * where B1 = beta1 + sum w_i B1_i + s delta1 uses the G1 half of the B-query.  r = s = 0 gives the zk_prove bytes; the verifier is unchanged.
+ * Contexts created from a full key only (zk_pk_load_raw_full / zk_keygen_full), unsharded (ZK_ERR_ARG otherwise).  The blinding runs on the
+ * device.  A zero-knowledge proof in flight is collected with zk_prove_zk_batch_collect (also for k = 1), a plain one with
+ * zk_prove_collect / zk_prove_batch_collect: the other collect returns ZK_ERR_ARG.  The library clears its copies of r, s once the proof
+ * is collected (or dropped) and never logs them.
+ * rs_canon: per proof {r, s} as canonical 4 x u64 each (k x 8 u64), every value < the Fr modulus (else ZK_ERR_ARG);
+ * NULL = drawn per proof from the operating system's CSPRNG (getrandom(2), 64 bytes reduced mod r). */
+int zk_prove_zk(zk_ctx *ctx, const uint64_t *witness, int canonical, const uint64_t *rs_canon, zk_proof *out);
+int zk_prove_zk_batch(zk_ctx *ctx, const uint64_t *witnesses, uint32_t k, int canonical, const uint64_t *rs_canon, zk_proof *out);
+int zk_prove_zk_batch_submit(zk_ctx *ctx, const uint64_t *witnesses, uint32_t k, int canonical, const uint64_t *rs_canon);
+int zk_prove_zk_batch_submit_resident(zk_ctx *ctx, const void *d_witnesses, uint32_t k, int canonical, const uint64_t *rs_canon);
+int zk_prove_zk_batch_collect(zk_ctx *ctx, zk_proof *out, uint32_t k, zk_timings *t);
 /* ---- sharded latency mode, SURVEY 8(e) option 2: the three transform chains of the witness map (row evaluations of A, B or C,
  * iFFT, cosetFFT) run on three different ranks instead of being replicated on all of them.
  *   zk_chain_submit         queue chain `which` (0 A, 1 B, 2 C) of this witness; its m results end up at zk_chain_device (A, B: evaluations on
