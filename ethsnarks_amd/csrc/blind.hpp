@@ -100,6 +100,9 @@ struct BlindG2Args {
     uint32_t k;
 };
 
+// (a second unit that wants the fixed-base helpers above only -- verify_gpu.cpp -- defines ZK_BLIND_NO_KERNELS: the kernels below are
+// plain definitions and belong to one unit)
+#ifndef ZK_BLIND_NO_KERNELS
 // r delta1, s delta1, -(r s) delta1 of every proof: quad q = 3 p + j computes product j of proof p
 __global__ void __launch_bounds__(BLIND_BLOCK)
 k_zk_blind_fixed(const G1::Affine *__restrict__ delta1, const fe *__restrict__ rs_in, G1::XYZZ *__restrict__ out, uint32_t k) {
@@ -155,6 +158,7 @@ k_zk_blind_g2(BlindG2Args a) {
     B = G2::addQ<BLIND_Q>(B, blind_fixed<G2>(s, a.delta2, ql), ql);
     if (ql == 0) a.out[p] = B;
 }
+#endif  // ZK_BLIND_NO_KERNELS
 
 // host: the fixed-base table of `base`, T[w][d - 1] = d 2^(c w) base (canonical affine)
 template <class C>

@@ -70,6 +70,7 @@ EXPORTS = [
     "zk_prove_submit_pinned", "zk_prove_batch_submit_pinned", "zk_host_alloc", "zk_host_free", "zk_host_register", "zk_host_unregister",
     "zk_prove_submit_resident", "zk_prove_stage", "zk_prove_stage_pinned", "zk_prove_submit_staged", "zk_ctx_info", "zk_ctx_table_info", "zk_ctx_partials_device", "zk_prove_collect_device", "zk_prove_combine_device", "zk_launch_count", "zk_profile_begin", "zk_profile_end", "zk_device_info", "zk_device_pci_bus_id",
     "zk_verify",
+    "zk_vctx_create", "zk_vctx_destroy", "zk_verify_batch", "zk_verify_batch_json", "zk_pairing_check", "zk_pairing_tower_op",
     "zk_ntt", "zk_witness_map", "zk_msm_g1", "zk_msm_g2", "zk_field_mul", "zk_fr_convert",
 ]
 
@@ -639,6 +640,63 @@ def stub_verify(vk_json, proof_json):
     return ok.value == 1
 
 
+class Verifier:
+    """zk_vctx: batch verifier of ONE verification key on the GPU (HIP pairing kernels).  vk: a VerificationKey (keygen, vk_from_json)
+    or the vk2json text.  verify(list of proof_to_json texts) -> list[bool], the verdicts stub_verify gives one by one."""
+
+    def __init__(self, vk, device=0, max_batch=64):
+        lib = load_library(_lib_path_loaded)
+        own = None
+        if isinstance(vk, (str, bytes)):
+            own = vk = vk_from_json(vk if isinstance(vk, str) else vk.decode())
+        h = C.c_void_p()
+        try:
+            _check(lib.zk_vctx_create(vk._h, int(device), C.c_uint32(max_batch), C.byref(h)))
+        finally:
+            if own is not None:
+                own.close()
+        self._h, self.max_batch = h, int(max_batch)
+
+    def verify(self, proofs_json):
+        texts = [p.encode() if isinstance(p, str) else bytes(p) for p in proofs_json]
+        k = len(texts)
+        arr = (C.c_char_p * max(k, 1))(*texts)
+        out = (C.c_uint8 * max(k, 1))()
+        _check(_lib.zk_verify_batch_json(self._h, arr, C.c_uint32(k), out))
+        return [bool(out[i]) for i in range(k)]
+
+    def verify_structs(self, proofs, inputs_canon):
+        """proofs: sequence of ZkProof; inputs_canon: (k, nIn, 4) canonical limbs (zk_verify_batch)"""
+        k = len(proofs)
+        arr = (ZkProof * max(k, 1))(*proofs)
+        inp = _c64(inputs_canon).reshape(-1)
+        out = (C.c_uint8 * max(k, 1))()
+        _check(_lib.zk_verify_batch(self._h, arr, _p64(inp) if inp.size else None, C.c_uint32(k), out))
+        return [bool(out[i]) for i in range(k)]
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and _lib is not None:
+            _lib.zk_vctx_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def stub_verify_batch(vk_json, proofs_json, device=0):
+    """the verdicts of stub_verify for every proof of a list, computed in one batch on the GPU"""
+    if not proofs_json:
+        return []
+    v = Verifier(vk_json, device=device, max_batch=len(proofs_json))
+    try:
+        return v.verify(proofs_json)
+    finally:
+        v.close()
+
+
 def stub_test_proof_verify(r1cs, witness, **kw):
     """ethsnarks::stub_test_proof_verify (src/stubs.cpp:135-148): keygen -> prove -> verify in memory,
     with the context fully initialised (the reference forgets constraint_system and domain)."""
@@ -796,4 +854,22 @@ def field_mul(a, b, field="fr", device=0):
     a = _c64(a); b = _c64(b)
     out = np.zeros_like(a)
     _check(load_library(_lib_path_loaded).zk_field_mul(_p64(a), _p64(b), _p64(out), C.c_uint32(a.size // 4), 0 if field == "fr" else 1, device))
+    return out
+
+
+def pairing_check(g1, g2, n, device=0):
+    """zk_pairing_check: g1 (k n, 8) / g2 (k n, 16) affine Montgomery limbs, all-zero = infinity; list of k bools, True iff the product
+    of the n pairings of row group i is one"""
+    g1 = _c64(g1).reshape(-1, 8); g2 = _c64(g2).reshape(-1, 16)
+    k = g1.shape[0] // n if n else 0
+    out = (C.c_uint8 * max(k, 1))()
+    _check(load_library(_lib_path_loaded).zk_pairing_check(_p64(g1), _p64(g2), C.c_uint32(n), C.c_uint32(k), device, out))
+    return [bool(out[i]) for i in range(k)]
+
+
+def pairing_tower_op(op, a, b=None):
+    """zk_pairing_tower_op (host code): a, b as (12, 4) canonical limbs in tower order; returns (12, 4)"""
+    a = _c64(a).reshape(12, 4)
+    out = np.zeros((12, 4), dtype=np.uint64)
+    _check(load_library(_lib_path_loaded).zk_pairing_tower_op(int(op), _p64(a), _p64(_c64(b).reshape(12, 4)) if b is not None else None, _p64(out)))
     return out

@@ -11,6 +11,7 @@
 //   ethsnarks::stub_genkeys<GadgetT>, stub_main_genkeys<GadgetT>  src/stubs.hpp:23-55
 //   ethsnarks::stub_main_verify(prog, argc, argv)                 src/stubs.hpp:12,  src/stubs.cpp:90-132
 //   ethsnarks::stub_verify(vk_json, proof_json)                   src/stubs.hpp:10,  src/stubs.cpp:16-33
+//   ethsnarks::stub_verify_batch(vk_json, proofs)                 many proofs of one key in one batch on the GPU (no counterpart in the fork)
 //   ethsnarks::stub_test_proof_verify(pb)                         src/stubs.hpp:14,  src/stubs.cpp:135-148 (context fully initialised)
 //
 // so that a gadget binary written against ethsnarks keeps its source: it includes this header instead of
@@ -138,6 +139,24 @@ inline bool stub_verify(const char *vk_json, const char *proof_json) {
     int ok = 0;
     zk_check(zk_verify(vk_json, proof_json, &ok));      // malformed JSON throws, as the reference's parser does
     return ok == 1;
+}
+// the verdicts of stub_verify for many proofs of ONE key, computed in one batch on the GPU (zk_vctx: HIP pairing kernels).  A proof text
+// that does not parse is `false` here (stub_verify throws); a malformed key throws.
+inline std::vector<bool> stub_verify_batch(const char *vk_json, const std::vector<std::string> &proofs_json) {
+    std::vector<bool> verdicts(proofs_json.size(), false);
+    if (proofs_json.empty()) return verdicts;
+    zk_vk *vk = nullptr;
+    zk_check(zk_vk_from_json(vk_json, &vk));
+    std::unique_ptr<zk_vk, void (*)(zk_vk *)> vk_own(vk, zk_vk_free);
+    zk_vctx *ctx = nullptr;
+    zk_check(zk_vctx_create(vk, (int)hip_device(), (uint32_t)proofs_json.size(), &ctx));
+    std::unique_ptr<zk_vctx, void (*)(zk_vctx *)> ctx_own(ctx, zk_vctx_destroy);
+    std::vector<const char *> texts;
+    for (const std::string &p : proofs_json) texts.push_back(p.c_str());
+    std::vector<uint8_t> ok(proofs_json.size(), 0);
+    zk_check(zk_verify_batch_json(ctx, texts.data(), (uint32_t)texts.size(), ok.data()));
+    for (size_t i = 0; i < ok.size(); i++) verdicts[i] = ok[i] == 1;
+    return verdicts;
 }
 
 // ProvingKeyT: owning handle of the nozk proving key (r1cs_gg_ppzksnark_zok_proving_key_nozk, hpp:171-274)

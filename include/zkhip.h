@@ -67,6 +67,7 @@ typedef struct zk_pk zk_pk;
 typedef struct zk_vk zk_vk;
 typedef struct zk_ctx zk_ctx;
 typedef struct zk_wplan zk_wplan;
+typedef struct zk_vctx zk_vctx;
 
 typedef struct {
     uint32_t n_rows;
@@ -294,6 +295,19 @@ int zk_proof_to_json(const zk_proof *proof, const uint64_t *inputs, uint32_t nIn
 int zk_verify(const char *vk_json, const char *proof_json, int *accepted);
 /* same symbol and signature as the reference's libethsnarks_verify (src/verify_dll.cpp:3-10) */
 bool ethsnarks_verify(const char *vk_json, const char *proof_json);
+/* ---- batch verifier on the device: k proofs of ONE key per call, the pairing work in HIP kernels (csrc/pairing.hpp, verify_gpu.cpp).
+ * zk_vctx_create uploads the key once: window tables of gammaABC[1..], line tables of gamma and delta, e(alpha, beta), staging for
+ * max_batch (1 .. 2^20) proofs; a key with a point off its curve is ZK_ERR_FORMAT.  The verdict of every proof equals zk_verify's on
+ * the text zk_proof_to_json writes for it (the coordinates; the *_inf flags are not read): an all-zero point is infinity and enters the
+ * product as 1, the (0, 1) the prover writes for an infinite point is on neither curve and is rejected, as are coordinates >= q, inputs >= r, points off their curves and B outside the order-r subgroup.
+ * A rejected proof does not disturb its neighbours.  One batch at a time per context (calls on one context are serialised).
+ *   proofs: k records; inputs_canon: k x nIn x 4 u64 canonical, nIn = |gammaABC| - 1 (may be NULL when nIn = 0);
+ *   accepted: k bytes, 1 = verifies.  ZK_ERR_ARG for null arguments, k = 0, k > max_batch. */
+int zk_vctx_create(const zk_vk *vk, int device, uint32_t max_batch, zk_vctx **out);
+void zk_vctx_destroy(zk_vctx *v);
+int zk_verify_batch(zk_vctx *v, const zk_proof *proofs, const uint64_t *inputs_canon, uint32_t k, uint8_t *accepted);
+/* the same from k proof_to_json texts; a text that does not parse or has the wrong number of inputs gets 0 */
+int zk_verify_batch_json(zk_vctx *v, const char *const *proof_json, uint32_t k, uint8_t *accepted);
 
 /* ---- witness completion on the GPU (the reference fills pb.values on the host, gadget by gadget).  For a
  * constraint system in "solved order" -- every constraint reads known variables in A and B and introduces at most one new
@@ -341,6 +355,13 @@ int zk_msm_g2(const uint64_t *bases, const uint64_t *scalars, uint32_t n, uint32
 /* host-only: n Fr elements between canonical and Montgomery form, in place (adapters whose field objects are opaque) */
 int zk_fr_convert(uint64_t *io, uint32_t n, int to_montgomery);
 int zk_field_mul(const uint64_t *a, const uint64_t *b, uint64_t *out, uint32_t n, int field /* 0 Fr, 1 Fq */, int device);
+/* k independent products of n pairs (affine Montgomery, all-zero = infinity, points in the order-r groups; n k <= 2^24):
+ * is_one[i] = 1 iff prod_j e(g1[i*n+j], g2[i*n+j]) = 1 */
+int zk_pairing_check(const uint64_t *g1, const uint64_t *g2, uint32_t n, uint32_t k, int device, uint8_t *is_one);
+/* host-only: one operation of the pairing's Fq12 tower (csrc/pairing.hpp) on canonical elements, 12 x 4 u64 in the order
+ * c0.c0.c0, c0.c0.c1, c0.c1.c0, ... (coefficient a_ij of v^i w^j at index 6 j + 2 i + {0: real, 1: u part}).
+ * op: 0 a b, 1 a^2, 2 1/a, 3..5 a^(q^1..3), 6 cyclotomic square, 7 a^((q^6-1)(q^2+1)), 8 final exponentiation, 9 conjugate (b unused but for 0) */
+int zk_pairing_tower_op(int op, const uint64_t *a, const uint64_t *b, uint64_t *out);
 
 #ifdef __cplusplus
 }
