@@ -6,3 +6,11 @@ src/r1cs_gg_ppzksnark_zok/r1cs_gg_ppzksnark_zok.tcc:451-550.  Compute is hand-wr
 thin host-side binding used by tests/ and bench.py.
 """
 __version__ = "0.4.0"
+
+
+def __getattr__(name):
+    # MerkleTree (ethsnarks_amd.merkle) is exported lazily: importing the package alone must not need numpy or the library
+    if name in ("MerkleTree", "MerkleProof"):
+        from . import merkle
+        return getattr(merkle, name)
+    raise AttributeError(name)

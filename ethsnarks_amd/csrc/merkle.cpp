@@ -1,0 +1,383 @@
+// merkle.cpp -- the device Merkle tree behind zk_mtree_* (include/zkhip.h): storage, placeholders, launch structure.  Kernels: merkle.hpp.
+//
+// Launch structure.  An append of leaves s .. n - 1 re-hashes on level d + 1 the parents s >> (d + 1) .. cnt_{d+1} - 1.  Levels with more than
+// TAIL_BLOCK such parents get one k_mimc_merkle_level launch each; every level above them runs inside ONE k_mimc_merkle_tail launch, so a
+// bulk build costs (large levels + 1) hashing launches and a single append exactly one.  An update works the same way from the sorted,
+// de-duplicated parent lists the host derives from the indices (k x depth integers).  ZK_MTREE_NO_TAIL=1 in the environment at creation makes
+// a tree launch every level on its own instead: the form the tail kernel is measured against (profiles/merkle_tree.txt).
+#include <algorithm>
+#include <memory>
+#include <mutex>
+#include <vector>
+#include <stdlib.h>
+#include <string.h>
+#include "bn254.hpp"
+#include "merkle.hpp"
+#include "../../include/ethsnarks_hip/gadgets.hpp"              // the streaming sha256 and keccak256 (host code)
+#include "../../include/zkhip.h"
+
+using namespace zk;
+using namespace zk::merkle;
+
+static_assert(sizeof(zk_mtree_layout) == sizeof(Layout), "zk_mtree_layout and merkle::Layout are one struct");
+
+namespace {
+int mfail(int code, const char *msg) { return fail_msg(code, msg); }
+
+int mt_use_device(int device) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return mfail(ZK_ERR_NODEVICE, "no HIP device (this library has no CPU path)");
+    if (device < 0 || device >= n) return mfail(ZK_ERR_ARG, "device ordinal out of range");
+    ZK_HIP(hipSetDevice(device));
+    return ZK_OK;
+}
+
+// a 32-byte big-endian digest as a field element: value mod r, Montgomery (the Montgomery product by R^2 reduces any value < 2^256)
+fe digest_to_mont(const uint8_t d[32]) {
+    fe v;
+    for (int i = 0; i < 8; i++) v.l[i] = ((uint32_t)d[28 - 4 * i] << 24) | ((uint32_t)d[29 - 4 * i] << 16) | ((uint32_t)d[30 - 4 * i] << 8) | d[31 - 4 * i];
+    return Fr::to_mont(v);
+}
+
+// round constants: C_0 = keccak256(keccak256("mimc")), C_{i+1} = keccak256(C_i) (src/gadgets/mimc.hpp:260-290);
+// IV_i = running sha256 of "MerkleTree-" || le16(i) (merkletree.py:36-44).  Montgomery; rc first, then iv.
+struct Consts { fe rc[MIMC_ROUNDS]; fe iv[MAX_DEPTH]; };
+const Consts &host_consts() {
+    static Consts c;
+    static std::once_flag once;
+    std::call_once(once, [] {
+        uint8_t dg[32], nx[32];
+        ethsnarks::hashes::keccak256((const uint8_t *)"mimc", 4, dg);
+        for (uint32_t i = 0; i < MIMC_ROUNDS; i++) {
+            ethsnarks::hashes::keccak256(dg, 32, nx);
+            memcpy(dg, nx, 32);
+            c.rc[i] = digest_to_mont(dg);
+        }
+        ethsnarks::hashes::sha256 h;
+        for (uint32_t i = 0; i < MAX_DEPTH; i++) {
+            const uint8_t tag[13] = {'M', 'e', 'r', 'k', 'l', 'e', 'T', 'r', 'e', 'e', '-', (uint8_t)(i & 0xff), (uint8_t)(i >> 8)};
+            h.update(tag, sizeof(tag));
+            h.digest(dg);
+            c.iv[i] = digest_to_mont(dg);
+        }
+    });
+    return c;
+}
+
+// unique(d, index) = sha256(be16(d) || be240(index)) mod r, Montgomery
+fe placeholder(uint32_t d, uint64_t index) {
+    uint8_t msg[32] = {0}, dg[32];
+    msg[0] = (uint8_t)(d >> 8); msg[1] = (uint8_t)d;
+    for (int k = 0; k < 8; k++) msg[31 - k] = (uint8_t)(index >> (8 * k));
+    ethsnarks::hashes::sha256 h;
+    h.update(msg, 32);
+    h.digest(dg);
+    return digest_to_mont(dg);
+}
+
+bool all_below_modulus(const uint64_t *v, uint64_t n) {
+    for (uint64_t i = 0; i < n; i++) { fe x; memcpy(x.l, v + 4 * i, 32); if (!fr_lt_modulus(x)) return false; }
+    return true;
+}
+}  // namespace
+
+struct zk_mtree {
+    int device = 0;
+    uint32_t depth = 0;
+    uint64_t n = 0;                                             // leaves
+    bool use_tail = true;
+    hipStream_t st = nullptr;
+    fe *lvl[MAX_DEPTH + 1] = {nullptr};                         // level d: cap[d] elements, level_count(n, d) of them in use
+    uint64_t cap[MAX_DEPTH + 1] = {0};
+    fe **d_lvl = nullptr;                                       // the pointers above, for the kernels
+    fe *d_consts = nullptr;                                     // Consts
+    fe *d_ph = nullptr;                                         // MAX_DEPTH placeholders: unique(d, level_count(n, d))
+    uint32_t *d_bad = nullptr;
+    void *d_scratch = nullptr; size_t scratch_cap = 0;          // indices, lists, gathered paths: grows, never shrinks
+    ~zk_mtree() {
+        for (fe *p : lvl) if (p) (void)hipFree(p);
+        void *bufs[] = {d_lvl, d_consts, d_ph, d_bad, d_scratch};
+        for (void *b : bufs) if (b) (void)hipFree(b);
+        if (st) (void)hipStreamDestroy(st);
+    }
+    uint64_t level_cap_max(uint32_t d) const { return (uint64_t)1 << (depth - d); }
+    TreeView view() const {
+        TreeView v;
+        v.lvl = d_lvl; v.ph = d_ph; v.rc = d_consts; v.iv = d_consts + MIMC_ROUNDS; v.n = n; v.depth = depth;
+        return v;
+    }
+};
+
+namespace {
+int mt_scratch(zk_mtree *t, size_t bytes) {
+    if (bytes <= t->scratch_cap) return ZK_OK;
+    void *p = nullptr;
+    const size_t want = std::max(bytes, 2 * t->scratch_cap);
+    if (hipMalloc(&p, want) != hipSuccess) return mfail(ZK_ERR_NOMEM, "device allocation failed (Merkle tree scratch)");
+    if (t->d_scratch) (void)hipFree(t->d_scratch);
+    t->d_scratch = p; t->scratch_cap = want;
+    return ZK_OK;
+}
+
+// placeholders for a tree of n_new leaves, queued on the stream (before the kernels that read them)
+int mt_put_placeholders(zk_mtree *t, uint64_t n_new) {
+    fe ph[MAX_DEPTH];
+    for (uint32_t d = 0; d < MAX_DEPTH; d++) ph[d] = d < t->depth ? placeholder(d, level_count(n_new, d)) : Fr::zero();
+    ZK_HIP(hipMemcpyAsync(t->d_ph, ph, sizeof(ph), hipMemcpyHostToDevice, t->st));
+    ZK_HIP(hipStreamSynchronize(t->st));                        // (ph lives on this stack frame)
+    return ZK_OK;
+}
+
+// room for n_new leaves on every level: all new buffers are claimed before one is put in place, so a failure changes nothing
+int mt_grow(zk_mtree *t, uint64_t n_new) {
+    fe *fresh[MAX_DEPTH + 1] = {nullptr};
+    uint64_t fresh_cap[MAX_DEPTH + 1] = {0};
+    bool any = false;
+    for (uint32_t d = 0; d <= t->depth; d++) {
+        const uint64_t need = level_count(n_new, d);
+        if (need <= t->cap[d]) continue;
+        const uint64_t want = std::min(std::max(need, 2 * t->cap[d]), t->level_cap_max(d));
+        if (hipMalloc(&fresh[d], sizeof(fe) * want) != hipSuccess) {
+            for (uint32_t e = 0; e < d; e++) if (fresh[e]) (void)hipFree(fresh[e]);
+            (void)hipGetLastError();
+            return mfail(ZK_ERR_NOMEM, "device allocation failed (Merkle tree nodes)");
+        }
+        fresh_cap[d] = want; any = true;
+    }
+    if (!any) return ZK_OK;
+    for (uint32_t d = 0; d <= t->depth; d++) {
+        if (!fresh[d]) continue;
+        const uint64_t used = level_count(t->n, d);
+        if (used) ZK_HIP(hipMemcpyAsync(fresh[d], t->lvl[d], sizeof(fe) * used, hipMemcpyDeviceToDevice, t->st));
+    }
+    ZK_HIP(hipStreamSynchronize(t->st));
+    for (uint32_t d = 0; d <= t->depth; d++) {
+        if (!fresh[d]) continue;
+        if (t->lvl[d]) (void)hipFree(t->lvl[d]);
+        t->lvl[d] = fresh[d]; t->cap[d] = fresh_cap[d];
+    }
+    ZK_HIP(hipMemcpy(t->d_lvl, t->lvl, sizeof(t->lvl), hipMemcpyHostToDevice));
+    return ZK_OK;
+}
+
+// hash the ancestors of the leaves s_old .. t->n - 1 (t->n already counts them, the placeholders are in place)
+int mt_hash_appended(zk_mtree *t, uint64_t s_old) {
+    const TreeView v = t->view();
+    uint32_t d = 0;
+    for (; d < t->depth; d++) {
+        const uint64_t j0 = s_old >> (d + 1), nj = level_count(t->n, d + 1) - j0;
+        if (t->use_tail && nj <= TAIL_BLOCK) break;
+        ZK_LAUNCH(k_mimc_merkle_level, zk_div_up(nj, LEVEL_BLOCK), LEVEL_BLOCK, t->st, v, d, j0, nj);
+    }
+    if (d < t->depth) ZK_LAUNCH_SYNC(k_mimc_merkle_tail, 1, TAIL_BLOCK, t->st, v, d, s_old, (const uint64_t *)nullptr, (const uint32_t *)nullptr, 0u);
+    ZK_HIP(hipGetLastError());
+    return ZK_OK;
+}
+
+// leaves: host pointer (checked by the caller) or device pointer
+int mt_append(zk_mtree *t, const void *src, bool resident, uint64_t n, int canonical) {
+    if (n == 0) return ZK_OK;
+    if (n > t->level_cap_max(0) - t->n) return mfail(ZK_ERR_ARG, "the tree is full: more leaves than 2^depth");
+    ZK_TRY(mt_use_device(t->device));
+    const uint64_t s_old = t->n, n_new = s_old + n;
+    ZK_TRY(mt_grow(t, n_new));
+    fe *dst = t->lvl[0] + s_old;                                // slots past the size: a failure below leaves nothing to undo
+    ZK_HIP(hipMemcpyAsync(dst, src, sizeof(fe) * n, resident ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, t->st));
+    if (resident || canonical) {
+        ZK_HIP(hipMemsetAsync(t->d_bad, 0, 4, t->st));
+        ZK_LAUNCH(k_mtree_ingest, zk_div_up(n, LEVEL_BLOCK), LEVEL_BLOCK, t->st, dst, n, canonical, t->d_bad);
+        ZK_HIP(hipGetLastError());
+        if (resident) {
+            uint32_t bad = 0;
+            ZK_HIP(hipMemcpyAsync(&bad, t->d_bad, 4, hipMemcpyDeviceToHost, t->st));
+            ZK_HIP(hipStreamSynchronize(t->st));
+            if (bad) return mfail(ZK_ERR_ARG, "a leaf is not below the Fr modulus");
+        }
+    }
+    ZK_TRY(mt_put_placeholders(t, n_new));
+    t->n = n_new;
+    ZK_TRY(mt_hash_appended(t, s_old));
+    ZK_HIP(hipStreamSynchronize(t->st));
+    return ZK_OK;
+}
+
+int mt_upload_indices(zk_mtree *t, const uint64_t *indices, uint32_t k, size_t extra_bytes) {
+    for (uint32_t i = 0; i < k; i++) if (indices[i] >= t->n) return mfail(ZK_ERR_ARG, "leaf index is not below the size of the tree");
+    ZK_TRY(mt_use_device(t->device));
+    ZK_TRY(mt_scratch(t, sizeof(uint64_t) * (size_t)k + extra_bytes));
+    ZK_HIP(hipMemcpyAsync(t->d_scratch, indices, sizeof(uint64_t) * (size_t)k, hipMemcpyHostToDevice, t->st));
+    return ZK_OK;
+}
+}  // namespace
+
+extern "C" int zk_mtree_create(uint32_t depth, uint64_t reserve_leaves, int device, zk_mtree **out) try {
+    if (!out) return mfail(ZK_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (depth < 1 || depth > MAX_DEPTH) return mfail(ZK_ERR_ARG, "depth must be in 1 .. 29");
+    ZK_TRY(mt_use_device(device));
+    std::unique_ptr<zk_mtree> t(new zk_mtree());
+    t->device = device; t->depth = depth;
+    if (const char *e = getenv("ZK_MTREE_NO_TAIL")) t->use_tail = !(e[0] == '1');
+    ZK_HIP(hipStreamCreateWithFlags(&t->st, hipStreamNonBlocking));
+    const Consts &c = host_consts();
+    if (hipMalloc(&t->d_consts, sizeof(Consts)) != hipSuccess || hipMalloc(&t->d_ph, sizeof(fe) * MAX_DEPTH) != hipSuccess ||
+        hipMalloc(&t->d_lvl, sizeof(t->lvl)) != hipSuccess || hipMalloc(&t->d_bad, 4) != hipSuccess)
+        return mfail(ZK_ERR_NOMEM, "device allocation failed (Merkle tree)");
+    ZK_HIP(hipMemcpy(t->d_consts, &c, sizeof(Consts), hipMemcpyHostToDevice));
+    ZK_TRY(mt_grow(t.get(), std::max<uint64_t>(1, std::min(reserve_leaves, t->level_cap_max(0)))));
+    ZK_TRY(mt_put_placeholders(t.get(), 0));
+    *out = t.release();
+    return ZK_OK;
+} ZK_GUARD
+
+extern "C" void zk_mtree_free(zk_mtree *t) try {
+    if (!t) return;
+    (void)mt_use_device(t->device);
+    delete t;
+} ZK_GUARD_VOID
+
+extern "C" int zk_mtree_size(const zk_mtree *t, uint64_t *n_leaves) try {
+    if (!t || !n_leaves) return mfail(ZK_ERR_ARG, "null argument");
+    *n_leaves = t->n;
+    return ZK_OK;
+} ZK_GUARD
+
+extern "C" int zk_mtree_append(zk_mtree *t, const uint64_t *leaves, uint64_t n, int canonical) try {
+    if (!t || (n && !leaves)) return mfail(ZK_ERR_ARG, "null argument");
+    if (n > t->level_cap_max(0) - t->n) return mfail(ZK_ERR_ARG, "the tree is full: more leaves than 2^depth");
+    if (!all_below_modulus(leaves, n)) return mfail(ZK_ERR_ARG, "a leaf is not below the Fr modulus");
+    return mt_append(t, leaves, false, n, canonical);
+} ZK_GUARD
+
+extern "C" int zk_mtree_append_resident(zk_mtree *t, const void *d_leaves, uint64_t n, int canonical) try {
+    if (!t || (n && !d_leaves)) return mfail(ZK_ERR_ARG, "null argument");
+    return mt_append(t, d_leaves, true, n, canonical);
+} ZK_GUARD
+
+extern "C" int zk_mtree_update(zk_mtree *t, const uint64_t *indices, const uint64_t *leaves, uint32_t k, int canonical) try {
+    if (!t || (k && (!indices || !leaves))) return mfail(ZK_ERR_ARG, "null argument");
+    if (k == 0) return ZK_OK;
+    for (uint32_t i = 0; i < k; i++) if (indices[i] >= t->n) return mfail(ZK_ERR_ARG, "leaf index is not below the size of the tree");
+    if (!all_below_modulus(leaves, k)) return mfail(ZK_ERR_ARG, "a leaf is not below the Fr modulus");
+    // distinct indices in ascending order, each with the value of its last occurrence
+    std::vector<uint32_t> order(k);
+    for (uint32_t i = 0; i < k; i++) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return indices[a] < indices[b]; });
+    std::vector<uint64_t> idx; std::vector<fe> vals;
+    idx.reserve(k); vals.reserve(k);
+    for (uint32_t i = 0; i < k; i++) {
+        if (i + 1 < k && indices[order[i + 1]] == indices[order[i]]) continue;
+        fe v; memcpy(v.l, leaves + 4 * (size_t)order[i], 32);
+        idx.push_back(indices[order[i]]); vals.push_back(canonical ? Fr::to_mont(v) : v);
+    }
+    const uint32_t m = (uint32_t)idx.size(), D = t->depth;
+    // row d: the parents on level d + 1, sorted and distinct (a shift keeps the order)
+    std::vector<uint64_t> lists((size_t)D * m);
+    uint32_t nlist[MAX_DEPTH] = {0};
+    std::vector<uint64_t> cur(idx);
+    for (uint32_t d = 0; d < D; d++) {
+        for (auto &j : cur) j >>= 1;
+        cur.erase(std::unique(cur.begin(), cur.end()), cur.end());
+        nlist[d] = (uint32_t)cur.size();
+        std::copy(cur.begin(), cur.end(), lists.begin() + (size_t)d * m);
+    }
+    ZK_TRY(mt_use_device(t->device));
+    // scratch: idx | lists | nlist | vals
+    const size_t o_lists = sizeof(uint64_t) * m, o_nlist = o_lists + sizeof(uint64_t) * (size_t)D * m, o_vals = (o_nlist + sizeof(nlist) + 31) & ~(size_t)31;
+    ZK_TRY(mt_scratch(t, o_vals + sizeof(fe) * m));
+    char *s = (char *)t->d_scratch;
+    ZK_HIP(hipMemcpyAsync(s, idx.data(), sizeof(uint64_t) * m, hipMemcpyHostToDevice, t->st));
+    ZK_HIP(hipMemcpyAsync(s + o_lists, lists.data(), sizeof(uint64_t) * (size_t)D * m, hipMemcpyHostToDevice, t->st));
+    ZK_HIP(hipMemcpyAsync(s + o_nlist, nlist, sizeof(nlist), hipMemcpyHostToDevice, t->st));
+    ZK_HIP(hipMemcpyAsync(s + o_vals, vals.data(), sizeof(fe) * m, hipMemcpyHostToDevice, t->st));
+    const TreeView v = t->view();
+    ZK_LAUNCH(k_mtree_set_leaves, zk_div_up(m, LEVEL_BLOCK), LEVEL_BLOCK, t->st, v, (const uint64_t *)s, (const fe *)(s + o_vals), m);
+    uint32_t d = 0;
+    for (; d < D; d++) {
+        if (t->use_tail && nlist[d] <= TAIL_BLOCK) break;
+        ZK_LAUNCH(k_mimc_merkle_update, zk_div_up(nlist[d], LEVEL_BLOCK), LEVEL_BLOCK, t->st, v, d, (const uint64_t *)(s + o_lists) + (size_t)d * m, nlist[d]);
+    }
+    if (d < D) ZK_LAUNCH_SYNC(k_mimc_merkle_tail, 1, TAIL_BLOCK, t->st, v, d, (uint64_t)0, (const uint64_t *)(s + o_lists), (const uint32_t *)(s + o_nlist), m);
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipStreamSynchronize(t->st));                        // (the staging vectors live until here)
+    return ZK_OK;
+} ZK_GUARD
+
+extern "C" int zk_mtree_node(const zk_mtree *t, uint32_t level, uint64_t offset, uint64_t out_canon[4]) try {
+    if (!t || !out_canon) return mfail(ZK_ERR_ARG, "null argument");
+    if (level > t->depth || offset >= t->level_cap_max(level)) return mfail(ZK_ERR_ARG, "no such node: level <= depth and offset < 2^(depth - level)");
+    fe v;
+    if (offset < level_count(t->n, level)) {
+        ZK_TRY(mt_use_device(t->device));
+        ZK_HIP(hipMemcpy(&v, t->lvl[level] + offset, sizeof(fe), hipMemcpyDeviceToHost));
+    } else v = placeholder(level, offset);
+    v = Fr::from_mont(v);
+    memcpy(out_canon, v.l, 32);
+    return ZK_OK;
+} ZK_GUARD
+
+extern "C" int zk_mtree_root(const zk_mtree *t, uint64_t root_canon[4]) try {
+    if (!t || !root_canon) return mfail(ZK_ERR_ARG, "null argument");
+    if (t->n == 0) return mfail(ZK_ERR_ARG, "the tree is empty: it has no root");
+    return zk_mtree_node(t, t->depth, 0, root_canon);
+} ZK_GUARD
+
+extern "C" int zk_mtree_paths(const zk_mtree *ct, const uint64_t *indices, uint32_t k, uint64_t *leaves_canon, uint64_t *paths_canon) try {
+    zk_mtree *t = const_cast<zk_mtree *>(ct);                   // (the stream and the scratch buffer; the tree itself is only read)
+    if (!t || (k && !indices)) return mfail(ZK_ERR_ARG, "null argument");
+    if (k == 0) return ZK_OK;
+    const size_t o_leaves = (sizeof(uint64_t) * (size_t)k + 31) & ~(size_t)31, o_paths = o_leaves + sizeof(fe) * (size_t)k;
+    ZK_TRY(mt_upload_indices(t, indices, k, o_paths + sizeof(fe) * (size_t)k * t->depth));
+    char *s = (char *)t->d_scratch;
+    ZK_LAUNCH(k_mtree_gather, zk_div_up((uint64_t)k * (t->depth + 1), LEVEL_BLOCK), LEVEL_BLOCK, t->st, t->view(), (const uint64_t *)s, k, (fe *)(s + o_leaves), (fe *)(s + o_paths));
+    ZK_HIP(hipGetLastError());
+    if (leaves_canon) ZK_HIP(hipMemcpyAsync(leaves_canon, s + o_leaves, sizeof(fe) * (size_t)k, hipMemcpyDeviceToHost, t->st));
+    if (paths_canon) ZK_HIP(hipMemcpyAsync(paths_canon, s + o_paths, sizeof(fe) * (size_t)k * t->depth, hipMemcpyDeviceToHost, t->st));
+    ZK_HIP(hipStreamSynchronize(t->st));
+    return ZK_OK;
+} ZK_GUARD
+
+extern "C" int zk_mtree_fill_witnesses(const zk_mtree *ct, const uint64_t *indices, uint32_t k, void *d_w, uint64_t row_elems, const zk_mtree_layout *layout) try {
+    zk_mtree *t = const_cast<zk_mtree *>(ct);
+    if (!t || (k && !indices) || !d_w || !layout) return mfail(ZK_ERR_ARG, "null argument");
+    if (k == 0) return ZK_OK;
+    if (t->n == 0) return mfail(ZK_ERR_ARG, "the tree is empty: it has no root");
+    const uint64_t D = t->depth;
+    if (layout->n_iv > MAX_DEPTH || row_elems == 0 || layout->root_var >= row_elems || layout->leaf_var >= row_elems || layout->addr_var0 + D > row_elems ||
+        layout->path_var0 + D > row_elems || (uint64_t)layout->iv_var0 + layout->n_iv > row_elems)
+        return mfail(ZK_ERR_ARG, "the layout names a variable outside the witness row");
+    ZK_TRY(mt_upload_indices(t, indices, k, 0));
+    Layout L;
+    memcpy(&L, layout, sizeof(L));
+    ZK_LAUNCH(k_mtree_fill_witness, zk_div_up((uint64_t)k * (3 + 2 * D + L.n_iv), LEVEL_BLOCK), LEVEL_BLOCK, t->st, t->view(), (const uint64_t *)t->d_scratch, k, (fe *)d_w, row_elems, L);
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipStreamSynchronize(t->st));
+    return ZK_OK;
+} ZK_GUARD
+
+extern "C" int zk_mimc_constants(uint64_t *round_constants_canon, uint64_t *ivs_canon) try {
+    const Consts &c = host_consts();
+    if (round_constants_canon) for (uint32_t i = 0; i < MIMC_ROUNDS; i++) { const fe v = Fr::from_mont(c.rc[i]); memcpy(round_constants_canon + 4 * i, v.l, 32); }
+    if (ivs_canon) for (uint32_t i = 0; i < MAX_DEPTH; i++) { const fe v = Fr::from_mont(c.iv[i]); memcpy(ivs_canon + 4 * i, v.l, 32); }
+    return ZK_OK;
+} ZK_GUARD
+
+extern "C" int zk_mimc_hash2(const uint64_t *left, const uint64_t *right, const uint64_t *iv, uint32_t n, int device, uint64_t *out) try {
+    if (!left || !right || !iv || !out) return mfail(ZK_ERR_ARG, "null argument");
+    if (n == 0) return ZK_OK;
+    if (!all_below_modulus(left, n) || !all_below_modulus(right, n) || !all_below_modulus(iv, n)) return mfail(ZK_ERR_ARG, "an operand is not below the Fr modulus");
+    ZK_TRY(mt_use_device(device));
+    const Consts &c = host_consts();
+    struct Buf { fe *p = nullptr; ~Buf() { if (p) (void)hipFree(p); } } in, rc;
+    const size_t bytes = sizeof(fe) * (size_t)n;
+    if (hipMalloc(&in.p, 4 * bytes) != hipSuccess || hipMalloc(&rc.p, sizeof(c.rc)) != hipSuccess) return mfail(ZK_ERR_NOMEM, "device allocation failed");
+    ZK_HIP(hipMemcpy(in.p, left, bytes, hipMemcpyHostToDevice));
+    ZK_HIP(hipMemcpy(in.p + n, right, bytes, hipMemcpyHostToDevice));
+    ZK_HIP(hipMemcpy(in.p + 2 * (size_t)n, iv, bytes, hipMemcpyHostToDevice));
+    ZK_HIP(hipMemcpy(rc.p, c.rc, sizeof(c.rc), hipMemcpyHostToDevice));
+    ZK_LAUNCH(k_mimc_hash2, zk_div_up(n, LEVEL_BLOCK), LEVEL_BLOCK, nullptr, (const fe *)in.p, (const fe *)(in.p + n), (const fe *)(in.p + 2 * (size_t)n), n, (const fe *)rc.p, in.p + 3 * (size_t)n);
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipDeviceSynchronize());
+    ZK_HIP(hipMemcpy(out, in.p + 3 * (size_t)n, bytes, hipMemcpyDeviceToHost));
+    return ZK_OK;
+} ZK_GUARD

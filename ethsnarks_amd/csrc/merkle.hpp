@@ -1,0 +1,172 @@
+// merkle.hpp -- MiMC-e7 Miyaguchi-Preneel hashing and the kernels of the device Merkle tree (merkle.cpp, zk_mtree_* of include/zkhip.h).
+//
+// The tree of ethsnarks/merkletree.py, width 2, MerkleHasher_MiMC: level 0 holds the leaves, node j of level d + 1 is
+//     mimc_hash([n(d, 2j), n(d, 2j + 1)], IV[d])          (src/gadgets/mimc.hpp:352-393, merkletree.py:36-44)
+// and with n leaves level d stores cnt_d = ceil(n / 2^d) nodes.  A node that does not exist reads as the placeholder
+// unique(d, index) = sha256(be16(d) || be240(index)) mod r; extents are prefixes, so a level meets at most ONE placeholder, at index cnt_d,
+// and only when cnt_d is odd.  The host keeps unique(d, cnt_d) for every level in a 29-element device table (TreeView::ph).
+//
+// One node = 2 ciphers x 91 rounds x (2 squarings + 2 products) = 728 Fr products on one dependent chain, VALU-bound like the rest of this
+// code base.  Values are Montgomery and canonical ([0, r)) in memory; a hash runs in the loose domain of bn254.hpp and folds once at the end.
+// The 91 round constants are read from a device table with a wave-uniform index: scalar loads, one copy per wave, no per-lane state.
+//
+// Kernels:
+//   k_mimc_merkle_level   one lane per parent of a contiguous range of one level (bulk build, the levels wider than a workgroup)
+//   k_mimc_merkle_update  the same for a sorted list of parent indices (batched update)
+//   k_mimc_merkle_tail    ONE workgroup walks every remaining level, a barrier between two levels: the upper levels of a tree have fewer
+//                         nodes than a workgroup has lanes and each costs a full chain latency however few nodes it has, so they share a launch
+//   k_mtree_ingest        new leaves: range check (< r), canonical -> Montgomery
+//   k_mtree_set_leaves    scatter updated leaves
+//   k_mtree_gather        leaves and authentication paths of k indices (canonical, for the host)
+//   k_mtree_fill_witness  the membership circuit's inputs of k indices, straight into k rows of a device witness buffer
+//   k_mimc_hash2          n independent two-block hashes (test entry point)
+#pragma once
+#include "bn254.hpp"
+
+namespace zk {
+namespace merkle {
+
+constexpr uint32_t MIMC_ROUNDS = 91;
+constexpr uint32_t MAX_DEPTH = 29;                              // the gadget's IV table has 29 entries (merkle_tree_IVs)
+constexpr uint32_t LEVEL_BLOCK = 64;
+constexpr uint32_t TAIL_BLOCK = 256;                            // a level with at most this many parents goes through the tail kernel
+
+// E_k(x) + k of the reference's mimc(): 91 rounds x <- (x + k + c_i)^7, then + k.  Loose in, loose out.
+ZK_HD fe mimc_cipher(const fe *__restrict__ rc, const fe &x0, const fe &k) {
+    fe x = x0;
+    for (uint32_t i = 0; i < MIMC_ROUNDS; i++) {
+        const fe t = Fr::ladd(Fr::ladd(x, k), rc[i]);
+        const fe t2 = Fr::lsqr(t);
+        const fe t4 = Fr::lsqr(t2);
+        const fe t6 = Fr::lmul(t4, t2);
+        x = Fr::lmul(t6, t);
+    }
+    return Fr::ladd(x, k);
+}
+// Miyaguchi-Preneel over two blocks: k1 = iv + E_iv(l) + l, k2 = k1 + E_k1(r) + r; canonical result
+ZK_HD fe mimc_hash2(const fe *__restrict__ rc, const fe &l, const fe &r, const fe &iv) {
+    const fe k1 = Fr::ladd(Fr::ladd(iv, mimc_cipher(rc, l, iv)), l);
+    const fe k2 = Fr::ladd(Fr::ladd(k1, mimc_cipher(rc, r, k1)), r);
+    return Fr::canon(k2);
+}
+
+ZK_HD bool fr_lt_modulus(const fe &a) {
+    uint64_t br = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) { const uint64_t t = (uint64_t)a.l[i] - FrParams::p(i) - br; br = (t >> 32) & 1; }
+    return br != 0;
+}
+
+// what every kernel knows of a tree: lvl[d] = the nodes of level d (d = 0 .. depth), ph[d] = unique(d, cnt_d), n = leaves
+struct TreeView {
+    fe *const *lvl;
+    const fe *ph, *rc, *iv;
+    uint64_t n;
+    uint32_t depth;
+};
+ZK_HD uint64_t level_count(uint64_t n, uint32_t d) { return (n + (((uint64_t)1 << d) - 1)) >> d; }
+
+// parent j of child level d (the caller guarantees 2 j < cnt_d)
+ZK_D void hash_parent(const TreeView &t, uint32_t d, uint64_t j) {
+    const fe *__restrict__ child = t.lvl[d];
+    const uint64_t cnt = level_count(t.n, d);
+    const fe l = child[2 * j];
+    const fe r = 2 * j + 1 < cnt ? child[2 * j + 1] : t.ph[d];
+    t.lvl[d + 1][j] = mimc_hash2(t.rc, l, r, t.iv[d]);
+}
+
+__global__ void __launch_bounds__(LEVEL_BLOCK)
+k_mimc_merkle_level(TreeView t, uint32_t d, uint64_t j0, uint64_t nj) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= nj) return;
+    hash_parent(t, d, j0 + g);
+}
+
+__global__ void __launch_bounds__(LEVEL_BLOCK)
+k_mimc_merkle_update(TreeView t, uint32_t d, const uint64_t *__restrict__ list, uint32_t nj) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= nj) return;
+    hash_parent(t, d, list[g]);
+}
+
+// child levels d_begin .. depth - 1 in one workgroup.  lists == nullptr: the parents of level d + 1 that cover the leaves s_old .. n - 1
+// (an append); else row d of lists (stride entries apart) holds nlist[d] parent indices (an update).  Every level has at most blockDim.x
+// parents (the host checks); the barrier makes level d + 1 visible to the lanes that hash level d + 2 from it.
+__global__ void __launch_bounds__(TAIL_BLOCK)
+k_mimc_merkle_tail(TreeView t, uint32_t d_begin, uint64_t s_old, const uint64_t *__restrict__ lists, const uint32_t *__restrict__ nlist, uint32_t stride) {
+    for (uint32_t d = d_begin; d < t.depth; d++) {
+        uint64_t j; bool on;
+        if (lists) { on = threadIdx.x < nlist[d]; j = on ? lists[(size_t)d * stride + threadIdx.x] : 0; }
+        else { const uint64_t j0 = s_old >> (d + 1); j = j0 + threadIdx.x; on = j < level_count(t.n, d + 1); }
+        if (on) hash_parent(t, d, j);
+        __syncthreads();
+    }
+}
+
+// leaves in place: bad += 1 for every value >= r (such a value is left as it is); canonical != 0: to Montgomery form
+__global__ void __launch_bounds__(LEVEL_BLOCK)
+k_mtree_ingest(fe *__restrict__ x, uint64_t n, int canonical, uint32_t *__restrict__ bad) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    const fe v = x[g];
+    if (!fr_lt_modulus(v)) { atomicAdd(bad, 1u); return; }
+    if (canonical) x[g] = Fr::to_mont(v);
+}
+
+// lvl[0][idx[i]] = vals[i] (Montgomery, already checked; the host removed duplicate indices)
+__global__ void __launch_bounds__(LEVEL_BLOCK)
+k_mtree_set_leaves(TreeView t, const uint64_t *__restrict__ idx, const fe *__restrict__ vals, uint32_t k) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= k) return;
+    t.lvl[0][idx[g]] = vals[g];
+}
+
+// node (d, o) as a path reads it: the stored node or the level's placeholder (o == cnt_d then)
+ZK_D fe node_or_placeholder(const TreeView &t, uint32_t d, uint64_t o) { return o < level_count(t.n, d) ? t.lvl[d][o] : t.ph[d]; }
+
+// one lane per (index, slot): slot 0 = the leaf -> leaves[i], slot 1 + d = the sibling on level d -> paths[i depth + d]; canonical values
+__global__ void __launch_bounds__(LEVEL_BLOCK)
+k_mtree_gather(TreeView t, const uint64_t *__restrict__ idx, uint32_t k, fe *__restrict__ leaves, fe *__restrict__ paths) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t S = t.depth + 1;
+    if (g >= (uint64_t)k * S) return;
+    const uint32_t i = (uint32_t)(g / S), s = (uint32_t)(g % S);
+    const uint64_t a = idx[i];
+    if (s == 0) leaves[i] = Fr::from_mont(t.lvl[0][a]);
+    else paths[(size_t)i * t.depth + (s - 1)] = Fr::from_mont(node_or_placeholder(t, s - 1, (a >> (s - 1)) ^ 1));
+}
+
+// where the membership circuit keeps its inputs in a witness row (variable indices; zk_mtree_layout of include/zkhip.h)
+struct Layout { uint32_t root_var, addr_var0, path_var0, leaf_var, iv_var0, n_iv; };
+
+// one lane per (row, slot): ONE, the root, depth address bits, depth path elements, the leaf, n_iv IVs.  Nothing else of the row is written.
+__global__ void __launch_bounds__(LEVEL_BLOCK)
+k_mtree_fill_witness(TreeView t, const uint64_t *__restrict__ idx, uint32_t k, fe *__restrict__ w, uint64_t row_elems, Layout L) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t D = t.depth, S = 3 + 2 * D + L.n_iv;
+    if (g >= (uint64_t)k * S) return;
+    const uint32_t i = (uint32_t)(g / S);
+    uint32_t s = (uint32_t)(g % S);
+    const uint64_t a = idx[i];
+    fe *__restrict__ row = w + (size_t)i * row_elems;
+    if (s == 0) { row[0] = Fr::one(); return; }
+    if (s == 1) { row[L.root_var] = t.lvl[D][0]; return; }
+    s -= 2;
+    if (s < D) { row[L.addr_var0 + s] = ((a >> s) & 1) ? Fr::one() : Fr::zero(); return; }
+    s -= D;
+    if (s < D) { row[L.path_var0 + s] = node_or_placeholder(t, s, (a >> s) ^ 1); return; }
+    s -= D;
+    if (s == 0) { row[L.leaf_var] = t.lvl[0][a]; return; }
+    row[L.iv_var0 + (s - 1)] = t.iv[s - 1];
+}
+
+// out[i] = mimc_hash([l[i], r[i]], iv[i]); canonical in and out (the host has checked the operands against r)
+__global__ void __launch_bounds__(LEVEL_BLOCK)
+k_mimc_hash2(const fe *__restrict__ l, const fe *__restrict__ r, const fe *__restrict__ iv, uint32_t n, const fe *__restrict__ rc, fe *__restrict__ out) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    out[g] = Fr::from_mont(mimc_hash2(rc, Fr::to_mont(l[g]), Fr::to_mont(r[g]), Fr::to_mont(iv[g])));
+}
+
+}  // namespace merkle
+}  // namespace zk

@@ -1,0 +1,194 @@
+"""MiMC Merkle tree in device memory (zk_mtree_* of include/zkhip.h; kernels in csrc/merkle.hpp).
+
+The surface of the reference's ethsnarks/merkletree.py (MerkleTree over MerkleHasher_MiMC, width 2): append, update, proof, root,
+leaf(depth, offset) -- plus the bulk forms a GPU needs: extend, update_many, proofs, and fill_witnesses, which writes the inputs of the
+membership circuit (gadgets.merkle_membership_circuit) for k leaves straight into a device witness buffer, ready for
+prover.WitnessPlan.solve and ProverContext.submit_batch(device_ptr=...).  All hashing runs in HIP kernels; there is no CPU path.
+"""
+import ctypes as C
+from collections import namedtuple
+
+import numpy as np
+
+from . import fields as F
+from . import gadgets as G
+from . import prover as P
+
+MAX_DEPTH = 29
+_SYMBOLS = ("zk_mtree_create", "zk_mtree_free", "zk_mtree_size", "zk_mtree_append", "zk_mtree_append_resident", "zk_mtree_update",
+            "zk_mtree_root", "zk_mtree_node", "zk_mtree_paths", "zk_mtree_fill_witnesses", "zk_mimc_constants", "zk_mimc_hash2")
+
+
+class Layout(C.Structure):
+    """zk_mtree_layout: the variable indices of the membership circuit's inputs in a witness row"""
+    _fields_ = [(n, C.c_uint32) for n in ("root_var", "addr_var0", "path_var0", "leaf_var", "iv_var0", "n_iv")]
+
+
+def membership_layout(depth):
+    """the allocation order of merkle_membership_circuit / merkle_path_authenticator: root, address bits, path, leaf, 29 IVs"""
+    return Layout(1, 2, 2 + depth, 2 + 2 * depth, 3 + 2 * depth, 29)
+
+
+def _lib():
+    """the loaded library, checked for the tree's entry points (the CPU emulation of the prover alone does not have them)"""
+    lib = P.load_library(P._lib_path_loaded)
+    missing = [n for n in _SYMBOLS if not hasattr(lib, n)]
+    if missing:
+        raise ImportError("%s has no Merkle tree entry points (%s ...): it was built without csrc/merkle.cpp" % (P._lib_path_loaded or P.LIB_PATH, missing[0]))
+    return lib
+
+
+def _leaf_limbs(values):
+    """ints in [0, r) -> canonical (n, 4) limbs; a numpy (n, 4) uint64 array is taken as canonical limbs as it is"""
+    if isinstance(values, np.ndarray) and values.dtype == np.uint64 and values.ndim == 2 and values.shape[1] == 4:
+        return np.ascontiguousarray(values)
+    vals = [int(v) for v in values]
+    for v in vals:
+        if not 0 <= v < F.FR:
+            raise ValueError("leaf %d is not in [0, r)" % v)
+    return F.ints_to_limbs(vals) if vals else np.zeros((0, 4), dtype=np.uint64)
+
+
+def mimc_constants():
+    """(round constants, level IVs) as the kernels use them"""
+    rc = np.zeros((91, 4), dtype=np.uint64)
+    iv = np.zeros((MAX_DEPTH, 4), dtype=np.uint64)
+    P._check(_lib().zk_mimc_constants(P._p64(rc), P._p64(iv)))
+    return F.limbs_to_ints(rc), F.limbs_to_ints(iv)
+
+
+def mimc_hash2(left, right, iv, device=0):
+    """[mimc_hash([l, r], iv) for l, r, iv in zip(left, right, iv)] on the device"""
+    a, b, c = (F.ints_to_limbs([int(v) for v in x]) for x in (left, right, iv))
+    if not (len(a) == len(b) == len(c)):
+        raise ValueError("left, right and iv differ in length")
+    out = np.zeros_like(a)
+    if len(a):
+        P._check(_lib().zk_mimc_hash2(P._p64(a), P._p64(b), P._p64(c), C.c_uint32(len(a)), int(device), P._p64(out)))
+    return F.limbs_to_ints(out)
+
+
+class MerkleProof(namedtuple("MerkleProof", "leaf address path")):
+    """leaf, address bits (level 0 first) and siblings of one leaf"""
+
+    def verify(self, root):
+        return G.merkle_root(self.leaf, self.address, self.path, G.merkle_ivs(MAX_DEPTH)) == root
+
+
+class MerkleTree:
+    """A tree of n_items = 2^depth leaf slots (depth 1 .. 29) resident on `device`."""
+
+    def __init__(self, n_items, device=0, reserve=0):
+        n_items = int(n_items)
+        if n_items < 2 or n_items & (n_items - 1):
+            raise ValueError("n_items must be a power of two >= 2")
+        self.n_items, self.depth, self.device = n_items, n_items.bit_length() - 1, int(device)
+        h = C.c_void_p()
+        P._check(_lib().zk_mtree_create(C.c_uint32(self.depth), C.c_uint64(reserve), self.device, C.byref(h)))
+        self._h = h
+
+    # ---- size
+    def __len__(self):
+        n = C.c_uint64(0)
+        P._check(P._lib.zk_mtree_size(self._h, C.byref(n)))
+        return int(n.value)
+
+    # ---- writing
+    def extend(self, leaves, n=None, canonical=True):
+        """append many leaves: ints, canonical (n, 4) limbs, or a prover.DeviceBuffer holding n elements (Montgomery unless canonical)"""
+        if isinstance(leaves, P.DeviceBuffer):
+            if n is None:
+                n = leaves.nbytes // 32
+            P._check(P._lib.zk_mtree_append_resident(self._h, C.c_void_p(leaves.ptr), C.c_uint64(n), int(canonical)))
+            return
+        a = _leaf_limbs(leaves)
+        if len(a):
+            P._check(P._lib.zk_mtree_append(self._h, P._p64(a), C.c_uint64(len(a)), int(canonical)))
+
+    def append(self, leaf):
+        """returns the index of the new leaf"""
+        i = len(self)
+        self.extend([leaf])
+        return i
+
+    def update_many(self, indices, leaves):
+        """leaves[j] replaces leaf indices[j]; the last occurrence of an index wins"""
+        idx = np.ascontiguousarray([int(i) for i in indices], dtype=np.uint64)
+        a = _leaf_limbs(leaves)
+        if len(idx) != len(a):
+            raise ValueError("indices and leaves differ in length")
+        if len(idx):
+            P._check(P._lib.zk_mtree_update(self._h, P._p64(idx), P._p64(a), C.c_uint32(len(idx)), 1))
+
+    def update(self, index, leaf):
+        self.update_many([index], [leaf])
+
+    def __setitem__(self, index, leaf):
+        self.update(index, leaf)
+
+    # ---- reading
+    def leaf(self, depth, offset):
+        """any node: level `depth` (0 = leaves), position `offset`; the placeholder where the tree holds nothing yet"""
+        out = np.zeros(4, dtype=np.uint64)
+        P._check(P._lib.zk_mtree_node(self._h, C.c_uint32(depth), C.c_uint64(offset), P._p64(out)))
+        return F.limbs_to_ints(out)[0]
+
+    def __getitem__(self, index):
+        index = int(index)
+        if not 0 <= index < len(self):
+            raise IndexError("leaf index out of range")
+        return self.leaf(0, index)
+
+    @property
+    def root(self):
+        if len(self) == 0:
+            return None
+        out = np.zeros(4, dtype=np.uint64)
+        P._check(P._lib.zk_mtree_root(self._h, P._p64(out)))
+        return F.limbs_to_ints(out)[0]
+
+    def proofs(self, indices):
+        idx = np.ascontiguousarray([int(i) for i in indices], dtype=np.uint64)
+        k = len(idx)
+        if k == 0:
+            return []
+        leaves = np.zeros((k, 4), dtype=np.uint64)
+        paths = np.zeros((k * self.depth, 4), dtype=np.uint64)
+        P._check(P._lib.zk_mtree_paths(self._h, P._p64(idx), C.c_uint32(k), P._p64(leaves), P._p64(paths)))
+        lv, pv, D = F.limbs_to_ints(leaves), F.limbs_to_ints(paths), self.depth
+        return [MerkleProof(lv[j], [(int(idx[j]) >> d) & 1 for d in range(D)], pv[j * D:(j + 1) * D]) for j in range(k)]
+
+    def proof(self, index):
+        return self.proofs([index])[0]
+
+    def fill_witnesses(self, indices, device_buffer, r1cs_or_layout=None, row_elems=None):
+        """rows 0 .. k - 1 of a device witness buffer get ONE, the root, the address bits, the path, the leaf and the IVs of the given
+        leaves (Montgomery).  r1cs_or_layout: the constraint system of merkle_membership_circuit(depth) (row = V + 1 elements, its
+        allocation order), or a Layout together with row_elems.  device_buffer: a prover.DeviceBuffer or a device pointer."""
+        if isinstance(r1cs_or_layout, Layout):
+            layout = r1cs_or_layout
+            if row_elems is None:
+                raise ValueError("a Layout needs row_elems")
+        else:
+            layout = membership_layout(self.depth)
+            if row_elems is None:
+                if r1cs_or_layout is None:
+                    raise ValueError("give the constraint system, or a Layout and row_elems")
+                row_elems = r1cs_or_layout.V + 1
+        idx = np.ascontiguousarray([int(i) for i in indices], dtype=np.uint64)
+        ptr = device_buffer.ptr if isinstance(device_buffer, P.DeviceBuffer) else int(device_buffer)
+        if isinstance(device_buffer, P.DeviceBuffer) and len(idx) * int(row_elems) * 32 > device_buffer.nbytes:
+            raise ValueError("the device buffer is smaller than k rows")
+        if len(idx):
+            P._check(P._lib.zk_mtree_fill_witnesses(self._h, P._p64(idx), C.c_uint32(len(idx)), C.c_void_p(ptr), C.c_uint64(row_elems), C.byref(layout)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and P._lib is not None:
+            P._lib.zk_mtree_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

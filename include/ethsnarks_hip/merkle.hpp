@@ -1,0 +1,90 @@
+// ethsnarks_hip/merkle.hpp -- the device MiMC Merkle tree of libzkhip.so (zk_mtree_* of zkhip.h) as a C++ object: the tree of the reference's
+// ethsnarks/merkletree.py (width 2, MerkleHasher_MiMC) kept in GPU memory and hashed by HIP kernels.  Header-only, RAII, no libsnark types:
+// a field element is a zk_fr = 4 x u64 little-endian limbs, canonical (not Montgomery) wherever it crosses this interface.
+//
+//   ethsnarks::MerkleTreeHIP tree(29);                 depth 1 .. 29, capacity 2^depth
+//   tree.append(leaf); tree.extend(leaves); tree.update(i, leaf); tree.update_many(indices, leaves);
+//   tree.size(); tree.empty(); tree.root();            root() throws on an empty tree (the reference's root is None then)
+//   tree.node(level, offset);                          the reference's tree.leaf(depth, offset), placeholders included
+//   tree.proof(i) / tree.proofs(indices);              leaf, address bits, path (level 0 first)
+//   tree.fill_witnesses(indices, d_w, row_elems);      inputs of merkle_path_authenticator for k leaves into a device witness buffer, for
+//                                                      zk_wplan_solve and zk_prove_batch_submit_resident
+// Every failure is a mtree_error carrying the C ABI's code and zk_last_error()'s text.
+#pragma once
+#include <zkhip.h>
+
+#include <array>
+#include <cstdint>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+namespace ethsnarks {
+
+typedef std::array<uint64_t, 4> zk_fr;
+
+struct mtree_error : std::runtime_error {
+    int code;
+    explicit mtree_error(int c) : std::runtime_error(std::string(zk_strerror(c)) + ": " + zk_last_error()), code(c) {}
+};
+
+struct MerkleProofHIP {
+    zk_fr leaf;
+    std::vector<bool> address;                                   // bit d: the node is the right child on level d
+    std::vector<zk_fr> path;
+};
+
+class MerkleTreeHIP {
+    zk_mtree *h_ = nullptr;
+    uint32_t depth_ = 0;
+    static void check(int rc) { if (rc != ZK_OK) throw mtree_error(rc); }
+
+public:
+    explicit MerkleTreeHIP(uint32_t depth, uint64_t reserve_leaves = 0, int device = 0) : depth_(depth) { check(zk_mtree_create(depth, reserve_leaves, device, &h_)); }
+    ~MerkleTreeHIP() { zk_mtree_free(h_); }
+    MerkleTreeHIP(const MerkleTreeHIP &) = delete;
+    MerkleTreeHIP &operator=(const MerkleTreeHIP &) = delete;
+    MerkleTreeHIP(MerkleTreeHIP &&o) noexcept : h_(o.h_), depth_(o.depth_) { o.h_ = nullptr; }
+
+    uint32_t depth() const { return depth_; }
+    uint64_t size() const { uint64_t n = 0; check(zk_mtree_size(h_, &n)); return n; }
+    bool empty() const { return size() == 0; }
+    zk_mtree *handle() const { return h_; }
+
+    uint64_t append(const zk_fr &leaf) { const uint64_t i = size(); check(zk_mtree_append(h_, leaf.data(), 1, 1)); return i; }
+    void extend(const std::vector<zk_fr> &leaves) { if (!leaves.empty()) check(zk_mtree_append(h_, leaves[0].data(), leaves.size(), 1)); }
+    // n field elements already in device memory (Montgomery unless canonical)
+    void extend_resident(const void *d_leaves, uint64_t n, bool canonical = false) { check(zk_mtree_append_resident(h_, d_leaves, n, canonical ? 1 : 0)); }
+    void update(uint64_t index, const zk_fr &leaf) { check(zk_mtree_update(h_, &index, leaf.data(), 1, 1)); }
+    // an index that occurs more than once takes the value of its last occurrence
+    void update_many(const std::vector<uint64_t> &indices, const std::vector<zk_fr> &leaves) {
+        if (indices.size() != leaves.size()) throw std::invalid_argument("update_many: indices and leaves differ in length");
+        if (!indices.empty()) check(zk_mtree_update(h_, indices.data(), leaves[0].data(), (uint32_t)indices.size(), 1));
+    }
+
+    zk_fr root() const { zk_fr r; check(zk_mtree_root(h_, r.data())); return r; }
+    zk_fr node(uint32_t level, uint64_t offset) const { zk_fr r; check(zk_mtree_node(h_, level, offset, r.data())); return r; }
+    std::vector<MerkleProofHIP> proofs(const std::vector<uint64_t> &indices) const {
+        const size_t k = indices.size();
+        std::vector<MerkleProofHIP> out(k);
+        if (!k) return out;
+        std::vector<zk_fr> leaves(k), paths(k * depth_);
+        check(zk_mtree_paths(h_, indices.data(), (uint32_t)k, leaves[0].data(), paths[0].data()));
+        for (size_t j = 0; j < k; j++) {
+            out[j].leaf = leaves[j];
+            out[j].path.assign(paths.begin() + (long)(j * depth_), paths.begin() + (long)((j + 1) * depth_));
+            for (uint32_t d = 0; d < depth_; d++) out[j].address.push_back((indices[j] >> d) & 1);
+        }
+        return out;
+    }
+    MerkleProofHIP proof(uint64_t index) const { return proofs({index})[0]; }
+
+    // the allocation order of merkle_path_authenticator: root, address bits, path, leaf, 29 IVs
+    zk_mtree_layout membership_layout() const { return zk_mtree_layout{1, 2, 2 + depth_, 2 + 2 * depth_, 3 + 2 * depth_, 29}; }
+    void fill_witnesses(const std::vector<uint64_t> &indices, void *d_w, uint64_t row_elems) const { fill_witnesses(indices, d_w, row_elems, membership_layout()); }
+    void fill_witnesses(const std::vector<uint64_t> &indices, void *d_w, uint64_t row_elems, const zk_mtree_layout &layout) const {
+        if (!indices.empty()) check(zk_mtree_fill_witnesses(h_, indices.data(), (uint32_t)indices.size(), d_w, row_elems, &layout));
+    }
+};
+
+}  // namespace ethsnarks

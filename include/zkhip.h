@@ -337,6 +337,44 @@ int zk_dev_free(void *p);
 int zk_dev_upload(void *dst, const void *src, size_t bytes);
 int zk_dev_download(void *dst, const void *src, size_t bytes);
 
+/* ---- MiMC Merkle tree in device memory (csrc/merkle.hpp, merkle.cpp): the tree of ethsnarks/merkletree.py, width 2, MerkleHasher_MiMC.
+ * depth D = 1 .. 29, capacity 2^D leaves; level 0 holds the leaves, node j of level d + 1 = mimc_hash([n(d, 2j), n(d, 2j+1)], IV[d]); with n
+ * leaves level d stores ceil(n / 2^d) nodes and a node that does not exist reads as unique(d, index) = sha256(be16(d) || be240(index)) mod r
+ * (merkletree.py:24-34).  Nodes stay in Montgomery form in device memory; storage grows geometrically per level (reserve_leaves is a hint).
+ * Codes: ZK_ERR_ARG for a null handle or argument, depth outside 1 .. 29, more leaves than the capacity, an index >= the size, a leaf >= r
+ * (host leaves are checked before any device work, resident leaves by the kernel that takes them in), the root of an empty tree, a layout
+ * that leaves the row; ZK_ERR_NOMEM when device memory runs out.  A call that fails with one of these leaves the tree as it was.
+ * A zk_mtree is single-threaded like a zk_ctx.  Its work runs on a stream of its own and is complete when a call returns.
+ *   zk_mtree_append            n leaves (n x 4 u64; Montgomery unless canonical != 0) become leaves size .. size + n - 1
+ *   zk_mtree_append_resident   the same from device memory (the buffer is only read)
+ *   zk_mtree_update            leaves[i] replaces leaf indices[i] and the ancestors are hashed again; an index that occurs more than
+ *                              once takes the value of its LAST occurrence
+ *   zk_mtree_root              canonical root; ZK_ERR_ARG for an empty tree (the reference's root is None then)
+ *   zk_mtree_node              the reference's tree.leaf(level, offset): any node, level 0 .. D, offset < 2^(D - level), placeholders included
+ *   zk_mtree_paths             for each of k indices the leaf and the D siblings (level 0 first), canonical; the address bits of index i
+ *                              are (i >> d) & 1.  Either output may be NULL
+ *   zk_mtree_fill_witnesses    for each of k indices writes into row j of a device witness buffer (row_elems Fr elements apart, Montgomery):
+ *                              ONE at variable 0, the root, D address bits, D path elements, the leaf and n_iv (<= 29) level IVs at the
+ *                              variable indices of the layout -- and nothing else of the row.  What zk_wplan_solve completes and
+ *                              zk_prove_batch_submit_resident proves.  merkle_path_authenticator's allocation order (root, address bits,
+ *                              path, leaf, IVs) is the layout {1, 2, 2 + D, 2 + 2 D, 3 + 2 D, 29}
+ *   zk_mimc_constants          host-only: the 91 round constants and 29 level IVs the kernels use, canonical (either may be NULL)
+ *   zk_mimc_hash2              out[i] = mimc_hash([left[i], right[i]], iv[i]) on the device, canonical in and out; an operand >= r is ZK_ERR_ARG */
+typedef struct zk_mtree zk_mtree;
+typedef struct { uint32_t root_var, addr_var0, path_var0, leaf_var, iv_var0, n_iv; } zk_mtree_layout;
+int zk_mtree_create(uint32_t depth, uint64_t reserve_leaves, int device, zk_mtree **out);
+void zk_mtree_free(zk_mtree *t);
+int zk_mtree_size(const zk_mtree *t, uint64_t *n_leaves);
+int zk_mtree_append(zk_mtree *t, const uint64_t *leaves, uint64_t n, int canonical);
+int zk_mtree_append_resident(zk_mtree *t, const void *d_leaves, uint64_t n, int canonical);
+int zk_mtree_update(zk_mtree *t, const uint64_t *indices, const uint64_t *leaves, uint32_t k, int canonical);
+int zk_mtree_root(const zk_mtree *t, uint64_t root_canon[4]);
+int zk_mtree_node(const zk_mtree *t, uint32_t level, uint64_t offset, uint64_t out_canon[4]);
+int zk_mtree_paths(const zk_mtree *t, const uint64_t *indices, uint32_t k, uint64_t *leaves_canon /* k x 4 */, uint64_t *paths_canon /* k x depth x 4 */);
+int zk_mtree_fill_witnesses(const zk_mtree *t, const uint64_t *indices, uint32_t k, void *d_w, uint64_t row_elems, const zk_mtree_layout *layout);
+int zk_mimc_constants(uint64_t *round_constants_canon /* 91 x 4 */, uint64_t *ivs_canon /* 29 x 4 */);
+int zk_mimc_hash2(const uint64_t *left, const uint64_t *right, const uint64_t *iv, uint32_t n, int device, uint64_t *out);
+
 /* ---- measurement aids (bench.py): kernel launches issued by this library so far; between zk_profile_begin() and
  * zk_profile_end() every launch is bracketed by a HIP event pair on its own stream -- the sum of the kernel durations
  * (overlapping kernels counted each), their number, and "name calls ms" lines per kernel come back */
