@@ -408,6 +408,9 @@ struct Field {
 #endif
 #if !(defined(__HIP_DEVICE_COMPILE__) && !defined(ZK_NO_ASM))
     static ZK_HD void lmul_x2(const fe &a, const fe &b, const fe &c, const fe &d, fe &r0, fe &r1) { r0 = lmul(a, b); r1 = lmul(c, d); }
+    static ZK_HD void lmul2_x2(const fe &a, const fe &b, const fe &c, const fe &d, const fe &e, const fe &f, const fe &g, const fe &h, fe &r0, fe &r1) {
+        r0 = lmul2(a, b, c, d); r1 = lmul2(e, f, g, h);
+    }
 #endif
     // two independent products of the G1 formulas as one call (dual issue on the device; PAIRS: whether the formulas use it)
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(ZK_NO_ASM) && !defined(ZK_NO_X2) && !defined(ZK_G1_NO_X2)

@@ -248,4 +248,8 @@ struct MsmWork {
     }
 };
 
+// arithmetic probe (include/zkhip.h, test infrastructure): one Curve<F> primitive per kernel instantiation over n cases, operands as
+// given (device pointers, field elements back to back), raw results; idx as in the header's ZK_PROBE_G1 / ZK_PROBE_G2 table
+template <class C> int curve_probe(int idx, const fe *d_in, uint32_t n, fe *d_out);
+
 }  // namespace zk

@@ -4,3 +4,4 @@
 #include "keygen_impl.hpp"
 template struct zk::MsmWork<zk::G1>;
 template int zk::batch_mul_base<zk::G1>(const zk::G1::Affine &, const zk::fe *, uint32_t, zk::G1::Affine *, hipStream_t);
+template int zk::curve_probe<zk::G1>(int, const zk::fe *, uint32_t, zk::fe *);

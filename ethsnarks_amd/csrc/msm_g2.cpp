@@ -4,3 +4,4 @@
 #include "keygen_impl.hpp"
 template struct zk::MsmWork<zk::G2>;
 template int zk::batch_mul_base<zk::G2>(const zk::G2::Affine &, const zk::fe *, uint32_t, zk::G2::Affine *, hipStream_t);
+template int zk::curve_probe<zk::G2>(int, const zk::fe *, uint32_t, zk::fe *);

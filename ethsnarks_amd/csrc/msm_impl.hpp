@@ -648,4 +648,56 @@ int MsmWork<C>::enqueue(const fe *scalars, const uint32_t *gather, uint32_t n, i
     return enqueue_reduce(view(), st, st_tail);
 }
 
+// ---- arithmetic probe (msm.hpp: curve_probe).  The quad forms (OP 5 .. 7) run every case on four adjacent lanes and store each lane's result.
+template <class C, int OP>
+__global__ void __launch_bounds__(64, OP == 3 ? C::WAVES_PER_SIMD_PAIRS : C::WAVES_PER_SIMD)
+k_curve_probe(const fe *__restrict__ in, fe *__restrict__ out, uint32_t n) {
+    typedef typename C::Affine A;
+    typedef typename C::XYZZ X;
+    constexpr bool QUAD = OP >= 5 && OP <= 7;
+    constexpr uint32_t AW = sizeof(A) / sizeof(fe), XW = sizeof(X) / sizeof(fe);
+    constexpr uint32_t IN = OP == 0 ? AW : (OP == 2 || OP == 3 || OP == 7) ? XW + AW : (OP == 4 || OP == 6) ? 2 * XW : XW;
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t i = QUAD ? t >> 2 : t, ql = t & 3u;
+    if (i >= n) return;                                         // (a quad leaves as a whole)
+    const fe *a = in + (size_t)i * IN;
+    if constexpr (OP == 9) {
+        *(A *)(out + (size_t)i * AW) = C::to_affine(*(const X *)a);
+    } else {
+        X r;
+        if constexpr (OP == 0) r = C::dbl_affine(*(const A *)a);
+        if constexpr (OP == 1) r = C::dbl(*(const X *)a);
+        if constexpr (OP == 2) r = C::madd(*(const X *)a, *(const A *)(a + XW));
+        if constexpr (OP == 3) r = C::madd_pairs(*(const X *)a, *(const A *)(a + XW));
+        if constexpr (OP == 4) r = C::add(*(const X *)a, *(const X *)(a + XW));
+        if constexpr (OP == 5) r = C::dbl_q(*(const X *)a, ql);
+        if constexpr (OP == 6) r = C::add_q(*(const X *)a, *(const X *)(a + XW), ql);
+        if constexpr (OP == 7) r = C::madd_q(*(const X *)a, *(const A *)(a + XW), ql);
+        if constexpr (OP == 8) r = C::canon(*(const X *)a);
+        *(X *)(out + (size_t)(QUAD ? t : i) * XW) = r;
+    }
+}
+template <class C, int OP> static int curve_probe_launch(const fe *d_in, uint32_t n, fe *d_out) {
+    const uint64_t threads = (uint64_t)n * ((OP >= 5 && OP <= 7) ? 4 : 1);
+    ZK_LAUNCH((k_curve_probe<C, OP>), zk_div_up(threads, 64), 64, nullptr, d_in, d_out, n);
+    ZK_HIP(hipGetLastError());
+    return ZK_OK;
+}
+template <class C>
+int curve_probe(int idx, const fe *d_in, uint32_t n, fe *d_out) {
+    switch (idx) {
+    case 0: return curve_probe_launch<C, 0>(d_in, n, d_out);
+    case 1: return curve_probe_launch<C, 1>(d_in, n, d_out);
+    case 2: return curve_probe_launch<C, 2>(d_in, n, d_out);
+    case 3: return curve_probe_launch<C, 3>(d_in, n, d_out);
+    case 4: return curve_probe_launch<C, 4>(d_in, n, d_out);
+    case 5: return curve_probe_launch<C, 5>(d_in, n, d_out);
+    case 6: return curve_probe_launch<C, 6>(d_in, n, d_out);
+    case 7: return curve_probe_launch<C, 7>(d_in, n, d_out);
+    case 8: return curve_probe_launch<C, 8>(d_in, n, d_out);
+    case 9: return curve_probe_launch<C, 9>(d_in, n, d_out);
+    }
+    return fail_msg(ZK_ERR_ARG, "unknown probe op");
+}
+
 }  // namespace zk

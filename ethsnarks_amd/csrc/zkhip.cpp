@@ -2208,3 +2208,154 @@ extern "C" int zk_field_mul(const uint64_t *a, const uint64_t *b, uint64_t *out,
     if (dout) hipFree(dout);
     return rc;
 } ZK_GUARD
+
+// ---- arithmetic probe (include/zkhip.h: test infrastructure).  One primitive of bn254.hpp per kernel instantiation, operands as given,
+// raw result limbs back.  The field forms live here, the curve forms with the curve kernels (msm_impl.hpp: curve_probe), so that both pass
+// through the same assembly post-pass as the kernels that prove.
+namespace {
+static ZK_HD fe2 probe_ld2(const fe *a) { fe2 r; r.c0 = a[0]; r.c1 = a[1]; return r; }
+static ZK_HD void probe_st2(fe *o, const fe2 &v) { o[0] = v.c0; o[1] = v.c1; }
+static ZK_HD fe probe_flag(bool b) { fe r = Fr::zero(); r.l[0] = b ? 1u : 0u; return r; }
+#define ZK_PROBE_OP(NAME, NIN, NOUT, ...) \
+    template <class F> struct NAME { static constexpr uint32_t IN = NIN, OUT = NOUT; static ZK_HD void run(const fe *a, fe *o) { __VA_ARGS__; } };
+ZK_PROBE_OP(PrAdd, 2, 1, o[0] = F::add(a[0], a[1]))
+ZK_PROBE_OP(PrSub, 2, 1, o[0] = F::sub(a[0], a[1]))
+ZK_PROBE_OP(PrNeg, 1, 1, o[0] = F::neg(a[0]))
+ZK_PROBE_OP(PrMul, 2, 1, o[0] = F::mul(a[0], a[1]))
+ZK_PROBE_OP(PrReduceOnce, 1, 1, o[0] = F::reduce_once(a[0]))
+ZK_PROBE_OP(PrCanon, 1, 1, o[0] = F::canon(a[0]))
+ZK_PROBE_OP(PrLmul, 2, 1, o[0] = F::lmul(a[0], a[1]))
+ZK_PROBE_OP(PrLsqr, 1, 1, o[0] = F::lsqr(a[0]))
+ZK_PROBE_OP(PrLadd, 2, 1, o[0] = F::ladd(a[0], a[1]))
+ZK_PROBE_OP(PrLsub, 2, 1, o[0] = F::lsub(a[0], a[1]))
+ZK_PROBE_OP(PrLdbl, 1, 1, o[0] = F::ldbl(a[0]))
+ZK_PROBE_OP(PrLneg, 1, 1, o[0] = F::lneg(a[0]))
+ZK_PROBE_OP(PrLisZero, 1, 1, o[0] = probe_flag(F::lis_zero(a[0])))
+ZK_PROBE_OP(PrLnegOp, 1, 1, o[0] = F::lneg_op(a[0]))
+ZK_PROBE_OP(PrLmulNegOp, 2, 1, o[0] = F::lmul(a[0], F::lneg_op(a[1])))
+ZK_PROBE_OP(PrLmul2, 4, 1, o[0] = F::lmul2(a[0], a[1], a[2], a[3]))
+ZK_PROBE_OP(PrLmul2NegOp, 4, 1, o[0] = F::lmul2(a[0], a[1], a[2], F::lneg_op(a[3])))
+ZK_PROBE_OP(PrLmul4, 8, 1, o[0] = F::lmul4(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7]))
+ZK_PROBE_OP(PrLmul4NegOp, 8, 1, o[0] = F::lmul4(a[0], a[1], a[2], F::lneg_op(a[3]), a[4], a[5], a[6], F::lneg_op(a[7])))
+ZK_PROBE_OP(PrLmulX2, 4, 2, F::lmul_x2(a[0], a[1], a[2], a[3], o[0], o[1]))
+ZK_PROBE_OP(PrLmul2X2, 8, 2, F::lmul2_x2(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], o[0], o[1]))
+ZK_PROBE_OP(PrToMont, 1, 1, o[0] = F::to_mont(a[0]))
+ZK_PROBE_OP(PrFromMont, 1, 1, o[0] = F::from_mont(a[0]))
+ZK_PROBE_OP(PrInv, 1, 1, o[0] = F::inv(a[0]))
+// Fq2 (F = Fq2): elements are two words
+ZK_PROBE_OP(Pr2Lmul, 4, 2, probe_st2(o, F::lmul(probe_ld2(a), probe_ld2(a + 2))))
+ZK_PROBE_OP(Pr2Lsqr, 2, 2, probe_st2(o, F::lsqr(probe_ld2(a))))
+ZK_PROBE_OP(Pr2Lmul2, 8, 2, probe_st2(o, F::lmul2(probe_ld2(a), probe_ld2(a + 2), probe_ld2(a + 4), probe_ld2(a + 6))))
+ZK_PROBE_OP(Pr2Ladd, 4, 2, probe_st2(o, F::ladd(probe_ld2(a), probe_ld2(a + 2))))
+ZK_PROBE_OP(Pr2Lsub, 4, 2, probe_st2(o, F::lsub(probe_ld2(a), probe_ld2(a + 2))))
+ZK_PROBE_OP(Pr2LisZero, 2, 2, o[0] = probe_flag(F::lis_zero(probe_ld2(a))); o[1] = Fr::zero())
+#undef ZK_PROBE_OP
+
+template <class Op>
+__global__ void __launch_bounds__(64) k_arith_probe(const fe *__restrict__ in, fe *__restrict__ out, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    fe a[Op::IN], o[Op::OUT];
+#pragma unroll
+    for (uint32_t k = 0; k < Op::IN; k++) a[k] = in[(size_t)i * Op::IN + k];
+    Op::run(a, o);
+#pragma unroll
+    for (uint32_t k = 0; k < Op::OUT; k++) out[(size_t)i * Op::OUT + k] = o[k];
+}
+template <class Op> int probe_launch(const fe *d_in, uint32_t n, fe *d_out) {
+    ZK_LAUNCH((k_arith_probe<Op>), zk_div_up(n, 64), 64, nullptr, d_in, d_out, n);
+    ZK_HIP(hipGetLastError());
+    return ZK_OK;
+}
+template <class F> int probe_field(int idx, const fe *d_in, uint32_t n, fe *d_out) {
+    switch (idx) {
+    case 0: return probe_launch<PrAdd<F>>(d_in, n, d_out);
+    case 1: return probe_launch<PrSub<F>>(d_in, n, d_out);
+    case 2: return probe_launch<PrNeg<F>>(d_in, n, d_out);
+    case 3: return probe_launch<PrMul<F>>(d_in, n, d_out);
+    case 4: return probe_launch<PrReduceOnce<F>>(d_in, n, d_out);
+    case 5: return probe_launch<PrCanon<F>>(d_in, n, d_out);
+    case 6: return probe_launch<PrLmul<F>>(d_in, n, d_out);
+    case 7: return probe_launch<PrLsqr<F>>(d_in, n, d_out);
+    case 8: return probe_launch<PrLadd<F>>(d_in, n, d_out);
+    case 9: return probe_launch<PrLsub<F>>(d_in, n, d_out);
+    case 10: return probe_launch<PrLdbl<F>>(d_in, n, d_out);
+    case 11: return probe_launch<PrLneg<F>>(d_in, n, d_out);
+    case 12: return probe_launch<PrLisZero<F>>(d_in, n, d_out);
+    case 13: return probe_launch<PrLnegOp<F>>(d_in, n, d_out);
+    case 14: return probe_launch<PrLmulNegOp<F>>(d_in, n, d_out);
+    case 15: return probe_launch<PrLmul2<F>>(d_in, n, d_out);
+    case 16: return probe_launch<PrLmul2NegOp<F>>(d_in, n, d_out);
+    case 17: return probe_launch<PrLmul4<F>>(d_in, n, d_out);
+    case 18: return probe_launch<PrLmul4NegOp<F>>(d_in, n, d_out);
+    case 19: return probe_launch<PrLmulX2<F>>(d_in, n, d_out);
+    case 20: return probe_launch<PrLmul2X2<F>>(d_in, n, d_out);
+    case 21: return probe_launch<PrToMont<F>>(d_in, n, d_out);
+    case 22: return probe_launch<PrFromMont<F>>(d_in, n, d_out);
+    case 23: return probe_launch<PrInv<F>>(d_in, n, d_out);
+    }
+    return fail(ZK_ERR_ARG, "unknown probe op");
+}
+int probe_fq2(int idx, const fe *d_in, uint32_t n, fe *d_out) {
+    switch (idx) {
+    case 0: return probe_launch<Pr2Lmul<Fq2>>(d_in, n, d_out);
+    case 1: return probe_launch<Pr2Lsqr<Fq2>>(d_in, n, d_out);
+    case 2: return probe_launch<Pr2Lmul2<Fq2>>(d_in, n, d_out);
+    case 3: return probe_launch<Pr2Ladd<Fq2>>(d_in, n, d_out);
+    case 4: return probe_launch<Pr2Lsub<Fq2>>(d_in, n, d_out);
+    case 5: return probe_launch<Pr2LisZero<Fq2>>(d_in, n, d_out);
+    }
+    return fail(ZK_ERR_ARG, "unknown probe op");
+}
+// words per case in and out; false for an op that does not exist
+bool probe_shape(int op, uint32_t &in_words, uint32_t &out_words) {
+    static const uint8_t field_in[24] = {2, 2, 1, 2, 1, 1, 2, 1, 2, 2, 1, 1, 1, 1, 2, 4, 4, 8, 8, 4, 8, 1, 1, 1};
+    static const uint8_t fq2_in[6] = {4, 2, 8, 4, 4, 2};
+    static const uint8_t curve_in[10] = {2, 4, 6, 6, 8, 4, 8, 6, 4, 4}, curve_out[10] = {4, 4, 4, 4, 4, 16, 16, 16, 4, 2};   // in field elements
+    if (op < 0) return false;
+    const int dom = op & ~0xff, idx = op & 0xff;
+    if (dom == ZK_PROBE_FR || dom == ZK_PROBE_FQ) {
+        if (idx >= 24) return false;
+        in_words = field_in[idx]; out_words = idx == 19 || idx == 20 ? 2 : 1;
+    } else if (dom == ZK_PROBE_FQ2) {
+        if (idx >= 6) return false;
+        in_words = fq2_in[idx]; out_words = 2;
+    } else if (dom == ZK_PROBE_G1 || dom == ZK_PROBE_G2) {
+        if (idx >= 10) return false;
+        const uint32_t ew = dom == ZK_PROBE_G2 ? 2 : 1;
+        in_words = curve_in[idx] * ew; out_words = curve_out[idx] * ew;
+    } else return false;
+    return true;
+}
+}  // namespace
+
+extern "C" int zk_arith_probe_shape(int op, uint32_t *in_words, uint32_t *out_words) try {
+    if (!in_words || !out_words) return fail(ZK_ERR_ARG, "null argument");
+    if (!probe_shape(op, *in_words, *out_words)) return fail(ZK_ERR_ARG, "unknown probe op");
+    return ZK_OK;
+} ZK_GUARD
+
+extern "C" int zk_arith_probe(int op, const uint64_t *in, uint32_t n, uint64_t *out, int device) try {
+    uint32_t wi = 0, wo = 0;
+    if (!probe_shape(op, wi, wo)) return fail(ZK_ERR_ARG, "unknown probe op");
+    if (n > (1u << 20)) return fail(ZK_ERR_ARG, "the probe takes at most 2^20 cases per call");
+    if (n && (!in || !out)) return fail(ZK_ERR_ARG, "null argument");
+    ZK_TRY(use_device(device));
+    if (!n) return ZK_OK;
+    fe *d_in = nullptr, *d_out = nullptr;
+    int rc = dev_upload(&d_in, (const fe *)in, (size_t)n * wi);
+    if (rc == ZK_OK && hipMalloc(&d_out, 32 * (size_t)n * wo) != hipSuccess) rc = fail(ZK_ERR_NOMEM, "out of device memory");
+    if (rc == ZK_OK) {
+        const int dom = op & ~0xff, idx = op & 0xff;
+        if (dom == ZK_PROBE_FR) rc = probe_field<Fr>(idx, d_in, n, d_out);
+        else if (dom == ZK_PROBE_FQ) rc = probe_field<Fq>(idx, d_in, n, d_out);
+        else if (dom == ZK_PROBE_FQ2) rc = probe_fq2(idx, d_in, n, d_out);
+        else if (dom == ZK_PROBE_G1) rc = curve_probe<G1>(idx, d_in, n, d_out);
+        else rc = curve_probe<G2>(idx, d_in, n, d_out);
+    }
+    if (rc == ZK_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(ZK_ERR_HIP, "probe kernel failed");
+    if (rc == ZK_OK && hipMemcpy(out, d_out, 32 * (size_t)n * wo, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(ZK_ERR_HIP, "copy from the device failed");
+    if (d_in) hipFree(d_in);
+    if (d_out) hipFree(d_out);
+    return rc;
+} ZK_GUARD

@@ -74,6 +74,7 @@ EXPORTS = [
     "zk_mtree_create", "zk_mtree_free", "zk_mtree_size", "zk_mtree_append", "zk_mtree_append_resident", "zk_mtree_update", "zk_mtree_root", "zk_mtree_node",
     "zk_mtree_paths", "zk_mtree_fill_witnesses", "zk_mimc_constants", "zk_mimc_hash2",
     "zk_ntt", "zk_witness_map", "zk_msm_g1", "zk_msm_g2", "zk_field_mul", "zk_fr_convert",
+    "zk_arith_probe", "zk_arith_probe_shape",
 ]
 
 _lib = None
@@ -856,6 +857,27 @@ def field_mul(a, b, field="fr", device=0):
     a = _c64(a); b = _c64(b)
     out = np.zeros_like(a)
     _check(load_library(_lib_path_loaded).zk_field_mul(_p64(a), _p64(b), _p64(out), C.c_uint32(a.size // 4), 0 if field == "fr" else 1, device))
+    return out
+
+
+PROBE_FR, PROBE_FQ, PROBE_FQ2, PROBE_G1, PROBE_G2 = 0x000, 0x100, 0x200, 0x300, 0x400      # include/zkhip.h ZK_PROBE_*
+
+
+def arith_probe_shape(op):
+    """zk_arith_probe_shape: (words per case in, words per case out), a word being 4 u64"""
+    wi, wo = C.c_uint32(0), C.c_uint32(0)
+    _check(load_library(_lib_path_loaded).zk_arith_probe_shape(int(op), C.byref(wi), C.byref(wo)))
+    return int(wi.value), int(wo.value)
+
+
+def arith_probe(op, operands, device=0):
+    """zk_arith_probe (test infrastructure): one primitive of csrc/bn254.hpp applied to n cases; operands (n, words in, 4) u64 limbs taken
+    as given, returns the raw result limbs (n, words out, 4)"""
+    wi, wo = arith_probe_shape(op)
+    a = _c64(operands).reshape(-1, wi, 4)
+    n = a.shape[0]
+    out = np.zeros((n, wo, 4), dtype=np.uint64)
+    _check(load_library(_lib_path_loaded).zk_arith_probe(int(op), _p64(a) if n else None, C.c_uint32(n), _p64(out) if n else None, device))
     return out
 
 

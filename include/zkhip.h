@@ -400,6 +400,35 @@ int zk_pairing_check(const uint64_t *g1, const uint64_t *g2, uint32_t n, uint32_
  * c0.c0.c0, c0.c0.c1, c0.c1.c0, ... (coefficient a_ij of v^i w^j at index 6 j + 2 i + {0: real, 1: u part}).
  * op: 0 a b, 1 a^2, 2 1/a, 3..5 a^(q^1..3), 6 cyclotomic square, 7 a^((q^6-1)(q^2+1)), 8 final exponentiation, 9 conjugate (b unused but for 0) */
 int zk_pairing_tower_op(int op, const uint64_t *a, const uint64_t *b, uint64_t *out);
+/* ---- arithmetic probe: TEST INFRASTRUCTURE, nothing on the proving path calls it.  One primitive of csrc/bn254.hpp per launch, applied
+ * to n <= 2^20 cases whose operands are taken AS GIVEN (raw 8 x u32 limb values, Montgomery where the primitive expects it; no range
+ * check) and whose RAW result limbs come back: no canon, no fix-up.  On the device this is the hand-written gfx950 layer (fips_asm.hpp,
+ * the loose domain [0, 2p)); in the CPU emulation the loose names are the strict host operations.
+ *   op = ZK_PROBE_FR / _FQ / _FQ2 / _G1 / _G2 plus an index.  A "word" is one field element of 4 u64; an Fq2 element is 2 words
+ *   (c0, c1), an affine point 2 elements (x, y), an XYZZ point 4 elements (X, Y, ZZ, ZZZ).
+ *   ZK_PROBE_FR, ZK_PROBE_FQ (operands a, b, ... one word each; one result word unless noted):
+ *      0 add(a, b)   1 sub(a, b)   2 neg(a)   3 mul(a, b)   4 reduce_once(a)   5 canon(a)
+ *      6 lmul(a, b)  7 lsqr(a)     8 ladd(a, b)  9 lsub(a, b)  10 ldbl(a)  11 lneg(a)  12 lis_zero(a) (0 or 1 in the low limb)
+ *     13 lneg_op(a)  14 lmul(a, lneg_op(b))
+ *     15 lmul2(a, b, c, d)   16 lmul2(a, b, c, lneg_op(d))
+ *     17 lmul4(a, .., h)     18 lmul4(a, b, c, lneg_op(d), e, f, g, lneg_op(h))
+ *     19 lmul_x2(a, b, c, d) -> (a b, c d): 2 words      20 lmul2_x2(a, .., h) -> (a b + c d, e f + g h): 2 words
+ *     21 to_mont(a)  22 from_mont(a)  23 inv(a)
+ *   ZK_PROBE_FQ2 (operands and result are Fq2 elements):
+ *      0 lmul(a, b)  1 lsqr(a)  2 lmul2(a, b, c, d)  3 ladd(a, b)  4 lsub(a, b)  5 lis_zero(a) (0 or 1 in the low limb of c0)
+ *   ZK_PROBE_G1, ZK_PROBE_G2 (Curve<Fq>, Curve<Fq2>; A = affine point, X = XYZZ point):
+ *      0 dbl_affine(A) -> X   1 dbl(X) -> X   2 madd(X, A) -> X   3 madd_pairs(X, A) -> X   4 add(X, X) -> X
+ *      5 dbl_q(X)   6 add_q(X, X)   7 madd_q(X, A): the case runs on four adjacent lanes that hold the same operands, the four
+ *        lanes' results come back one after the other (4 X per case)
+ *      8 canon(X) -> X   9 to_affine(X) -> A
+ * zk_arith_probe_shape (host-only): words per case that `in` holds and `out` receives; ZK_ERR_ARG for an unknown op. */
+#define ZK_PROBE_FR 0x000
+#define ZK_PROBE_FQ 0x100
+#define ZK_PROBE_FQ2 0x200
+#define ZK_PROBE_G1 0x300
+#define ZK_PROBE_G2 0x400
+int zk_arith_probe_shape(int op, uint32_t *in_words, uint32_t *out_words);
+int zk_arith_probe(int op, const uint64_t *in, uint32_t n, uint64_t *out, int device);
 
 #ifdef __cplusplus
 }

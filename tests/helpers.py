@@ -33,6 +33,24 @@ def rand_scalars(n, seed, ones_every=0, zeros_every=0):
     return sc
 
 
+def structured_ntt_vectors(logm, seed=5):
+    """[(label, (m, 4) limb array)]: transform inputs in which whole butterfly layers produce exact zeros and sums that equal the modulus
+    -- a difference of equal elements comes out as 0 or as the second representative r of zero, and the last pass must store the canonical
+    one.  The limbs are raw values below r (r - 1 is the largest valid representative)."""
+    m = 1 << logm
+    top, one, zero = F.ints_to_limbs([F.FR - 1])[0], F.ints_to_limbs([1])[0], np.zeros(4, dtype=np.uint64)
+    const = lambda v: np.broadcast_to(v, (m, 4)).copy()
+    delta0 = const(zero); delta0[0] = one
+    delta_last = const(zero); delta_last[m - 1] = one
+    alt = const(top); alt[1::2] = one
+    rng = np.random.default_rng(seed + logm)
+    mixed = rng.integers(0, 1 << 62, size=(m, 4), dtype=np.uint64)
+    mixed[:, 3] &= (1 << 59) - 1
+    mixed[::9] = top; mixed[::8] = zero
+    return [("zero", const(zero)), ("constant r-1", const(top)), ("delta at 0", delta0), ("delta at m-1", delta_last),
+            ("alternating r-1, 1", alt), ("random with zeros and r-1", mixed)]
+
+
 def tiled_bases(oracle, n, g2=False, distinct=512, seed=11):
     """n valid curve points: `distinct` oracle-generated multiples of the generator, tiled."""
     rng = R.SplitMix64(seed)

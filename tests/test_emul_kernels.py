@@ -5,7 +5,7 @@ import json
 import numpy as np
 import pytest
 from ethsnarks_amd import r1cs as R, fields as F
-from helpers import golden_cases, build_case, rand_scalars
+from helpers import golden_cases, build_case, rand_scalars, structured_ntt_vectors
 
 
 @pytest.fixture(scope="module")
@@ -35,6 +35,15 @@ def test_ntt(zk, oracle, logm):
     for inv in (False, True):
         for coset in (False, True):
             assert np.array_equal(zk.ntt(x, logm, inv, coset), oracle.ntt(x, logm, inv, coset))
+
+
+@pytest.mark.parametrize("logm", [0, 1, 2, 3, 5, 11, 12, 13, 14])
+def test_ntt_structured_vectors(zk, oracle, logm):
+    """zeros, constants, deltas and alternating values through the transform kernels: layers of exact zeros and of sums equal to r"""
+    for label, x in structured_ntt_vectors(logm):
+        for inv in (False, True):
+            for coset in (False, True):
+                assert np.array_equal(zk.ntt(x, logm, inv, coset), oracle.ntt(x, logm, inv, coset)), (label, logm, inv, coset)
 
 
 @pytest.mark.parametrize("g2", [False, True])

@@ -5,7 +5,7 @@ import json
 import numpy as np
 import pytest
 from ethsnarks_amd import r1cs as R, fields as F
-from helpers import golden_cases, build_case, rand_scalars, tiled_bases
+from helpers import golden_cases, build_case, rand_scalars, tiled_bases, structured_ntt_vectors
 
 pytestmark = pytest.mark.gpu
 
@@ -35,6 +35,16 @@ def test_ntt_vs_oracle(hip, oracle, logm):
     for inv in (False, True):
         for coset in (False, True):
             assert np.array_equal(hip.ntt(x, logm, inv, coset), oracle.ntt(x, logm, inv, coset)), (logm, inv, coset)
+
+
+@pytest.mark.parametrize("logm", [0, 1, 3, 4, 10, 11, 12, 13, 15, 18, 20, 21])
+def test_ntt_structured_vectors(hip, oracle, logm):
+    """zeros, constants, deltas and alternating values through the production transform kernels: whole butterfly layers produce exact
+    zeros and sums equal to r, so the loose subtraction returns 0 or r and the last pass must store the canonical one"""
+    for label, x in structured_ntt_vectors(logm):
+        for inv in (False, True):
+            for coset in (False, True):
+                assert np.array_equal(hip.ntt(x, logm, inv, coset), oracle.ntt(x, logm, inv, coset)), (label, logm, inv, coset)
 
 
 def test_ntt_roundtrip_full_size(hip):
