@@ -2249,6 +2249,11 @@ ZK_PROBE_OP(Pr2Lmul2, 8, 2, probe_st2(o, F::lmul2(probe_ld2(a), probe_ld2(a + 2)
 ZK_PROBE_OP(Pr2Ladd, 4, 2, probe_st2(o, F::ladd(probe_ld2(a), probe_ld2(a + 2))))
 ZK_PROBE_OP(Pr2Lsub, 4, 2, probe_st2(o, F::lsub(probe_ld2(a), probe_ld2(a + 2))))
 ZK_PROBE_OP(Pr2LisZero, 2, 2, o[0] = probe_flag(F::lis_zero(probe_ld2(a))); o[1] = Fr::zero())
+ZK_PROBE_OP(Pr2Ldbl, 2, 2, probe_st2(o, F::ldbl(probe_ld2(a))))
+ZK_PROBE_OP(Pr2Lneg, 2, 2, probe_st2(o, F::lneg(probe_ld2(a))))
+ZK_PROBE_OP(Pr2Canon, 2, 2, probe_st2(o, F::canon(probe_ld2(a))))
+ZK_PROBE_OP(Pr2Inv, 2, 2, probe_st2(o, F::inv(F::canon(probe_ld2(a)))))
+ZK_PROBE_OP(Pr2Eq, 4, 2, o[0] = probe_flag(F::eq(F::canon(probe_ld2(a)), F::canon(probe_ld2(a + 2)))); o[1] = Fr::zero())
 #undef ZK_PROBE_OP
 
 template <class Op>
@@ -2304,13 +2309,18 @@ int probe_fq2(int idx, const fe *d_in, uint32_t n, fe *d_out) {
     case 3: return probe_launch<Pr2Ladd<Fq2>>(d_in, n, d_out);
     case 4: return probe_launch<Pr2Lsub<Fq2>>(d_in, n, d_out);
     case 5: return probe_launch<Pr2LisZero<Fq2>>(d_in, n, d_out);
+    case 6: return probe_launch<Pr2Ldbl<Fq2>>(d_in, n, d_out);
+    case 7: return probe_launch<Pr2Lneg<Fq2>>(d_in, n, d_out);
+    case 8: return probe_launch<Pr2Canon<Fq2>>(d_in, n, d_out);
+    case 9: return probe_launch<Pr2Inv<Fq2>>(d_in, n, d_out);
+    case 10: return probe_launch<Pr2Eq<Fq2>>(d_in, n, d_out);
     }
     return fail(ZK_ERR_ARG, "unknown probe op");
 }
 // words per case in and out; false for an op that does not exist
 bool probe_shape(int op, uint32_t &in_words, uint32_t &out_words) {
     static const uint8_t field_in[24] = {2, 2, 1, 2, 1, 1, 2, 1, 2, 2, 1, 1, 1, 1, 2, 4, 4, 8, 8, 4, 8, 1, 1, 1};
-    static const uint8_t fq2_in[6] = {4, 2, 8, 4, 4, 2};
+    static const uint8_t fq2_in[11] = {4, 2, 8, 4, 4, 2, 2, 2, 2, 2, 4};
     static const uint8_t curve_in[10] = {2, 4, 6, 6, 8, 4, 8, 6, 4, 4}, curve_out[10] = {4, 4, 4, 4, 4, 16, 16, 16, 4, 2};   // in field elements
     if (op < 0) return false;
     const int dom = op & ~0xff, idx = op & 0xff;
@@ -2318,7 +2328,7 @@ bool probe_shape(int op, uint32_t &in_words, uint32_t &out_words) {
         if (idx >= 24) return false;
         in_words = field_in[idx]; out_words = idx == 19 || idx == 20 ? 2 : 1;
     } else if (dom == ZK_PROBE_FQ2) {
-        if (idx >= 6) return false;
+        if (idx >= 11) return false;
         in_words = fq2_in[idx]; out_words = 2;
     } else if (dom == ZK_PROBE_G1 || dom == ZK_PROBE_G2) {
         if (idx >= 10) return false;

@@ -75,6 +75,7 @@ EXPORTS = [
     "zk_mtree_paths", "zk_mtree_fill_witnesses", "zk_mimc_constants", "zk_mimc_hash2",
     "zk_ntt", "zk_witness_map", "zk_msm_g1", "zk_msm_g2", "zk_field_mul", "zk_fr_convert",
     "zk_arith_probe", "zk_arith_probe_shape",
+    "zk_pairing_probe", "zk_pairing_probe_shape", "zk_vctx_probe_prepare",
 ]
 
 _lib = None
@@ -677,6 +678,16 @@ class Verifier:
         _check(_lib.zk_verify_batch(self._h, arr, _p64(inp) if inp.size else None, C.c_uint32(k), out))
         return [bool(out[i]) for i in range(k)]
 
+    def probe_prepare(self, proofs, inputs_canon):
+        """zk_vctx_probe_prepare (test infrastructure): the prepare kernel alone; returns (points (k, 10, 4) raw limbs in the order
+        A.x, A.y, nAcc.x, nAcc.y, nC.x, nC.y, B.x.c0, B.x.c1, B.y.c0, B.y.c1, and the list of k `ok` flags)"""
+        k = len(proofs)
+        arr = (ZkProof * max(k, 1))(*proofs)
+        inp = _c64(inputs_canon).reshape(-1)
+        out = np.zeros((max(k, 1), 42), dtype=np.uint64)
+        _check(_lib.zk_vctx_probe_prepare(self._h, arr, _p64(inp) if inp.size else None, C.c_uint32(k), _p64(out)))
+        return out[:k, :40].reshape(k, 10, 4).copy(), [int(v) & 0xffffffff for v in out[:k, 40]]
+
     def close(self):
         if getattr(self, "_h", None) is not None and _lib is not None:
             _lib.zk_vctx_destroy(self._h)
@@ -878,6 +889,24 @@ def arith_probe(op, operands, device=0):
     n = a.shape[0]
     out = np.zeros((n, wo, 4), dtype=np.uint64)
     _check(load_library(_lib_path_loaded).zk_arith_probe(int(op), _p64(a) if n else None, C.c_uint32(n), _p64(out) if n else None, device))
+    return out
+
+
+def pairing_probe_shape(op):
+    """zk_pairing_probe_shape: (words per case in, words per case out), a word being 4 u64"""
+    wi, wo = C.c_uint32(0), C.c_uint32(0)
+    _check(load_library(_lib_path_loaded).zk_pairing_probe_shape(int(op), C.byref(wi), C.byref(wo)))
+    return int(wi.value), int(wo.value)
+
+
+def pairing_probe(op, operands, device=0):
+    """zk_pairing_probe (test infrastructure): one function of csrc/pairing.hpp applied on the device to n cases, one lane each; operands
+    (n, words in, 4) u64 limbs taken as given, returns the raw result limbs (n, words out, 4)"""
+    wi, wo = pairing_probe_shape(op)
+    a = _c64(operands).reshape(-1, wi, 4)
+    n = a.shape[0]
+    out = np.zeros((n, wo, 4), dtype=np.uint64)
+    _check(load_library(_lib_path_loaded).zk_pairing_probe(int(op), _p64(a) if n else None, C.c_uint32(n), _p64(out) if n else None, device))
     return out
 
 

@@ -416,6 +416,8 @@ int zk_pairing_tower_op(int op, const uint64_t *a, const uint64_t *b, uint64_t *
  *     21 to_mont(a)  22 from_mont(a)  23 inv(a)
  *   ZK_PROBE_FQ2 (operands and result are Fq2 elements):
  *      0 lmul(a, b)  1 lsqr(a)  2 lmul2(a, b, c, d)  3 ladd(a, b)  4 lsub(a, b)  5 lis_zero(a) (0 or 1 in the low limb of c0)
+ *      6 ldbl(a)  7 lneg(a)  8 canon(a)  9 inv(canon(a)) (strict result; 0 -> 0: the form pairing.hpp's f2inv uses)
+ *     10 eq(canon(a), canon(b)) (0 or 1 in the low limb of c0)
  *   ZK_PROBE_G1, ZK_PROBE_G2 (Curve<Fq>, Curve<Fq2>; A = affine point, X = XYZZ point):
  *      0 dbl_affine(A) -> X   1 dbl(X) -> X   2 madd(X, A) -> X   3 madd_pairs(X, A) -> X   4 add(X, X) -> X
  *      5 dbl_q(X)   6 add_q(X, X)   7 madd_q(X, A): the case runs on four adjacent lanes that hold the same operands, the four
@@ -429,6 +431,33 @@ int zk_pairing_tower_op(int op, const uint64_t *a, const uint64_t *b, uint64_t *
 #define ZK_PROBE_G2 0x400
 int zk_arith_probe_shape(int op, uint32_t *in_words, uint32_t *out_words);
 int zk_arith_probe(int op, const uint64_t *in, uint32_t n, uint64_t *out, int device);
+/* ---- pairing probe: TEST INFRASTRUCTURE, nothing on the verifying path calls it.  One function of csrc/pairing.hpp per launch, one lane
+ * per case (blocks of 64), n <= 2^12 cases.  The kernels sit in csrc/verify_gpu.cpp and call the compiled bodies the batch verifier calls
+ * (the tower functions are real, non-inlined device functions on operands in the lane's scratch memory).  Operands are taken AS GIVEN
+ * (raw 8 x u32 limb values, Montgomery form, loose domain [0, 2q); no range check), RAW result limbs come back: no canon.  In the CPU
+ * emulation the loose names are the strict host operations.  (zk_pairing_tower_op above stays the host-only, canonical form.)
+ *   A "word" is one Fq element of 4 u64.  fe2 = 2 words (c0, c1), fe6 = 6 (c0, c1, c2), fe12 = 12 in the order of zk_pairing_tower_op;
+ *   G1 = affine point, 2 words; G2 = affine twist point, 4 words (all-zero: infinity); T = G2Hom (X, Y, Z), 6 words; L = LineC (a, b, c),
+ *   6 words; a flag or skip operand is one word whose low limb is 0 or 1; "~" marks the form whose output aliases its first operand.
+ *      0 f6mul(a, b)   1 ~f6mul   2 f6mul01(a, b0, b1)   3 f6inv(a)   4 f6mulv(a)   5 f6add(a, b)   6 f6sub(a, b)   7 f6neg(a)
+ *      8 f2mulxi(a)    9 f2muls(a, s: 1 word)   10 f2conj(a)
+ *     11 f12mul(a, b) 12 ~f12mul  13 f12sqr(a)  14 ~f12sqr  15 f12inv(a)  16 ~f12inv  17 f12conj(a)  18 .. 20 f12frob<1 .. 3>(a)
+ *     21 f12cycsqr(a) 22 ~f12cycsqr   23 f12mul034(f, c0, d0, d1) -> f   24 f12eq(a, b) -> flag   25 f12is_one(a) -> flag
+ *     26 f12canon(a) (strict: every coefficient < q)   27 f12exp_negz(a)   28 final_exp_easy(a)   29 final_exp(a)
+ *     30 dbl_step(T) -> (T', L)   31 add_step(T, Q: G2) -> (T', L)   32 g2_frob1(Q) -> G2   33 g2_negfrob2(Q) -> G2
+ *     34 ell(f, L, P: G1, skip) -> f
+ *     35 .. 37 miller_multi with nv = 1 .. 3 variable pairs, operands P_0 .. P_(nv-1) then Q_0 .. Q_(nv-1) -> f before the final exponentiation
+ *     38, 39  the fixed-Q route with nf = 1, 2: operands P_0 .. then Q_0 .. then one word fskip (low limb: bit j skips pair j); the lane
+ *             runs miller_precompute for its Q into global storage the host allocates, then miller_multi(nv = 0, nf, fskip) -> f
+ *     40 .. 42 k_pair_product itself with n = 1 .. 3 pairs per case (operands as 35 .. 37), its `values` returned: FE(prod ML), canonical
+ *     43 g2_on_curve(Q) -> flag   44 g2_in_subgroup(Q) -> flag   45 g1_on_curve(P) -> flag
+ * zk_pairing_probe_shape (host-only): words per case that `in` holds and `out` receives; ZK_ERR_ARG for an unknown op.
+ * zk_vctx_probe_prepare (TEST INFRASTRUCTURE as well): runs the prepare kernel of zk_verify_batch alone on a live context and returns the
+ * k records it hands to the pairing kernel, 42 u64 each: A, -acc, -C (G1), B (G2) as raw Montgomery limbs, (0, 0) = infinity, then `ok`
+ * in the low 32 bits of word 40 (1: coordinates < q, inputs < r, A and C on the curve) and padding.  Arguments as zk_verify_batch. */
+int zk_pairing_probe_shape(int op, uint32_t *in_words, uint32_t *out_words);
+int zk_pairing_probe(int op, const uint64_t *in, uint32_t n, uint64_t *out, int device);
+int zk_vctx_probe_prepare(zk_vctx *v, const zk_proof *proofs, const uint64_t *inputs_canon, uint32_t k, uint64_t *out_points);
 
 #ifdef __cplusplus
 }

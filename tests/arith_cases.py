@@ -115,7 +115,16 @@ def field_cases(name, p, loose=True):
 # ---- Fq2: elements are (c0, c1); the components run through the same lists
 def fq2_cases(name, loose=True):
     q = A.FQ
-    width = {"lmul": 2, "lsqr": 1, "lmul2": 4, "ladd": 2, "lsub": 2, "lis_zero": 1}[name]
+    width = {"lmul": 2, "lsqr": 1, "lmul2": 4, "ladd": 2, "lsub": 2, "lis_zero": 1, "ldbl": 1, "lneg": 1, "canon": 1, "inv": 1, "eq": 2}[name]
+    if name == "eq":                                      # every pair of representatives of every edge pair, near misses, and the drawn tuples
+        e = edge_values(q, loose)
+        pairs = [(a, b) for a in e for b in e if a % q == b % q or abs(a - b) in (1, q - 1, q + 1)]
+        flat = [(a, c, b, d) for (a, b) in pairs for (c, d) in pairs[::7]] + tuple_cases(q, 4, (), loose, seed=12)[:N_DRAWN]
+        return [((t[0], t[1]), (t[2], t[3])) for t in flat]
+    if name == "inv":                                     # one Fq inversion per case: the edge cross product and a few random elements
+        e = edge_values(q, loose)
+        r = random_values(q, 48, 14, loose)
+        return [((a, b),) for a in e[:12] for b in e[:12]] + [((r[2 * i], r[2 * i + 1]),) for i in range(24)]
     if name == "lis_zero":
         e = edge_values(q, loose)
         return [((a, b),) for a in e for b in e]
@@ -123,7 +132,9 @@ def fq2_cases(name, loose=True):
     return [tuple((t[2 * i], t[2 * i + 1]) for i in range(width)) for t in flat]
 
 
-FQ2_OPS = {"lmul": 0, "lsqr": 1, "lmul2": 2, "ladd": 3, "lsub": 4, "lis_zero": 5}
+FQ2_OPS = {"lmul": 0, "lsqr": 1, "lmul2": 2, "ladd": 3, "lsub": 4, "lis_zero": 5, "ldbl": 6, "lneg": 7, "canon": 8, "inv": 9, "eq": 10}
+FQ2_FLAG = ("lis_zero", "eq")                             # result: 0 or 1 in the low limb of c0
+FQ2_STRICT_RESULT = ("canon", "inv")                      # result in [0, q)
 
 
 # ---- curves

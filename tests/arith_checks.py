@@ -101,12 +101,15 @@ def check_fq2_op(zk, name, loose):
     bad = []
     for i, (t, g) in enumerate(zip(cases, got)):
         exp = A.fq2_expected(name, t)
-        if name == "lis_zero":
+        if name in K.FQ2_FLAG:
             ok = g == [exp, 0]
+        elif name in K.FQ2_STRICT_RESULT:
+            ok = tuple(g) == exp
         else:
             ok = (g[0] % q, g[1] % q) == exp and g[0] < 2 * q and g[1] < 2 * q
         if not ok:
-            bad.append("fq2 %s case %d operands %s: got %s, want %s (mod q) below 2q" % (name, i, _hx(t), _hx(tuple(g)), _hx(exp) if name != "lis_zero" else exp))
+            bad.append("fq2 %s case %d operands %s: got %s, want %s (mod q) below %s" % (name, i, _hx(t), _hx(tuple(g)), _hx(exp) if name not in K.FQ2_FLAG else exp,
+                                                                                         "q" if name in K.FQ2_STRICT_RESULT else "2q"))
     _report("fq2 %s (%d cases)" % (name, len(cases)), bad)
 
 

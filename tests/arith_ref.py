@@ -95,6 +95,11 @@ def fq2_expected(name, a):
     if name == "ladd": return _f2_mont(pyref.f2_add(v[0], v[1]))
     if name == "lsub": return _f2_mont(pyref.f2_sub(v[0], v[1]))
     if name == "lis_zero": return 1 if v[0] == (0, 0) else 0
+    if name == "ldbl": return _f2_mont(pyref.f2_add(v[0], v[0]))
+    if name == "lneg": return _f2_mont(pyref.f2_neg(v[0]))
+    if name == "canon": return (a[0][0] % FQ, a[0][1] % FQ)
+    if name == "inv": return _f2_mont(pyref.f2_inv(v[0])) if v[0] != (0, 0) else (0, 0)
+    if name == "eq": return 1 if v[0] == v[1] else 0
     raise KeyError(name)
 
 

@@ -60,7 +60,7 @@ def test_curve_op(zk, oracle, g2, name):
 
 def test_probe_argument_checks(zk):
     """the ABI's rules: unknown ops and null buffers are ZK_ERR_ARG, zero cases are fine"""
-    for op in (-1, 24, zk.PROBE_FQ + 24, zk.PROBE_FQ2 + 6, zk.PROBE_G1 + 10, zk.PROBE_G2 + 10, 0x500):
+    for op in (-1, 24, zk.PROBE_FQ + 24, zk.PROBE_FQ2 + 11, zk.PROBE_G1 + 10, zk.PROBE_G2 + 10, 0x500):
         with pytest.raises(zk.ZkError) as e:
             zk.arith_probe_shape(op)
         assert e.value.code == 1

@@ -402,7 +402,7 @@ def test_new_entry_points_end_in_the_exception_barrier():
     src = open(os.path.join(ROOT, "ethsnarks_amd", "csrc", "verify_gpu.cpp")).read()
     src = "\n".join(l for l in src.split("\n") if not l.lstrip().startswith("//"))     # (a comment between two functions is no function body)
     heads = list(re.finditer(r'^extern "C" [^\n;]*?(\w+)\s*\(([^;{]*?)\)\s*(try\s*)?\{', src, flags=re.M))
-    assert len(heads) == 6
+    assert len(heads) == 9
     for i, m in enumerate(heads):
         body = src[m.end():heads[i + 1].start() if i + 1 < len(heads) else len(src)]
         assert m.group(3), m.group(1) + " is not a function-try-block"
