@@ -283,6 +283,73 @@ struct Field {
     static __device__ __forceinline__ fe lmul4(const fe &a, const fe &b, const fe &c, const fe &d, const fe &e, const fe &f, const fe &g, const fe &h) {
         const fe *const op[8] = {&a, &b, &c, &d, &e, &f, &g, &h}; return mul_fips_n<4, false>(op);
     }
+    // ---- six-term dot product with a CONSTANT row: x_0 m_0 + ... + x_5 m_5 with one Montgomery reduction (the MIX layer of Poseidon,
+    // poseidon.hpp: every output element is such a sum).  The row limbs are wave-uniform and ride in SGPRs (the macN_vs forms the m*p
+    // products use), so the 48 limbs of a row cost no VGPR.  6 x 64 + 72 multiplies against 6 x 136 for six products, and no modular additions.
+    // PRECONDITION: x loose (< 2p), the row CANONICAL (< p).  Then sum x_i m_i < 12 p^2 and the reduced value is below
+    //     (12 p^2 + R p)/R = p (12 p/R + 1) < 3.27 p          (p/R < 0.1891 for both moduli)
+    // which is below 4p < 2^256, so it fits the eight limbs and ONE fold by 2p (subtract 2p when the value is >= 2p) leaves it in [0, 2p):
+    // a value below 2p stays, one in [2p, 3.27p) lands in [0, 1.27p).  (lmul4 needs two folds because its 4.03p passes 4p; a second fold
+    // here would never subtract.)  With BOTH operands loose the bound is
+    // (24 p^2 + R p)/R < 5.54 p, which passes 2^256 = 5.29 p: the limbs would wrap.  The precondition is not to be relaxed.
+    template <int N, int J0, int I>
+    static __device__ __forceinline__ void col_as(uint64_t &lo, uint32_t &hi, const fe &a, const fe &b) {
+#define ZK_AS(k) a.l[J0 + k], b.l[I - J0 - k]
+        if constexpr (N == 1) fips::mac1_vs(lo, hi, ZK_AS(0));
+        if constexpr (N == 2) fips::mac2_vs(lo, hi, ZK_AS(0), ZK_AS(1));
+        if constexpr (N == 3) fips::mac3_vs(lo, hi, ZK_AS(0), ZK_AS(1), ZK_AS(2));
+        if constexpr (N == 4) fips::mac4_vs(lo, hi, ZK_AS(0), ZK_AS(1), ZK_AS(2), ZK_AS(3));
+        if constexpr (N == 5) fips::mac5_vs(lo, hi, ZK_AS(0), ZK_AS(1), ZK_AS(2), ZK_AS(3), ZK_AS(4));
+        if constexpr (N == 6) fips::mac6_vs(lo, hi, ZK_AS(0), ZK_AS(1), ZK_AS(2), ZK_AS(3), ZK_AS(4), ZK_AS(5));
+        if constexpr (N == 7) fips::mac7_vs(lo, hi, ZK_AS(0), ZK_AS(1), ZK_AS(2), ZK_AS(3), ZK_AS(4), ZK_AS(5), ZK_AS(6));
+        if constexpr (N == 8) fips::mac8_vs(lo, hi, ZK_AS(0), ZK_AS(1), ZK_AS(2), ZK_AS(3), ZK_AS(4), ZK_AS(5), ZK_AS(6), ZK_AS(7));
+    }
+    template <int N, int J0, int I>
+    static __device__ __forceinline__ void col_as_set(uint64_t &lo, uint32_t &hi, uint64_t ad, const fe &a, const fe &b) {
+        if constexpr (N == 1) fips::mac1_vs_set(lo, hi, ad, ZK_AS(0));
+        if constexpr (N == 2) fips::mac2_vs_set(lo, hi, ad, ZK_AS(0), ZK_AS(1));
+        if constexpr (N == 3) fips::mac3_vs_set(lo, hi, ad, ZK_AS(0), ZK_AS(1), ZK_AS(2));
+        if constexpr (N == 4) fips::mac4_vs_set(lo, hi, ad, ZK_AS(0), ZK_AS(1), ZK_AS(2), ZK_AS(3));
+        if constexpr (N == 5) fips::mac5_vs_set(lo, hi, ad, ZK_AS(0), ZK_AS(1), ZK_AS(2), ZK_AS(3), ZK_AS(4));
+        if constexpr (N == 6) fips::mac6_vs_set(lo, hi, ad, ZK_AS(0), ZK_AS(1), ZK_AS(2), ZK_AS(3), ZK_AS(4), ZK_AS(5));
+        if constexpr (N == 7) fips::mac7_vs_set(lo, hi, ad, ZK_AS(0), ZK_AS(1), ZK_AS(2), ZK_AS(3), ZK_AS(4), ZK_AS(5), ZK_AS(6));
+        if constexpr (N == 8) fips::mac8_vs_set(lo, hi, ad, ZK_AS(0), ZK_AS(1), ZK_AS(2), ZK_AS(3), ZK_AS(4), ZK_AS(5), ZK_AS(6), ZK_AS(7));
+#undef ZK_AS
+    }
+    static __device__ __forceinline__ fe ldot6(const fe (&x)[6], const fe *__restrict__ row) {
+        uint64_t lo = 0, ad; uint32_t hi;
+        uint32_t m[8], t[8];
+        fips::mac1_vs_sethi(lo, hi, x[0].l[0], row[0].l[0]);    // column 0: six products, no addend
+        fips::mac5_vs(lo, hi, x[1].l[0], row[1].l[0], x[2].l[0], row[2].l[0], x[3].l[0], row[3].l[0], x[4].l[0], row[4].l[0], x[5].l[0], row[5].l[0]);
+        m[0] = mont_m((uint32_t)lo);
+        fips::mac1_vs(lo, hi, m[0], P::p(0));
+        ad = next_addend(lo, hi);
+#define ZK_LOW(I) \
+        col_as_set<I + 1, 0, I>(lo, hi, ad, x[0], row[0]); \
+        col_as<I + 1, 0, I>(lo, hi, x[1], row[1]); col_as<I + 1, 0, I>(lo, hi, x[2], row[2]); col_as<I + 1, 0, I>(lo, hi, x[3], row[3]); \
+        col_as<I + 1, 0, I>(lo, hi, x[4], row[4]); col_as<I + 1, 0, I>(lo, hi, x[5], row[5]); \
+        col_mp<I, 0, I>(lo, hi, m); \
+        m[I] = mont_m((uint32_t)lo); \
+        fips::mac1_vs(lo, hi, m[I], P::p(0)); \
+        ad = next_addend(lo, hi);
+#define ZK_HIGH(I) \
+        col_as_set<15 - I, I - 7, I>(lo, hi, ad, x[0], row[0]); \
+        col_as<15 - I, I - 7, I>(lo, hi, x[1], row[1]); col_as<15 - I, I - 7, I>(lo, hi, x[2], row[2]); col_as<15 - I, I - 7, I>(lo, hi, x[3], row[3]); \
+        col_as<15 - I, I - 7, I>(lo, hi, x[4], row[4]); col_as<15 - I, I - 7, I>(lo, hi, x[5], row[5]); \
+        col_mp<15 - I, I - 7, I>(lo, hi, m); \
+        t[I - 8] = (uint32_t)lo; \
+        ad = next_addend(lo, hi);
+        ZK_LOW(1) ZK_LOW(2) ZK_LOW(3) ZK_LOW(4) ZK_LOW(5) ZK_LOW(6) ZK_LOW(7)
+        ZK_HIGH(8) ZK_HIGH(9) ZK_HIGH(10) ZK_HIGH(11) ZK_HIGH(12) ZK_HIGH(13) ZK_HIGH(14)
+#undef ZK_LOW
+#undef ZK_HIGH
+        t[7] = (uint32_t)ad;
+        fe r;
+#pragma unroll
+        for (int i = 0; i < 8; i++) r.l[i] = t[i];
+        if constexpr (P::is_fq) fips::reduce8_fq2(r.l); else fips::reduce8_fr2(r.l);
+        return r;
+    }
     // ---- dual forms: TWO independent products advance together, instruction by instruction, so that the serial tail of every
     // column of one (last multiply-add -> m_i -> m_i p_0 -> next column's addend) fills with the other's multiply-adds
     // (fips_asm.hpp, *_x2).  Measured (tools/mulbench.cpp, profiles/r03_dual_issue.txt): a chain of single products gains 14 % at
@@ -401,6 +468,11 @@ struct Field {
     static ZK_HD fe lmul2(const fe &a, const fe &b, const fe &c, const fe &d) { return add(mul(a, b), mul(c, d)); }
     static ZK_HD fe lmul4(const fe &a, const fe &b, const fe &c, const fe &d, const fe &e, const fe &f, const fe &g, const fe &h) {
         return add(add(mul(a, b), mul(c, d)), add(mul(e, f), mul(g, h)));
+    }
+    static ZK_HD fe ldot6(const fe (&x)[6], const fe *row) {
+        fe s = mul(x[0], row[0]);
+        for (int i = 1; i < 6; i++) s = add(s, mul(x[i], row[i]));
+        return s;
     }
     static ZK_HD fe ladd(const fe &a, const fe &b) { return add(a, b); }
     static ZK_HD fe lsub(const fe &a, const fe &b) { return sub(a, b); }

@@ -5,6 +5,7 @@
 // bulk build costs (large levels + 1) hashing launches and a single append exactly one.  An update works the same way from the sorted,
 // de-duplicated parent lists the host derives from the indices (k x depth integers).  ZK_MTREE_NO_TAIL=1 in the environment at creation makes
 // a tree launch every level on its own instead: the form the tail kernel is measured against (profiles/merkle_tree.txt).
+// A tree over the Poseidon hasher (zk_mtree_create_ex; node width 2, 3 or 4) has the same launch structure with the k_poseidon_merkle_* kernels.
 #include <algorithm>
 #include <memory>
 #include <mutex>
@@ -13,6 +14,7 @@
 #include <string.h>
 #include "bn254.hpp"
 #include "merkle.hpp"
+#include "poseidon.hpp"
 #include "../../include/ethsnarks_hip/gadgets.hpp"              // the streaming sha256 and keccak256 (host code)
 #include "../../include/zkhip.h"
 
@@ -64,6 +66,35 @@ const Consts &host_consts() {
     return c;
 }
 
+// Poseidon (poseidon.hpp): C_i and the c of the Cauchy matrix M[i][j] = 1 / (c_i - c_{6+j}) are blake2b-256 chains -- the seed is hashed, then
+// the raw 32-byte digest again and again; each digest read little-endian and reduced mod r, the reduction never feeding back into the chain
+// (ethsnarks/poseidon/permutation.py:94-117, src/gadgets/poseidon.hpp:66-108).  Montgomery, canonical; C first, then M row major.
+struct PConsts { fe c[poseidon::ROUNDS]; fe m[poseidon::T * poseidon::T]; };
+static_assert(sizeof(PConsts) == sizeof(fe) * poseidon::N_CONSTS, "the device table is C then M");
+void poseidon_chain(const char *seed, uint32_t n, fe *out) {
+    uint8_t dg[32], nx[32];
+    ethsnarks::hashes::blake2b((const uint8_t *)seed, strlen(seed), dg);
+    for (uint32_t i = 0; i < n; i++) {
+        fe v;
+        for (int k = 0; k < 8; k++) v.l[k] = (uint32_t)dg[4 * k] | ((uint32_t)dg[4 * k + 1] << 8) | ((uint32_t)dg[4 * k + 2] << 16) | ((uint32_t)dg[4 * k + 3] << 24);
+        out[i] = Fr::to_mont(v);                                // (the Montgomery product by R^2 reduces any value < 2^256)
+        ethsnarks::hashes::blake2b(dg, 32, nx);
+        memcpy(dg, nx, 32);
+    }
+}
+const PConsts &host_pconsts() {
+    static PConsts c;
+    static std::once_flag once;
+    std::call_once(once, [] {
+        poseidon_chain("poseidon_constants", poseidon::ROUNDS, c.c);
+        fe x[2 * poseidon::T];
+        poseidon_chain("poseidon_matrix_0000", 2 * poseidon::T, x);
+        for (uint32_t i = 0; i < poseidon::T; i++)
+            for (uint32_t j = 0; j < poseidon::T; j++) c.m[poseidon::T * i + j] = Fr::inv(Fr::sub(x[i], x[poseidon::T + j]));
+    });
+    return c;
+}
+
 // unique(d, index) = sha256(be16(d) || be240(index)) mod r, Montgomery
 fe placeholder(uint32_t d, uint64_t index) {
     uint8_t msg[32] = {0}, dg[32];
@@ -83,7 +114,8 @@ bool all_below_modulus(const uint64_t *v, uint64_t n) {
 
 struct zk_mtree {
     int device = 0;
-    uint32_t depth = 0;
+    uint32_t depth = 0, width = 2;
+    int hasher = ZK_MTREE_HASH_MIMC;
     uint64_t n = 0;                                             // leaves
     bool use_tail = true;
     hipStream_t st = nullptr;
@@ -91,19 +123,22 @@ struct zk_mtree {
     uint64_t cap[MAX_DEPTH + 1] = {0};
     fe **d_lvl = nullptr;                                       // the pointers above, for the kernels
     fe *d_consts = nullptr;                                     // Consts
-    fe *d_ph = nullptr;                                         // MAX_DEPTH placeholders: unique(d, level_count(n, d))
+    fe *d_pconsts = nullptr;                                    // PConsts (Poseidon trees only)
+    fe *d_ph = nullptr;                                         // MAX_DEPTH x (width - 1) placeholders: unique(d, count(d) + k)
     uint32_t *d_bad = nullptr;
     void *d_scratch = nullptr; size_t scratch_cap = 0;          // indices, lists, gathered paths: grows, never shrinks
     ~zk_mtree() {
         for (fe *p : lvl) if (p) (void)hipFree(p);
-        void *bufs[] = {d_lvl, d_consts, d_ph, d_bad, d_scratch};
+        void *bufs[] = {d_lvl, d_consts, d_pconsts, d_ph, d_bad, d_scratch};
         for (void *b : bufs) if (b) (void)hipFree(b);
         if (st) (void)hipStreamDestroy(st);
     }
-    uint64_t level_cap_max(uint32_t d) const { return (uint64_t)1 << (depth - d); }
+    uint64_t level_cap_max(uint32_t d) const { return pow_w(width, depth - d); }
+    uint64_t count(uint64_t leaves, uint32_t d) const { return level_count_w(leaves, d, width); }
+    bool is_poseidon() const { return hasher == ZK_MTREE_HASH_POSEIDON; }
     TreeView view() const {
         TreeView v;
-        v.lvl = d_lvl; v.ph = d_ph; v.rc = d_consts; v.iv = d_consts + MIMC_ROUNDS; v.n = n; v.depth = depth;
+        v.lvl = d_lvl; v.ph = d_ph; v.rc = d_consts; v.iv = d_consts + MIMC_ROUNDS; v.pc = d_pconsts; v.n = n; v.depth = depth; v.width = width;
         return v;
     }
 };
@@ -121,8 +156,11 @@ int mt_scratch(zk_mtree *t, size_t bytes) {
 
 // placeholders for a tree of n_new leaves, queued on the stream (before the kernels that read them)
 int mt_put_placeholders(zk_mtree *t, uint64_t n_new) {
-    fe ph[MAX_DEPTH];
-    for (uint32_t d = 0; d < MAX_DEPTH; d++) ph[d] = d < t->depth ? placeholder(d, level_count(n_new, d)) : Fr::zero();
+    fe ph[MAX_DEPTH * (MAX_WIDTH - 1)];
+    const uint32_t per = t->width - 1;
+    for (uint32_t d = 0; d < MAX_DEPTH; d++)
+        for (uint32_t k = 0; k < per; k++) ph[d * per + k] = d < t->depth ? placeholder(d, t->count(n_new, d) + k) : Fr::zero();
+    for (uint32_t i = MAX_DEPTH * per; i < MAX_DEPTH * (MAX_WIDTH - 1); i++) ph[i] = Fr::zero();
     ZK_HIP(hipMemcpyAsync(t->d_ph, ph, sizeof(ph), hipMemcpyHostToDevice, t->st));
     ZK_HIP(hipStreamSynchronize(t->st));                        // (ph lives on this stack frame)
     return ZK_OK;
@@ -134,7 +172,7 @@ int mt_grow(zk_mtree *t, uint64_t n_new) {
     uint64_t fresh_cap[MAX_DEPTH + 1] = {0};
     bool any = false;
     for (uint32_t d = 0; d <= t->depth; d++) {
-        const uint64_t need = level_count(n_new, d);
+        const uint64_t need = t->count(n_new, d);
         if (need <= t->cap[d]) continue;
         const uint64_t want = std::min(std::max(need, 2 * t->cap[d]), t->level_cap_max(d));
         if (hipMalloc(&fresh[d], sizeof(fe) * want) != hipSuccess) {
@@ -147,7 +185,7 @@ int mt_grow(zk_mtree *t, uint64_t n_new) {
     if (!any) return ZK_OK;
     for (uint32_t d = 0; d <= t->depth; d++) {
         if (!fresh[d]) continue;
-        const uint64_t used = level_count(t->n, d);
+        const uint64_t used = t->count(t->n, d);
         if (used) ZK_HIP(hipMemcpyAsync(fresh[d], t->lvl[d], sizeof(fe) * used, hipMemcpyDeviceToDevice, t->st));
     }
     ZK_HIP(hipStreamSynchronize(t->st));
@@ -165,11 +203,15 @@ int mt_hash_appended(zk_mtree *t, uint64_t s_old) {
     const TreeView v = t->view();
     uint32_t d = 0;
     for (; d < t->depth; d++) {
-        const uint64_t j0 = s_old >> (d + 1), nj = level_count(t->n, d + 1) - j0;
+        const uint64_t j0 = s_old / pow_w(t->width, d + 1), nj = t->count(t->n, d + 1) - j0;
         if (t->use_tail && nj <= TAIL_BLOCK) break;
-        ZK_LAUNCH(k_mimc_merkle_level, zk_div_up(nj, LEVEL_BLOCK), LEVEL_BLOCK, t->st, v, d, j0, nj);
+        if (t->is_poseidon()) ZK_LAUNCH(k_poseidon_merkle_level, zk_div_up(nj, LEVEL_BLOCK), LEVEL_BLOCK, t->st, v, d, j0, nj);
+        else ZK_LAUNCH(k_mimc_merkle_level, zk_div_up(nj, LEVEL_BLOCK), LEVEL_BLOCK, t->st, v, d, j0, nj);
     }
-    if (d < t->depth) ZK_LAUNCH_SYNC(k_mimc_merkle_tail, 1, TAIL_BLOCK, t->st, v, d, s_old, (const uint64_t *)nullptr, (const uint32_t *)nullptr, 0u);
+    if (d < t->depth) {
+        if (t->is_poseidon()) ZK_LAUNCH_SYNC(k_poseidon_merkle_tail, 1, TAIL_BLOCK, t->st, v, d, s_old, (const uint64_t *)nullptr, (const uint32_t *)nullptr, 0u);
+        else ZK_LAUNCH_SYNC(k_mimc_merkle_tail, 1, TAIL_BLOCK, t->st, v, d, s_old, (const uint64_t *)nullptr, (const uint32_t *)nullptr, 0u);
+    }
     ZK_HIP(hipGetLastError());
     return ZK_OK;
 }
@@ -177,7 +219,7 @@ int mt_hash_appended(zk_mtree *t, uint64_t s_old) {
 // leaves: host pointer (checked by the caller) or device pointer
 int mt_append(zk_mtree *t, const void *src, bool resident, uint64_t n, int canonical) {
     if (n == 0) return ZK_OK;
-    if (n > t->level_cap_max(0) - t->n) return mfail(ZK_ERR_ARG, "the tree is full: more leaves than 2^depth");
+    if (n > t->level_cap_max(0) - t->n) return mfail(ZK_ERR_ARG, "the tree is full: more leaves than width^depth");
     ZK_TRY(mt_use_device(t->device));
     const uint64_t s_old = t->n, n_new = s_old + n;
     ZK_TRY(mt_grow(t, n_new));
@@ -210,23 +252,42 @@ int mt_upload_indices(zk_mtree *t, const uint64_t *indices, uint32_t k, size_t e
 }
 }  // namespace
 
-extern "C" int zk_mtree_create(uint32_t depth, uint64_t reserve_leaves, int device, zk_mtree **out) try {
+extern "C" int zk_mtree_create_ex(uint32_t depth, uint32_t width, int hasher, uint64_t reserve_leaves, int device, zk_mtree **out) try {
     if (!out) return mfail(ZK_ERR_ARG, "null argument");
     *out = nullptr;
+    if (hasher != ZK_MTREE_HASH_MIMC && hasher != ZK_MTREE_HASH_POSEIDON) return mfail(ZK_ERR_ARG, "unknown hasher");
+    if (hasher == ZK_MTREE_HASH_MIMC && width != 2) return mfail(ZK_ERR_ARG, "the MiMC tree has node width 2");
+    if (width < 2 || width > MAX_WIDTH) return mfail(ZK_ERR_ARG, "the Poseidon tree has node width 2, 3 or 4");
     if (depth < 1 || depth > MAX_DEPTH) return mfail(ZK_ERR_ARG, "depth must be in 1 .. 29");
+    if (hasher == ZK_MTREE_HASH_POSEIDON && depth > (width == 2 ? 29u : width == 3 ? 18u : 14u))
+        return mfail(ZK_ERR_ARG, "a Poseidon tree holds at most 2^29 leaves: depth <= 29, 18, 14 at width 2, 3, 4");
     ZK_TRY(mt_use_device(device));
     std::unique_ptr<zk_mtree> t(new zk_mtree());
-    t->device = device; t->depth = depth;
+    t->device = device; t->depth = depth; t->width = width; t->hasher = hasher;
     if (const char *e = getenv("ZK_MTREE_NO_TAIL")) t->use_tail = !(e[0] == '1');
     ZK_HIP(hipStreamCreateWithFlags(&t->st, hipStreamNonBlocking));
     const Consts &c = host_consts();
-    if (hipMalloc(&t->d_consts, sizeof(Consts)) != hipSuccess || hipMalloc(&t->d_ph, sizeof(fe) * MAX_DEPTH) != hipSuccess ||
+    if (hipMalloc(&t->d_consts, sizeof(Consts)) != hipSuccess || (t->is_poseidon() && hipMalloc(&t->d_pconsts, sizeof(PConsts)) != hipSuccess) ||
+        hipMalloc(&t->d_ph, sizeof(fe) * MAX_DEPTH * (MAX_WIDTH - 1)) != hipSuccess ||
         hipMalloc(&t->d_lvl, sizeof(t->lvl)) != hipSuccess || hipMalloc(&t->d_bad, 4) != hipSuccess)
         return mfail(ZK_ERR_NOMEM, "device allocation failed (Merkle tree)");
     ZK_HIP(hipMemcpy(t->d_consts, &c, sizeof(Consts), hipMemcpyHostToDevice));
+    if (t->is_poseidon()) ZK_HIP(hipMemcpy(t->d_pconsts, &host_pconsts(), sizeof(PConsts), hipMemcpyHostToDevice));   // (a MiMC tree has no use for them)
     ZK_TRY(mt_grow(t.get(), std::max<uint64_t>(1, std::min(reserve_leaves, t->level_cap_max(0)))));
     ZK_TRY(mt_put_placeholders(t.get(), 0));
     *out = t.release();
+    return ZK_OK;
+} ZK_GUARD
+
+extern "C" int zk_mtree_create(uint32_t depth, uint64_t reserve_leaves, int device, zk_mtree **out) {
+    return zk_mtree_create_ex(depth, 2, ZK_MTREE_HASH_MIMC, reserve_leaves, device, out);
+}
+
+extern "C" int zk_mtree_info(const zk_mtree *t, uint32_t *depth, uint32_t *width, int *hasher) try {
+    if (!t) return mfail(ZK_ERR_ARG, "null argument");
+    if (depth) *depth = t->depth;
+    if (width) *width = t->width;
+    if (hasher) *hasher = t->hasher;
     return ZK_OK;
 } ZK_GUARD
 
@@ -244,7 +305,7 @@ extern "C" int zk_mtree_size(const zk_mtree *t, uint64_t *n_leaves) try {
 
 extern "C" int zk_mtree_append(zk_mtree *t, const uint64_t *leaves, uint64_t n, int canonical) try {
     if (!t || (n && !leaves)) return mfail(ZK_ERR_ARG, "null argument");
-    if (n > t->level_cap_max(0) - t->n) return mfail(ZK_ERR_ARG, "the tree is full: more leaves than 2^depth");
+    if (n > t->level_cap_max(0) - t->n) return mfail(ZK_ERR_ARG, "the tree is full: more leaves than width^depth");
     if (!all_below_modulus(leaves, n)) return mfail(ZK_ERR_ARG, "a leaf is not below the Fr modulus");
     return mt_append(t, leaves, false, n, canonical);
 } ZK_GUARD
@@ -276,7 +337,7 @@ extern "C" int zk_mtree_update(zk_mtree *t, const uint64_t *indices, const uint6
     uint32_t nlist[MAX_DEPTH] = {0};
     std::vector<uint64_t> cur(idx);
     for (uint32_t d = 0; d < D; d++) {
-        for (auto &j : cur) j >>= 1;
+        for (auto &j : cur) j /= t->width;
         cur.erase(std::unique(cur.begin(), cur.end()), cur.end());
         nlist[d] = (uint32_t)cur.size();
         std::copy(cur.begin(), cur.end(), lists.begin() + (size_t)d * m);
@@ -295,9 +356,13 @@ extern "C" int zk_mtree_update(zk_mtree *t, const uint64_t *indices, const uint6
     uint32_t d = 0;
     for (; d < D; d++) {
         if (t->use_tail && nlist[d] <= TAIL_BLOCK) break;
-        ZK_LAUNCH(k_mimc_merkle_update, zk_div_up(nlist[d], LEVEL_BLOCK), LEVEL_BLOCK, t->st, v, d, (const uint64_t *)(s + o_lists) + (size_t)d * m, nlist[d]);
+        if (t->is_poseidon()) ZK_LAUNCH(k_poseidon_merkle_update, zk_div_up(nlist[d], LEVEL_BLOCK), LEVEL_BLOCK, t->st, v, d, (const uint64_t *)(s + o_lists) + (size_t)d * m, nlist[d]);
+        else ZK_LAUNCH(k_mimc_merkle_update, zk_div_up(nlist[d], LEVEL_BLOCK), LEVEL_BLOCK, t->st, v, d, (const uint64_t *)(s + o_lists) + (size_t)d * m, nlist[d]);
     }
-    if (d < D) ZK_LAUNCH_SYNC(k_mimc_merkle_tail, 1, TAIL_BLOCK, t->st, v, d, (uint64_t)0, (const uint64_t *)(s + o_lists), (const uint32_t *)(s + o_nlist), m);
+    if (d < D) {
+        if (t->is_poseidon()) ZK_LAUNCH_SYNC(k_poseidon_merkle_tail, 1, TAIL_BLOCK, t->st, v, d, (uint64_t)0, (const uint64_t *)(s + o_lists), (const uint32_t *)(s + o_nlist), m);
+        else ZK_LAUNCH_SYNC(k_mimc_merkle_tail, 1, TAIL_BLOCK, t->st, v, d, (uint64_t)0, (const uint64_t *)(s + o_lists), (const uint32_t *)(s + o_nlist), m);
+    }
     ZK_HIP(hipGetLastError());
     ZK_HIP(hipStreamSynchronize(t->st));                        // (the staging vectors live until here)
     return ZK_OK;
@@ -305,9 +370,9 @@ extern "C" int zk_mtree_update(zk_mtree *t, const uint64_t *indices, const uint6
 
 extern "C" int zk_mtree_node(const zk_mtree *t, uint32_t level, uint64_t offset, uint64_t out_canon[4]) try {
     if (!t || !out_canon) return mfail(ZK_ERR_ARG, "null argument");
-    if (level > t->depth || offset >= t->level_cap_max(level)) return mfail(ZK_ERR_ARG, "no such node: level <= depth and offset < 2^(depth - level)");
+    if (level > t->depth || offset >= t->level_cap_max(level)) return mfail(ZK_ERR_ARG, "no such node: level <= depth and offset < width^(depth - level)");
     fe v;
-    if (offset < level_count(t->n, level)) {
+    if (offset < t->count(t->n, level)) {
         ZK_TRY(mt_use_device(t->device));
         ZK_HIP(hipMemcpy(&v, t->lvl[level] + offset, sizeof(fe), hipMemcpyDeviceToHost));
     } else v = placeholder(level, offset);
@@ -326,13 +391,14 @@ extern "C" int zk_mtree_paths(const zk_mtree *ct, const uint64_t *indices, uint3
     zk_mtree *t = const_cast<zk_mtree *>(ct);                   // (the stream and the scratch buffer; the tree itself is only read)
     if (!t || (k && !indices)) return mfail(ZK_ERR_ARG, "null argument");
     if (k == 0) return ZK_OK;
+    const size_t per = (size_t)t->depth * (t->width - 1);      // siblings of one path
     const size_t o_leaves = (sizeof(uint64_t) * (size_t)k + 31) & ~(size_t)31, o_paths = o_leaves + sizeof(fe) * (size_t)k;
-    ZK_TRY(mt_upload_indices(t, indices, k, o_paths + sizeof(fe) * (size_t)k * t->depth));
+    ZK_TRY(mt_upload_indices(t, indices, k, o_paths + sizeof(fe) * (size_t)k * per));
     char *s = (char *)t->d_scratch;
-    ZK_LAUNCH(k_mtree_gather, zk_div_up((uint64_t)k * (t->depth + 1), LEVEL_BLOCK), LEVEL_BLOCK, t->st, t->view(), (const uint64_t *)s, k, (fe *)(s + o_leaves), (fe *)(s + o_paths));
+    ZK_LAUNCH(k_mtree_gather, zk_div_up((uint64_t)k * (per + 1), LEVEL_BLOCK), LEVEL_BLOCK, t->st, t->view(), (const uint64_t *)s, k, (fe *)(s + o_leaves), (fe *)(s + o_paths));
     ZK_HIP(hipGetLastError());
     if (leaves_canon) ZK_HIP(hipMemcpyAsync(leaves_canon, s + o_leaves, sizeof(fe) * (size_t)k, hipMemcpyDeviceToHost, t->st));
-    if (paths_canon) ZK_HIP(hipMemcpyAsync(paths_canon, s + o_paths, sizeof(fe) * (size_t)k * t->depth, hipMemcpyDeviceToHost, t->st));
+    if (paths_canon) ZK_HIP(hipMemcpyAsync(paths_canon, s + o_paths, sizeof(fe) * (size_t)k * per, hipMemcpyDeviceToHost, t->st));
     ZK_HIP(hipStreamSynchronize(t->st));
     return ZK_OK;
 } ZK_GUARD
@@ -340,9 +406,11 @@ extern "C" int zk_mtree_paths(const zk_mtree *ct, const uint64_t *indices, uint3
 extern "C" int zk_mtree_fill_witnesses(const zk_mtree *ct, const uint64_t *indices, uint32_t k, void *d_w, uint64_t row_elems, const zk_mtree_layout *layout) try {
     zk_mtree *t = const_cast<zk_mtree *>(ct);
     if (!t || (k && !indices) || !d_w || !layout) return mfail(ZK_ERR_ARG, "null argument");
+    if (t->width != 2) return mfail(ZK_ERR_ARG, "the membership circuit exists for node width 2 only (there is no wide path selector)");
     if (k == 0) return ZK_OK;
     if (t->n == 0) return mfail(ZK_ERR_ARG, "the tree is empty: it has no root");
     const uint64_t D = t->depth;
+    if (t->is_poseidon() && layout->n_iv != 0) return mfail(ZK_ERR_ARG, "the Poseidon membership circuit has no IV variables: layout.n_iv must be 0");
     if (layout->n_iv > MAX_DEPTH || row_elems == 0 || layout->root_var >= row_elems || layout->leaf_var >= row_elems || layout->addr_var0 + D > row_elems ||
         layout->path_var0 + D > row_elems || (uint64_t)layout->iv_var0 + layout->n_iv > row_elems)
         return mfail(ZK_ERR_ARG, "the layout names a variable outside the witness row");
@@ -379,5 +447,65 @@ extern "C" int zk_mimc_hash2(const uint64_t *left, const uint64_t *right, const 
     ZK_HIP(hipGetLastError());
     ZK_HIP(hipDeviceSynchronize());
     ZK_HIP(hipMemcpy(out, in.p + 3 * (size_t)n, bytes, hipMemcpyDeviceToHost));
+    return ZK_OK;
+} ZK_GUARD
+
+// ---- Poseidon by itself
+extern "C" int zk_poseidon_constants(uint64_t *C_canon, uint64_t *M_canon) try {
+    const PConsts &c = host_pconsts();
+    if (C_canon) for (uint32_t i = 0; i < poseidon::ROUNDS; i++) { const fe v = Fr::from_mont(c.c[i]); memcpy(C_canon + 4 * i, v.l, 32); }
+    if (M_canon) for (uint32_t i = 0; i < poseidon::T * poseidon::T; i++) { const fe v = Fr::from_mont(c.m[i]); memcpy(M_canon + 4 * i, v.l, 32); }
+    return ZK_OK;
+} ZK_GUARD
+
+namespace {
+// ZK_POSEIDON_MIX=lmul / dot6 in the environment picks the MIX form of zk_poseidon_hash and zk_poseidon_permute for a call: a TEST AND
+// MEASUREMENT knob like ZK_MTREE_NO_TAIL (the two forms are tested and measured against each other, tests/test_poseidon_gpu.py,
+// tools/poseidon_bench.py; documented in zkhip.h); unset or anything else: the form the tree uses.  The tree never reads it
+bool poseidon_use_dot6() {
+    const char *e = getenv("ZK_POSEIDON_MIX");
+    if (e && !strcmp(e, "lmul")) return false;
+    if (e && !strcmp(e, "dot6")) return true;
+    return poseidon::POSEIDON_MIX_DOT6;
+}
+struct DevBuf { fe *p = nullptr; ~DevBuf() { if (p) (void)hipFree(p); } };
+}  // namespace
+
+extern "C" int zk_poseidon_hash(const uint64_t *inputs, uint32_t n_in, uint32_t n, int device, uint64_t *out) try {
+    if (!inputs || !out) return mfail(ZK_ERR_ARG, "null argument");
+    if (n_in < 1 || n_in >= poseidon::T) return mfail(ZK_ERR_ARG, "a hash takes 1 .. 5 inputs");
+    if (n == 0) return ZK_OK;
+    if (!all_below_modulus(inputs, (uint64_t)n * n_in)) return mfail(ZK_ERR_ARG, "an operand is not below the Fr modulus");
+    ZK_TRY(mt_use_device(device));
+    const PConsts &c = host_pconsts();
+    DevBuf in, pc, o;
+    if (hipMalloc(&in.p, sizeof(fe) * (size_t)n * n_in) != hipSuccess || hipMalloc(&pc.p, sizeof(PConsts)) != hipSuccess || hipMalloc(&o.p, sizeof(fe) * (size_t)n) != hipSuccess)
+        return mfail(ZK_ERR_NOMEM, "device allocation failed");
+    ZK_HIP(hipMemcpy(in.p, inputs, sizeof(fe) * (size_t)n * n_in, hipMemcpyHostToDevice));
+    ZK_HIP(hipMemcpy(pc.p, &c, sizeof(PConsts), hipMemcpyHostToDevice));
+    if (poseidon_use_dot6()) ZK_LAUNCH(poseidon::k_poseidon_hash<true>, zk_div_up(n, poseidon::BLOCK), poseidon::BLOCK, nullptr, (const fe *)in.p, n_in, n, (const fe *)pc.p, o.p);
+    else ZK_LAUNCH(poseidon::k_poseidon_hash<false>, zk_div_up(n, poseidon::BLOCK), poseidon::BLOCK, nullptr, (const fe *)in.p, n_in, n, (const fe *)pc.p, o.p);
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipDeviceSynchronize());
+    ZK_HIP(hipMemcpy(out, o.p, sizeof(fe) * (size_t)n, hipMemcpyDeviceToHost));
+    return ZK_OK;
+} ZK_GUARD
+
+extern "C" int zk_poseidon_permute(uint64_t *states, uint32_t n, int device) try {
+    if (!states) return mfail(ZK_ERR_ARG, "null argument");
+    if (n == 0) return ZK_OK;
+    if (!all_below_modulus(states, (uint64_t)n * poseidon::T)) return mfail(ZK_ERR_ARG, "an operand is not below the Fr modulus");
+    ZK_TRY(mt_use_device(device));
+    const PConsts &c = host_pconsts();
+    DevBuf st, pc;
+    const size_t bytes = sizeof(fe) * (size_t)n * poseidon::T;
+    if (hipMalloc(&st.p, bytes) != hipSuccess || hipMalloc(&pc.p, sizeof(PConsts)) != hipSuccess) return mfail(ZK_ERR_NOMEM, "device allocation failed");
+    ZK_HIP(hipMemcpy(st.p, states, bytes, hipMemcpyHostToDevice));
+    ZK_HIP(hipMemcpy(pc.p, &c, sizeof(PConsts), hipMemcpyHostToDevice));
+    if (poseidon_use_dot6()) ZK_LAUNCH(poseidon::k_poseidon_permute<true>, zk_div_up(n, poseidon::BLOCK), poseidon::BLOCK, nullptr, st.p, n, (const fe *)pc.p);
+    else ZK_LAUNCH(poseidon::k_poseidon_permute<false>, zk_div_up(n, poseidon::BLOCK), poseidon::BLOCK, nullptr, st.p, n, (const fe *)pc.p);
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipDeviceSynchronize());
+    ZK_HIP(hipMemcpy(states, st.p, bytes, hipMemcpyDeviceToHost));
     return ZK_OK;
 } ZK_GUARD

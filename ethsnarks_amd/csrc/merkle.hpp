@@ -20,14 +20,23 @@
 //   k_mtree_gather        leaves and authentication paths of k indices (canonical, for the host)
 //   k_mtree_fill_witness  the membership circuit's inputs of k indices, straight into k rows of a device witness buffer
 //   k_mimc_hash2          n independent two-block hashes (test entry point)
+//
+// The same tree over the Poseidon hasher (MerkleHasher_Poseidon, merkletree.py:63-78; the permutation is poseidon.hpp) has node widths
+// w = 2, 3, 4: node j of level d + 1 is poseidon([n(d, w j), .., n(d, w j + w - 1)]) -- no IV, the depth does not enter the hash -- and level d
+// stores cnt_d = ceil(n / w^d) nodes.  The last parent of a level can meet up to w - 1 absent children, at indices cnt_d .. (next multiple of
+// w) - 1, so the placeholder table holds w - 1 entries per level: ph[d (w - 1) + k] = unique(d, cnt_d + k).  (w = 2: the MiMC table.)
+//   k_poseidon_merkle_level / _update / _tail    the three hashing kernels above, for the Poseidon hasher; the width is a wave-uniform value
+// The kernels that move leaves and paths serve both hashers.
 #pragma once
 #include "bn254.hpp"
+#include "poseidon.hpp"
 
 namespace zk {
 namespace merkle {
 
 constexpr uint32_t MIMC_ROUNDS = 91;
 constexpr uint32_t MAX_DEPTH = 29;                              // the gadget's IV table has 29 entries (merkle_tree_IVs)
+constexpr uint32_t MAX_WIDTH = 4;                               // Poseidon nodes: 2, 3 or 4 children (merkletree.py:68 with t = 6)
 constexpr uint32_t LEVEL_BLOCK = 64;
 constexpr uint32_t TAIL_BLOCK = 256;                            // a level with at most this many parents goes through the tail kernel
 
@@ -57,14 +66,23 @@ ZK_HD bool fr_lt_modulus(const fe &a) {
     return br != 0;
 }
 
-// what every kernel knows of a tree: lvl[d] = the nodes of level d (d = 0 .. depth), ph[d] = unique(d, cnt_d), n = leaves
+// what every kernel knows of a tree: lvl[d] = the nodes of level d (d = 0 .. depth), ph[d (width - 1) + k] = unique(d, cnt_d + k), n = leaves,
+// pc = the Poseidon constants (poseidon.hpp)
 struct TreeView {
     fe *const *lvl;
-    const fe *ph, *rc, *iv;
+    const fe *ph, *rc, *iv, *pc;
     uint64_t n;
-    uint32_t depth;
+    uint32_t depth, width;
 };
 ZK_HD uint64_t level_count(uint64_t n, uint32_t d) { return (n + (((uint64_t)1 << d) - 1)) >> d; }
+// ceil(n / w^d) for w = 2, 3, 4 (a ceiling division taken d times is the ceiling division by w^d)
+ZK_HD uint64_t level_count_w(uint64_t n, uint32_t d, uint32_t w) {
+    if (w == 2) return level_count(n, d);
+    if (w == 4) return level_count(n, 2 * d);
+    for (uint32_t i = 0; i < d; i++) n = (n + w - 1) / w;
+    return n;
+}
+ZK_HD uint64_t pow_w(uint32_t w, uint32_t e) { uint64_t p = 1; for (uint32_t i = 0; i < e; i++) p *= w; return p; }
 
 // parent j of child level d (the caller guarantees 2 j < cnt_d)
 ZK_D void hash_parent(const TreeView &t, uint32_t d, uint64_t j) {
@@ -103,6 +121,48 @@ k_mimc_merkle_tail(TreeView t, uint32_t d_begin, uint64_t s_old, const uint64_t 
     }
 }
 
+// ---- the Poseidon hasher.  Parent j of child level d (the caller guarantees w j < cnt_d): its children, placeholders where the level ends
+ZK_D void poseidon_hash_parent(const TreeView &t, uint32_t d, uint64_t j) {
+    const fe *__restrict__ child = t.lvl[d];
+    const uint32_t w = t.width;
+    const uint64_t cnt = level_count_w(t.n, d, w);
+    fe x[poseidon::T];
+#pragma unroll
+    for (uint32_t k = 0; k < poseidon::T; k++) {
+        const uint64_t c = j * w + k;
+        x[k] = k >= w ? Fr::zero() : c < cnt ? child[c] : t.ph[(size_t)d * (w - 1) + (c - cnt)];
+    }
+    poseidon::permute<poseidon::POSEIDON_MIX_DOT6>(t.pc, x);
+    t.lvl[d + 1][j] = Fr::canon(x[0]);
+}
+
+__global__ void __launch_bounds__(LEVEL_BLOCK)
+k_poseidon_merkle_level(TreeView t, uint32_t d, uint64_t j0, uint64_t nj) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= nj) return;
+    poseidon_hash_parent(t, d, j0 + g);
+}
+
+__global__ void __launch_bounds__(LEVEL_BLOCK)
+k_poseidon_merkle_update(TreeView t, uint32_t d, const uint64_t *__restrict__ list, uint32_t nj) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= nj) return;
+    poseidon_hash_parent(t, d, list[g]);
+}
+
+// as k_mimc_merkle_tail; an append re-hashes on level d + 1 the parents s_old / w^(d+1) .. cnt_{d+1} - 1
+__global__ void __launch_bounds__(TAIL_BLOCK)
+k_poseidon_merkle_tail(TreeView t, uint32_t d_begin, uint64_t s_old, const uint64_t *__restrict__ lists, const uint32_t *__restrict__ nlist, uint32_t stride) {
+    uint64_t pw = pow_w(t.width, d_begin + 1);
+    for (uint32_t d = d_begin; d < t.depth; d++, pw *= t.width) {
+        uint64_t j; bool on;
+        if (lists) { on = threadIdx.x < nlist[d]; j = on ? lists[(size_t)d * stride + threadIdx.x] : 0; }
+        else { j = s_old / pw + threadIdx.x; on = j < level_count_w(t.n, d + 1, t.width); }
+        if (on) poseidon_hash_parent(t, d, j);
+        __syncthreads();
+    }
+}
+
 // leaves in place: bad += 1 for every value >= r (such a value is left as it is); canonical != 0: to Montgomery form
 __global__ void __launch_bounds__(LEVEL_BLOCK)
 k_mtree_ingest(fe *__restrict__ x, uint64_t n, int canonical, uint32_t *__restrict__ bad) {
@@ -121,19 +181,26 @@ k_mtree_set_leaves(TreeView t, const uint64_t *__restrict__ idx, const fe *__res
     t.lvl[0][idx[g]] = vals[g];
 }
 
-// node (d, o) as a path reads it: the stored node or the level's placeholder (o == cnt_d then)
-ZK_D fe node_or_placeholder(const TreeView &t, uint32_t d, uint64_t o) { return o < level_count(t.n, d) ? t.lvl[d][o] : t.ph[d]; }
+// node (d, o) as a path reads it: the stored node or one of the level's placeholders (cnt_d <= o < cnt_d + width - 1 then)
+ZK_D fe node_or_placeholder(const TreeView &t, uint32_t d, uint64_t o) {
+    const uint64_t cnt = level_count_w(t.n, d, t.width);
+    return o < cnt ? t.lvl[d][o] : t.ph[(size_t)d * (t.width - 1) + (o - cnt)];
+}
 
-// one lane per (index, slot): slot 0 = the leaf -> leaves[i], slot 1 + d = the sibling on level d -> paths[i depth + d]; canonical values
+// one lane per (index, slot): slot 0 = the leaf -> leaves[i], slot 1 + d (w - 1) + q = sibling q of level d -> paths[(i depth + d)(w - 1) + q];
+// the siblings of a level are the other nodes of the own parent in node order (merkletree.py:163-177).  Canonical values
 __global__ void __launch_bounds__(LEVEL_BLOCK)
 k_mtree_gather(TreeView t, const uint64_t *__restrict__ idx, uint32_t k, fe *__restrict__ leaves, fe *__restrict__ paths) {
     const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t S = t.depth + 1;
+    const uint32_t w = t.width, P = t.depth * (w - 1), S = P + 1;
     if (g >= (uint64_t)k * S) return;
     const uint32_t i = (uint32_t)(g / S), s = (uint32_t)(g % S);
     const uint64_t a = idx[i];
-    if (s == 0) leaves[i] = Fr::from_mont(t.lvl[0][a]);
-    else paths[(size_t)i * t.depth + (s - 1)] = Fr::from_mont(node_or_placeholder(t, s - 1, (a >> (s - 1)) ^ 1));
+    if (s == 0) { leaves[i] = Fr::from_mont(t.lvl[0][a]); return; }
+    const uint32_t d = (s - 1) / (w - 1), q = (s - 1) % (w - 1);
+    const uint64_t ad = a / pow_w(w, d);                         // the own node on level d
+    const uint32_t own = (uint32_t)(ad % w);
+    paths[(size_t)i * P + (s - 1)] = Fr::from_mont(node_or_placeholder(t, d, ad - own + (q < own ? q : q + 1)));
 }
 
 // where the membership circuit keeps its inputs in a witness row (variable indices; zk_mtree_layout of include/zkhip.h)

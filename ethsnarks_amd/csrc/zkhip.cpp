@@ -2272,7 +2272,24 @@ template <class Op> int probe_launch(const fe *d_in, uint32_t n, fe *d_out) {
     ZK_HIP(hipGetLastError());
     return ZK_OK;
 }
+// ldot6 takes its row from scalar registers: the row must be the same in every lane of a wave.  One case per block of 64 lanes, which all
+// compute it (the row is read through a wave-uniform address, as the Poseidon kernels read theirs); lane 0 stores the result
+template <class F>
+__global__ void __launch_bounds__(64) k_arith_probe_dot6(const fe *__restrict__ in, fe *__restrict__ out, uint32_t n) {
+    const uint32_t i = blockIdx.x;
+    if (i >= n) return;
+    fe a[6];
+#pragma unroll
+    for (uint32_t k = 0; k < 6; k++) a[k] = in[(size_t)i * 12 + k];
+    const fe o = F::ldot6(a, in + (size_t)i * 12 + 6);
+    if (threadIdx.x == 0) out[i] = o;
+}
 template <class F> int probe_field(int idx, const fe *d_in, uint32_t n, fe *d_out) {
+    if (idx == 25) {
+        ZK_LAUNCH((k_arith_probe_dot6<F>), n, 64, nullptr, d_in, d_out, n);
+        ZK_HIP(hipGetLastError());
+        return ZK_OK;
+    }
     switch (idx) {
     case 0: return probe_launch<PrAdd<F>>(d_in, n, d_out);
     case 1: return probe_launch<PrSub<F>>(d_in, n, d_out);
@@ -2319,13 +2336,13 @@ int probe_fq2(int idx, const fe *d_in, uint32_t n, fe *d_out) {
 }
 // words per case in and out; false for an op that does not exist
 bool probe_shape(int op, uint32_t &in_words, uint32_t &out_words) {
-    static const uint8_t field_in[24] = {2, 2, 1, 2, 1, 1, 2, 1, 2, 2, 1, 1, 1, 1, 2, 4, 4, 8, 8, 4, 8, 1, 1, 1};
+    static const uint8_t field_in[26] = {2, 2, 1, 2, 1, 1, 2, 1, 2, 2, 1, 1, 1, 1, 2, 4, 4, 8, 8, 4, 8, 1, 1, 1, 0, 12};   // (24 is not assigned)
     static const uint8_t fq2_in[11] = {4, 2, 8, 4, 4, 2, 2, 2, 2, 2, 4};
     static const uint8_t curve_in[10] = {2, 4, 6, 6, 8, 4, 8, 6, 4, 4}, curve_out[10] = {4, 4, 4, 4, 4, 16, 16, 16, 4, 2};   // in field elements
     if (op < 0) return false;
     const int dom = op & ~0xff, idx = op & 0xff;
     if (dom == ZK_PROBE_FR || dom == ZK_PROBE_FQ) {
-        if (idx >= 24) return false;
+        if (idx >= 26 || idx == 24) return false;
         in_words = field_in[idx]; out_words = idx == 19 || idx == 20 ? 2 : 1;
     } else if (dom == ZK_PROBE_FQ2) {
         if (idx >= 11) return false;

@@ -8,6 +8,8 @@ be proven on a box that has neither libsnark nor the reference checkout:
     merkle_path_selector                   src/gadgets/merkle_tree.cpp:11-63
     markle_path_compute / _authenticator   src/gadgets/merkle_tree.hpp:71-191
     merkle_tree_IVs                        src/gadgets/merkle_tree.cpp:75-113 (= ethsnarks/merkletree.py:36-44)
+    FifthPower_gadget / Poseidon128<nInputs, nOutputs>    src/gadgets/poseidon.hpp:25-63, 145-402, 520-521
+    poseidon_constants / poseidon                         ethsnarks/poseidon/permutation.py:94-196
 
 Variable allocation order and constraint order follow the C++ constructors / generate_r1cs_constraints, so
 the constraint system has the reference's shape (21 345 constraints at depth 29).  The native (out of
@@ -436,3 +438,201 @@ def isnonzero_circuit(values=(0, 5, 0, 7, 1), seed=11):
     assert pb.is_satisfied()
     return r1cs, w, triples
 
+
+
+# ----------------------------------------------------------------------------- Poseidon (permutation.py DefaultParams = Poseidon128)
+POSEIDON_T, POSEIDON_F, POSEIDON_P = 6, 8, 57
+
+
+def _poseidon_chain(seed, n):
+    """blake2b-256 chain: the seed is hashed, then the raw digest again; each digest little-endian, reduced mod r (never fed back reduced)"""
+    out, s = [], seed
+    for _ in range(n):
+        s = hashlib.blake2b(s, digest_size=32).digest()
+        out.append(int.from_bytes(s, "little") % FR)
+    return out
+
+
+_POSEIDON = None
+
+
+def poseidon_constants():
+    """(C, M): the 65 round constants and the 6 x 6 Cauchy matrix M[i][j] = 1 / (c[i] - c[6 + j])"""
+    global _POSEIDON
+    if _POSEIDON is None:
+        t = POSEIDON_T
+        C = _poseidon_chain(b"poseidon_constants", POSEIDON_F + POSEIDON_P)
+        c = _poseidon_chain(b"poseidon_matrix_0000", 2 * t)
+        _POSEIDON = (C, [[pow((c[i] - c[t + j]) % FR, FR - 2, FR) for j in range(t)] for i in range(t)])
+    return _POSEIDON
+
+
+def _poseidon_is_full(i):
+    return i < POSEIDON_F // 2 or i >= POSEIDON_F // 2 + POSEIDON_P
+
+
+def poseidon(inputs, chained=False):
+    """permutation.py:150-196: ARK, S-box (all elements in a full round, element 0 in a partial one), MIX; state[0], or the state when chained"""
+    C, M = poseidon_constants()
+    t = POSEIDON_T
+    assert len(inputs) > 0 and (len(inputs) < t or (chained and len(inputs) == t))
+    state = [int(v) % FR for v in inputs] + [0] * (t - len(inputs))
+    for i, c in enumerate(C):
+        state = [(v + c) % FR for v in state]
+        if _poseidon_is_full(i):
+            state = [pow(v, 5, FR) for v in state]
+        else:
+            state[0] = pow(state[0], 5, FR)
+        state = [sum(M[r][j] * v for j, v in enumerate(state)) % FR for r in range(t)]
+    return state if chained else state[0]
+
+
+def poseidon_merkle_root(leaf, address_bits, path):
+    item = leaf
+    for bit, sib in zip(address_bits, path):
+        item = poseidon([sib, item] if bit else [item, sib])
+    return item
+
+
+class FifthPowerGadget:
+    """FifthPower_gadget, src/gadgets/poseidon.hpp:25-63: x2 = x x, x4 = x2 x2, x5 = x x4 for a linear combination x"""
+
+    def __init__(self, pb):
+        self.pb = pb
+        self.x2, self.x4, self.x5 = pb.allocate(), pb.allocate(), pb.allocate()
+
+    def result(self):
+        return self.x5
+
+    def generate_r1cs_constraints(self, x):
+        pb = self.pb
+        pb.add_r1cs_constraint(x, x, V(self.x2))
+        pb.add_r1cs_constraint(V(self.x2), V(self.x2), V(self.x4))
+        pb.add_r1cs_constraint(x, V(self.x4), V(self.x5))
+
+    def generate_r1cs_witness(self, val_x):
+        x2 = val_x * val_x % FR
+        x4 = x2 * x2 % FR
+        self.pb.set_val(self.x2, x2); self.pb.set_val(self.x4, x4); self.pb.set_val(self.x5, x4 * val_x)
+
+
+class _PoseidonRound:
+    """Poseidon_Round<t, nSBox, nInputs, nOutputs>, src/gadgets/poseidon.hpp:145-265: the state is a list of linear combinations; elements that
+    pass without an S-box stay linear, their round constant collected into the ONE term of every output"""
+
+    def __init__(self, pb, C_i, M, state, n_sbox, n_inputs, n_outputs):
+        t = POSEIDON_T
+        self.pb, self.C_i, self.state, self.n_inputs = pb, C_i, state, n_inputs
+        self.sboxes = [FifthPowerGadget(pb) for _ in range(n_sbox)]
+        self.outputs = []
+        for i in range(n_outputs):
+            lc = {}
+            if n_sbox < t:
+                lc[0] = C_i * sum(M[i][j] for j in range(n_sbox, t)) % FR
+            for s_, g in enumerate(self.sboxes):
+                lc[g.result()] = M[i][s_]
+            for k in range(n_sbox, n_inputs):                     # terms merged per variable index
+                m = M[i][k]
+                for v, c in state[k].items():
+                    lc[v] = (lc.get(v, 0) + c * m) % FR
+            self.outputs.append({v: c for v, c in lc.items() if c})
+
+    def generate_r1cs_constraints(self):
+        for h, g in enumerate(self.sboxes):
+            g.generate_r1cs_constraints(lc_add(self.state[h], self.C_i) if h < self.n_inputs else self.C_i)
+
+    def generate_r1cs_witness(self):
+        vals = self.pb.values
+        for h, g in enumerate(self.sboxes):
+            v = self.C_i
+            if h < self.n_inputs:
+                v += sum(c * vals[i] for i, c in self.state[h].items())
+            g.generate_r1cs_witness(v % FR)
+
+
+class PoseidonGadget:
+    """Poseidon128<nInputs, nOutputs> with constrained outputs (Master_Poseidon_gadget_T, src/gadgets/poseidon.hpp:268-402): the S-box variables
+    x2, x4, x5 in round order (six S-boxes in the full rounds 0-3 and 61-64, one in the partial rounds 4-60), then the output variables;
+    three constraints per S-box in that order, then one  lc * 1 = out  per output: 315 + 1 constraints for <2, 1>"""
+
+    def __init__(self, pb, inputs, n_outputs=1):
+        t, n_rounds = POSEIDON_T, POSEIDON_F + POSEIDON_P
+        assert 0 < len(inputs) < t and 0 < n_outputs <= t
+        C, M = poseidon_constants()
+        self.pb = pb
+        self.rounds = []
+        state = [{v: 1} for v in inputs]
+        for i in range(n_rounds):
+            n_sbox = t if _poseidon_is_full(i) else 1
+            n_in = len(inputs) if i == 0 else t
+            n_out = n_outputs if i == n_rounds - 1 else t
+            self.rounds.append(_PoseidonRound(pb, C[i], M, state, n_sbox, n_in, n_out))
+            state = self.rounds[-1].outputs
+        self.outputs = pb.allocate_array(n_outputs)
+
+    def result(self):
+        return self.outputs[0]
+
+    def generate_r1cs_constraints(self):
+        for r in self.rounds:
+            r.generate_r1cs_constraints()
+        for lc, out in zip(self.rounds[-1].outputs, self.outputs):
+            self.pb.add_r1cs_constraint(lc, 1, V(out))
+
+    def generate_r1cs_witness(self):
+        for r in self.rounds:
+            r.generate_r1cs_witness()
+        vals = self.pb.values
+        for lc, out in zip(self.rounds[-1].outputs, self.outputs):
+            self.pb.set_val(out, sum(c * vals[i] for i, c in lc.items()))
+
+
+def poseidon_membership_circuit(depth=29, leaf=None, address=0, path=None):
+    """Membership in the Poseidon tree of node width 2: per level a merkle_path_selector, then Poseidon128<2, 1> over (left, right); the closing
+    constraint is  result * 1 = root.  Inputs in the order root (public), address bits, path, leaf -- there are no IV variables.
+    322 depth + 1 constraints (29 -> 9 339, domain 2^14), in solved order.  Default witness: the leaf and sibling of merkle_membership_circuit,
+    the other siblings the `unique` placeholders."""
+    item_a = 3703141493535563179657531719960160174296085208671919316200479060314459804651
+    item_b = 134551314051432487569247388144051420116740427803855572138106146683954151557
+    if leaf is None:
+        leaf = item_a
+    if path is None:
+        path = [item_b] + [merkle_unique(d, 1) for d in range(1, depth)]
+    bits = [(address >> i) & 1 for i in range(depth)]
+    root = poseidon_merkle_root(leaf, bits, path)
+    pb = Protoboard()
+    expected_root = pb.allocate(root)
+    pb.set_input_sizes(1)
+    address_bits = pb.allocate_array(depth, bits)
+    path_vars = pb.allocate_array(depth, path)
+    leaf_var = pb.allocate(leaf)
+    item = leaf_var
+    for d in range(depth):
+        sel = MerklePathSelector(pb, item, path_vars[d], address_bits[d])
+        h = PoseidonGadget(pb, [sel.left, sel.right])
+        sel.generate_r1cs_witness(); h.generate_r1cs_witness()
+        sel.generate_r1cs_constraints(); h.generate_r1cs_constraints()
+        item = h.result()
+    pb.add_r1cs_constraint(V(item), 1, V(expected_root))
+    assert pb.val(item) == root
+    r1cs, w = pb.to_r1cs()
+    return r1cs, w, root
+
+
+def poseidon_preimage_circuit(n_inputs=2, seed=7):
+    """Poseidon128<n_inputs, 1> over private inputs, the digest the single public input: 3 (48 + 57) + 1 + 1 constraints"""
+    from .r1cs import SplitMix64
+    rng = SplitMix64(seed)
+    msgs = [rng.fr() for _ in range(n_inputs)]
+    digest = poseidon(msgs)
+    pb = Protoboard()
+    out = pb.allocate(digest)
+    pb.set_input_sizes(1)
+    m = pb.allocate_array(n_inputs, msgs)
+    g = PoseidonGadget(pb, m)
+    g.generate_r1cs_witness()
+    g.generate_r1cs_constraints()
+    pb.add_r1cs_constraint(V(g.result()), 1, V(out))
+    assert pb.val(g.result()) == digest
+    r1cs, w = pb.to_r1cs()
+    return r1cs, w, digest

@@ -1,9 +1,12 @@
-"""MiMC Merkle tree in device memory (zk_mtree_* of include/zkhip.h; kernels in csrc/merkle.hpp).
+"""Merkle trees in device memory: MiMC (node width 2) and Poseidon (node width 2, 3 or 4) (zk_mtree_* of include/zkhip.h; kernels in csrc/merkle.hpp).
 
 The surface of the reference's ethsnarks/merkletree.py (MerkleTree over MerkleHasher_MiMC, width 2): append, update, proof, root,
 leaf(depth, offset) -- plus the bulk forms a GPU needs: extend, update_many, proofs, and fill_witnesses, which writes the inputs of the
 membership circuit (gadgets.merkle_membership_circuit) for k leaves straight into a device witness buffer, ready for
 prover.WitnessPlan.solve and ProverContext.submit_batch(device_ptr=...).  All hashing runs in HIP kernels; there is no CPU path.
+
+MerkleTree(n, hasher="poseidon", width=w) is the reference's MerkleTree over MerkleHasher_Poseidon (csrc/poseidon.hpp): n = w^depth leaf slots,
+proofs with w - 1 siblings per level; poseidon_hash / poseidon_permute / poseidon_constants expose the permutation itself.
 """
 import ctypes as C
 from collections import namedtuple
@@ -16,7 +19,9 @@ from . import prover as P
 
 MAX_DEPTH = 29
 _SYMBOLS = ("zk_mtree_create", "zk_mtree_free", "zk_mtree_size", "zk_mtree_append", "zk_mtree_append_resident", "zk_mtree_update",
-            "zk_mtree_root", "zk_mtree_node", "zk_mtree_paths", "zk_mtree_fill_witnesses", "zk_mimc_constants", "zk_mimc_hash2")
+            "zk_mtree_root", "zk_mtree_node", "zk_mtree_paths", "zk_mtree_fill_witnesses", "zk_mimc_constants", "zk_mimc_hash2",
+            "zk_mtree_create_ex", "zk_mtree_info", "zk_poseidon_constants", "zk_poseidon_hash", "zk_poseidon_permute")
+HASHERS = {"mimc": 0, "poseidon": 1}                          # ZK_MTREE_HASH_*
 
 
 class Layout(C.Structure):
@@ -24,8 +29,11 @@ class Layout(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("root_var", "addr_var0", "path_var0", "leaf_var", "iv_var0", "n_iv")]
 
 
-def membership_layout(depth):
-    """the allocation order of merkle_membership_circuit / merkle_path_authenticator: root, address bits, path, leaf, 29 IVs"""
+def membership_layout(depth, hasher="mimc"):
+    """the allocation order of merkle_membership_circuit / merkle_path_authenticator: root, address bits, path, leaf, 29 IVs;
+    poseidon_membership_circuit has the same order and no IVs"""
+    if hasher == "poseidon":
+        return Layout(1, 2, 2 + depth, 2 + 2 * depth, 0, 0)
     return Layout(1, 2, 2 + depth, 2 + 2 * depth, 3 + 2 * depth, 29)
 
 
@@ -68,23 +76,79 @@ def mimc_hash2(left, right, iv, device=0):
     return F.limbs_to_ints(out)
 
 
-class MerkleProof(namedtuple("MerkleProof", "leaf address path")):
-    """leaf, address bits (level 0 first) and siblings of one leaf"""
+def poseidon_constants():
+    """(C, M) as the kernels use them: 65 round constants, the 6 x 6 matrix as a list of rows"""
+    c = np.zeros((65, 4), dtype=np.uint64)
+    m = np.zeros((36, 4), dtype=np.uint64)
+    P._check(_lib().zk_poseidon_constants(P._p64(c), P._p64(m)))
+    mv = F.limbs_to_ints(m)
+    return F.limbs_to_ints(c), [mv[6 * i:6 * i + 6] for i in range(6)]
+
+
+def poseidon_hash(inputs, device=0):
+    """[poseidon(row) for row in inputs] on the device; every row has the same length, 1 .. 5"""
+    rows = [[int(v) for v in row] for row in inputs]
+    if not rows:
+        return []
+    n_in = len(rows[0])
+    if any(len(r) != n_in for r in rows):
+        raise ValueError("the input lists differ in length")
+    a = F.ints_to_limbs([v for r in rows for v in r]) if n_in else np.zeros((0, 4), dtype=np.uint64)
+    out = np.zeros((len(rows), 4), dtype=np.uint64)
+    P._check(_lib().zk_poseidon_hash(P._p64(a), C.c_uint32(n_in), C.c_uint32(len(rows)), int(device), P._p64(out)))
+    return F.limbs_to_ints(out)
+
+
+def poseidon_permute(states, device=0):
+    """the chained form: every six-element state through the permutation, on the device"""
+    rows = [[int(v) for v in row] for row in states]
+    if not rows:
+        return []
+    if any(len(r) != 6 for r in rows):
+        raise ValueError("a state has six elements")
+    a = F.ints_to_limbs([v for r in rows for v in r])
+    P._check(_lib().zk_poseidon_permute(P._p64(a), C.c_uint32(len(rows)), int(device)))
+    v = F.limbs_to_ints(a)
+    return [v[6 * i:6 * i + 6] for i in range(len(rows))]
+
+
+class MerkleProof(namedtuple("MerkleProof", "leaf address path width hasher", defaults=(2, "mimc"))):
+    """leaf, address digits (level 0 first; bits at width 2) and siblings of one leaf: one sibling per level at width 2, a list of
+    width - 1 per level above that (the other children of the parent, in node order)"""
 
     def verify(self, root):
-        return G.merkle_root(self.leaf, self.address, self.path, G.merkle_ivs(MAX_DEPTH)) == root
+        if self.hasher == "mimc":
+            return G.merkle_root(self.leaf, self.address, self.path, G.merkle_ivs(MAX_DEPTH)) == root
+        item = self.leaf
+        for digit, sibs in zip(self.address, self.path):
+            args = list(sibs) if isinstance(sibs, list) else [sibs]
+            args.insert(digit, item)
+            item = G.poseidon(args)
+        return item == root
 
 
 class MerkleTree:
-    """A tree of n_items = 2^depth leaf slots (depth 1 .. 29) resident on `device`."""
+    """A tree of n_items = width^depth leaf slots resident on `device`: hasher "mimc" (width 2, depth 1 .. 29) or "poseidon" (width 2, 3, 4;
+    at most 2^29 leaf slots)."""
 
-    def __init__(self, n_items, device=0, reserve=0):
-        n_items = int(n_items)
-        if n_items < 2 or n_items & (n_items - 1):
-            raise ValueError("n_items must be a power of two >= 2")
-        self.n_items, self.depth, self.device = n_items, n_items.bit_length() - 1, int(device)
+    def __init__(self, n_items, device=0, reserve=0, *, width=2, hasher="mimc"):
+        n_items, width = int(n_items), int(width)
+        if hasher not in HASHERS:
+            raise ValueError("hasher must be 'mimc' or 'poseidon'")
+        if width < 2:
+            raise ValueError("the node width must be at least 2")
+        depth, cap = 0, 1
+        while cap < n_items:
+            cap *= width
+            depth += 1
+        if n_items < 2 or cap != n_items:
+            raise ValueError("n_items must be a power of two >= 2" if width == 2 else "n_items must be a power of the width")
+        self.n_items, self.depth, self.device, self.width, self.hasher = n_items, depth, int(device), width, hasher
         h = C.c_void_p()
-        P._check(_lib().zk_mtree_create(C.c_uint32(self.depth), C.c_uint64(reserve), self.device, C.byref(h)))
+        if hasher == "mimc" and width == 2:
+            P._check(_lib().zk_mtree_create(C.c_uint32(depth), C.c_uint64(reserve), self.device, C.byref(h)))
+        else:
+            P._check(_lib().zk_mtree_create_ex(C.c_uint32(depth), C.c_uint32(width), HASHERS[hasher], C.c_uint64(reserve), self.device, C.byref(h)))
         self._h = h
 
     # ---- size
@@ -153,10 +217,17 @@ class MerkleTree:
         if k == 0:
             return []
         leaves = np.zeros((k, 4), dtype=np.uint64)
-        paths = np.zeros((k * self.depth, 4), dtype=np.uint64)
+        D, w = self.depth, self.width
+        paths = np.zeros((k * D * (w - 1), 4), dtype=np.uint64)
         P._check(P._lib.zk_mtree_paths(self._h, P._p64(idx), C.c_uint32(k), P._p64(leaves), P._p64(paths)))
-        lv, pv, D = F.limbs_to_ints(leaves), F.limbs_to_ints(paths), self.depth
-        return [MerkleProof(lv[j], [(int(idx[j]) >> d) & 1 for d in range(D)], pv[j * D:(j + 1) * D]) for j in range(k)]
+        lv, pv = F.limbs_to_ints(leaves), F.limbs_to_ints(paths)
+        if w == 2:
+            return [MerkleProof(lv[j], [(int(idx[j]) >> d) & 1 for d in range(D)], pv[j * D:(j + 1) * D], 2, self.hasher) for j in range(k)]
+        out, S = [], D * (w - 1)
+        for j in range(k):
+            digits = [int(idx[j]) // w ** d % w for d in range(D)]
+            out.append(MerkleProof(lv[j], digits, [pv[j * S + d * (w - 1):j * S + (d + 1) * (w - 1)] for d in range(D)], w, self.hasher))
+        return out
 
     def proof(self, index):
         return self.proofs([index])[0]
@@ -170,7 +241,7 @@ class MerkleTree:
             if row_elems is None:
                 raise ValueError("a Layout needs row_elems")
         else:
-            layout = membership_layout(self.depth)
+            layout = membership_layout(self.depth, self.hasher)
             if row_elems is None:
                 if r1cs_or_layout is None:
                     raise ValueError("give the constraint system, or a Layout and row_elems")

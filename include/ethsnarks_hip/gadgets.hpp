@@ -7,6 +7,7 @@
 //   markle_path_compute<HashT>, merkle_path_authenticator    src/gadgets/merkle_tree.hpp:71-191  (the reference spells "markle")
 //   merkle_tree_IVs                                          src/gadgets/merkle_tree.cpp:75-113 (= ethsnarks/merkletree.py:36-44)
 //   mimc(), mimc_hash()                                      src/gadgets/mimc.hpp:352-393 (native evaluation through a protoboard)
+//   FifthPower_gadget, Poseidon_gadget_T, Poseidon128, poseidon()    src/gadgets/poseidon.hpp, ethsnarks/poseidon/permutation.py
 //
 // Same class names, constructor arguments, variable allocation order and constraint order as the reference, so a
 // circuit built here has the reference's shape (depth-29 authenticator: 21 345 constraints) and the reference's
@@ -100,6 +101,48 @@ struct sha256 {                                              // streaming, so a 
         for (int i = 0; i < 8; i++) for (int k = 0; k < 4; k++) out[4 * i + k] = (uint8_t)(hc[i] >> (24 - 8 * k));
     }
 };
+
+// BLAKE2b (RFC 7693), unkeyed, digest of 1 .. 64 bytes: the chain behind the Poseidon constants
+inline uint64_t rotr64(uint64_t v, unsigned n) { return (v >> n) | (v << (64 - n)); }
+inline void blake2b_compress(uint64_t h[8], const uint8_t block[128], uint64_t t, bool last) {
+    static const uint64_t IV[8] = {0x6a09e667f3bcc908ULL, 0xbb67ae8584caa73bULL, 0x3c6ef372fe94f82bULL, 0xa54ff53a5f1d36f1ULL,
+                                   0x510e527fade682d1ULL, 0x9b05688c2b3e6c1fULL, 0x1f83d9abfb41bd6bULL, 0x5be0cd19137e2179ULL};
+    static const uint8_t SIGMA[10][16] = {
+        {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, {14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3},
+        {11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4}, {7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8},
+        {9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13}, {2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9},
+        {12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11}, {13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10},
+        {6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5}, {10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0}};
+    uint64_t m[16], v[16];
+    for (int i = 0; i < 16; i++) { m[i] = 0; for (int k = 7; k >= 0; k--) m[i] = (m[i] << 8) | block[8 * i + k]; }
+    for (int i = 0; i < 8; i++) { v[i] = h[i]; v[8 + i] = IV[i]; }
+    v[12] ^= t;                                              // (the high counter word stays 0: inputs are far below 2^64 bytes)
+    if (last) v[14] = ~v[14];
+    for (int r = 0; r < 12; r++) {
+        const uint8_t *s = SIGMA[r % 10];
+        auto G = [&](int a, int b, int c, int d, uint64_t x, uint64_t y) {
+            v[a] = v[a] + v[b] + x; v[d] = rotr64(v[d] ^ v[a], 32); v[c] = v[c] + v[d]; v[b] = rotr64(v[b] ^ v[c], 24);
+            v[a] = v[a] + v[b] + y; v[d] = rotr64(v[d] ^ v[a], 16); v[c] = v[c] + v[d]; v[b] = rotr64(v[b] ^ v[c], 63);
+        };
+        G(0, 4, 8, 12, m[s[0]], m[s[1]]); G(1, 5, 9, 13, m[s[2]], m[s[3]]); G(2, 6, 10, 14, m[s[4]], m[s[5]]); G(3, 7, 11, 15, m[s[6]], m[s[7]]);
+        G(0, 5, 10, 15, m[s[8]], m[s[9]]); G(1, 6, 11, 12, m[s[10]], m[s[11]]); G(2, 7, 8, 13, m[s[12]], m[s[13]]); G(3, 4, 9, 14, m[s[14]], m[s[15]]);
+    }
+    for (int i = 0; i < 8; i++) h[i] ^= v[i] ^ v[8 + i];
+}
+inline void blake2b(const uint8_t *data, size_t len, uint8_t *out, size_t outlen = 32) {
+    static const uint64_t IV[8] = {0x6a09e667f3bcc908ULL, 0xbb67ae8584caa73bULL, 0x3c6ef372fe94f82bULL, 0xa54ff53a5f1d36f1ULL,
+                                   0x510e527fade682d1ULL, 0x9b05688c2b3e6c1fULL, 0x1f83d9abfb41bd6bULL, 0x5be0cd19137e2179ULL};
+    uint64_t h[8];
+    for (int i = 0; i < 8; i++) h[i] = IV[i];
+    h[0] ^= 0x01010000ULL ^ (uint64_t)outlen;                // parameter block: digest length, no key, fanout = depth = 1
+    size_t off = 0;
+    uint8_t block[128];
+    while (len - off > 128) { memcpy(block, data + off, 128); off += 128; blake2b_compress(h, block, off, false); }
+    memset(block, 0, 128);
+    if (len > off) memcpy(block, data + off, len - off);
+    blake2b_compress(h, block, len, true);                   // the last block (also the only one of an empty message), zero padded
+    for (size_t i = 0; i < outlen; i++) out[i] = (uint8_t)(h[i / 8] >> (8 * (i % 8)));
+}
 }  // namespace hashes
 
 // ------------------------------------------------------------------------------------------ MiMC
@@ -236,6 +279,154 @@ inline const FieldT mimc_hash(const std::vector<FieldT> &m, const FieldT &iv = F
     MiMC_e7_hash_gadget g(pb, viv, vars, "mimc_hash");
     g.generate_r1cs_witness();
     return pb.val(g.result());
+}
+
+// ------------------------------------------------------------------------------------------ Poseidon
+// Poseidon128 = the permutation of ethsnarks/poseidon/permutation.py (DefaultParams: t = 6, 8 full + 57 partial rounds, x^5, one constant per
+// round, a Cauchy matrix) as a gadget with the reference's names (src/gadgets/poseidon.hpp): FifthPower_gadget, Poseidon_gadget_T, Poseidon128.
+// Variables: x2, x4, x5 per S-box in round order (six S-boxes in a full round, one in a partial round), then the output variables; constraints:
+// three per S-box in that order, then one  lc * 1 = out  per output -- what the reference's master gadget lays down and what
+// ethsnarks_amd/gadgets.py PoseidonGadget builds.  An element that passes a round without an S-box stays a linear combination; its round
+// constant is collected into the ONE term of every output of the round.
+struct PoseidonConstants {
+    std::vector<FieldT> C;                                   // one per round
+    std::vector<FieldT> M;                                   // t x t, row major
+};
+// blake2b-256 chain: the seed is hashed, then the raw digest again; every digest little-endian, reduced mod r (the chain runs unreduced)
+inline void poseidon_constants_fill(const std::string &seed, unsigned n_constants, std::vector<FieldT> &result) {
+    uint8_t digest[32], next[32], be[32];
+    hashes::blake2b(reinterpret_cast<const uint8_t *>(seed.data()), seed.size(), digest);
+    result.reserve(result.size() + n_constants);
+    for (unsigned i = 0; i < n_constants; i++) {
+        for (int k = 0; k < 32; k++) be[k] = digest[31 - k];
+        result.push_back(FieldT::from_bytes_be(be));
+        hashes::blake2b(digest, 32, next);
+        memcpy(digest, next, 32);
+    }
+}
+inline const std::vector<FieldT> poseidon_constants(const std::string &seed, unsigned n_constants) { std::vector<FieldT> r; poseidon_constants_fill(seed, n_constants, r); return r; }
+inline void poseidon_matrix_fill(const std::string &seed, unsigned t, std::vector<FieldT> &result) {
+    const std::vector<FieldT> c = poseidon_constants(seed, 2 * t);
+    result.reserve(result.size() + t * t);
+    for (unsigned i = 0; i < t; i++) for (unsigned j = 0; j < t; j++) result.push_back((c[i] - c[t + j]).inverse());
+}
+inline const std::vector<FieldT> poseidon_matrix(const std::string &seed, unsigned t) { std::vector<FieldT> r; poseidon_matrix_fill(seed, t, r); return r; }
+template <unsigned param_t, unsigned param_F, unsigned param_P>
+const PoseidonConstants &poseidon_params() {
+    static PoseidonConstants constants;
+    static std::once_flag once;
+    std::call_once(once, []() {
+        poseidon_constants_fill("poseidon_constants", param_F + param_P, constants.C);
+        poseidon_matrix_fill("poseidon_matrix_0000", param_t, constants.M);
+    });
+    return constants;
+}
+
+// x2 = x x, x4 = x2 x2, x5 = x x4 for a linear combination x
+class FifthPower_gadget : public GadgetT {
+public:
+    const VariableT x2, x4, x5;
+    FifthPower_gadget(ProtoboardT &in_pb, const std::string &annotation_prefix)
+        : GadgetT(in_pb, annotation_prefix), x2(make_variable(in_pb, FMT(annotation_prefix, ".x2"))), x4(make_variable(in_pb, FMT(annotation_prefix, ".x4"))),
+          x5(make_variable(in_pb, FMT(annotation_prefix, ".x5"))) {}
+    const VariableT &result() const { return x5; }
+    void generate_r1cs_constraints(const LinearCombinationT &x) const {
+        pb.add_r1cs_constraint(ConstraintT(x, x, x2), ".x^2 = x * x");
+        pb.add_r1cs_constraint(ConstraintT(x2, x2, x4), ".x^4 = x2 * x2");
+        pb.add_r1cs_constraint(ConstraintT(x, x4, x5), ".x^5 = x * x4");
+    }
+    void generate_r1cs_witness(const FieldT &val_x) const {
+        const FieldT v2 = val_x * val_x, v4 = v2 * v2;
+        pb.val(x2) = v2; pb.val(x4) = v4; pb.val(x5) = v4 * val_x;
+    }
+};
+
+template <unsigned param_t, unsigned param_c, unsigned param_F, unsigned param_P, unsigned nInputs, unsigned nOutputs, bool constrainOutputs = true>
+class Poseidon_gadget_T : public GadgetT {
+    static_assert(nInputs > 0 && nInputs < param_t && nOutputs > 0 && nOutputs <= param_t && param_F % 2 == 0, "Poseidon: 0 < nInputs < t, 0 < nOutputs <= t");
+    // one round: S-boxes on the first n_sbox elements of `state` (+ C_i), n_in of which exist; the outputs are rows of M over the results
+    struct Round {
+        FieldT C_i;
+        unsigned n_in;
+        std::vector<LinearCombinationT> state;
+        std::vector<FifthPower_gadget> sboxes;
+        std::vector<LinearCombinationT> outputs;
+    };
+    std::vector<Round> rounds;
+
+public:
+    const PoseidonConstants &constants;
+    VariableArrayT _output_vars;
+    static constexpr unsigned partial_begin = param_F / 2, partial_end = partial_begin + param_P, total_rounds = param_F + param_P;
+
+    Poseidon_gadget_T(ProtoboardT &in_pb, const VariableArrayT &in_inputs, const std::string &annotation_prefix)
+        : GadgetT(in_pb, annotation_prefix), constants(poseidon_params<param_t, param_F, param_P>()) {
+        if (in_inputs.size() != nInputs) throw std::invalid_argument("Poseidon: the input array does not have nInputs variables");
+        std::vector<LinearCombinationT> state(in_inputs.begin(), in_inputs.end());
+        rounds.reserve(total_rounds);
+        for (unsigned i = 0; i < total_rounds; i++) {
+            const unsigned n_sbox = i < partial_begin || i >= partial_end ? param_t : param_c;
+            const unsigned n_out = i + 1 == total_rounds ? nOutputs : param_t;
+            Round r;
+            r.C_i = constants.C[i]; r.n_in = i == 0 ? nInputs : param_t; r.state = state;
+            r.sboxes.reserve(n_sbox);
+            for (unsigned h = 0; h < n_sbox; h++) r.sboxes.emplace_back(in_pb, FMT(annotation_prefix, ".round[%u].sbox[%u]", i, h));
+            for (unsigned o = 0; o < n_out; o++) {
+                const FieldT *row = &constants.M[o * param_t];
+                LinearCombinationT lc;
+                FieldT constant_term;
+                for (unsigned j = n_sbox; j < param_t; j++) constant_term += r.C_i * row[j];
+                lc.add_term(0, constant_term);
+                for (unsigned h = 0; h < n_sbox; h++) lc.add_term(r.sboxes[h].result().index, row[h]);
+                for (unsigned k = n_sbox; k < r.n_in; k++) lc = lc + r.state[k] * row[k];
+                r.outputs.push_back(lc);
+            }
+            state = r.outputs;
+            rounds.push_back(std::move(r));
+        }
+        if (constrainOutputs) _output_vars = make_var_array(in_pb, nOutputs, FMT(annotation_prefix, ".output"));
+    }
+    const std::vector<LinearCombinationT> &output_lcs() const { return rounds.back().outputs; }
+    const VariableArrayT &outputs() const { return _output_vars; }
+    const VariableT &result() const { return _output_vars.at(0); }
+
+    void generate_r1cs_constraints() const {
+        for (const Round &r : rounds)
+            for (unsigned h = 0; h < r.sboxes.size(); h++)
+                r.sboxes[h].generate_r1cs_constraints(h < r.n_in ? r.state[h] + LinearCombinationT(r.C_i) : LinearCombinationT(r.C_i));
+        if (constrainOutputs)
+            for (unsigned o = 0; o < nOutputs; o++) pb.add_r1cs_constraint(ConstraintT(rounds.back().outputs[o], 1, _output_vars[o]), ".output = last_round.output");
+    }
+    void generate_r1cs_witness() const {
+        for (const Round &r : rounds)
+            for (unsigned h = 0; h < r.sboxes.size(); h++) r.sboxes[h].generate_r1cs_witness(h < r.n_in ? r.C_i + pb.lc_val(r.state[h]) : r.C_i);
+        if (constrainOutputs)
+            for (unsigned o = 0; o < nOutputs; o++) pb.val(_output_vars[o]) = pb.lc_val(rounds.back().outputs[o]);
+    }
+};
+template <unsigned nInputs, unsigned nOutputs, bool constrainOutputs = true>
+using Poseidon128 = Poseidon_gadget_T<6, 1, 8, 57, nInputs, nOutputs, constrainOutputs>;
+
+// native evaluation (permutation.py:150-196), plain field arithmetic: the state after the permutation of (inputs, 0, ..)
+inline std::vector<FieldT> poseidon_permutation(const std::vector<FieldT> &inputs) {
+    constexpr unsigned t = 6, F = 8, P = 57;
+    if (inputs.empty() || inputs.size() > t) throw std::invalid_argument("poseidon: 1 .. 6 state elements");
+    const PoseidonConstants &k = poseidon_params<t, F, P>();
+    std::vector<FieldT> state(inputs);
+    state.resize(t);
+    for (unsigned i = 0; i < F + P; i++) {
+        for (auto &v : state) v += k.C[i];
+        const unsigned n_sbox = i < F / 2 || i >= F / 2 + P ? t : 1;
+        for (unsigned j = 0; j < n_sbox; j++) { const FieldT v2 = state[j] * state[j]; state[j] = v2 * v2 * state[j]; }
+        std::vector<FieldT> next(t);
+        for (unsigned r = 0; r < t; r++) for (unsigned j = 0; j < t; j++) next[r] += k.M[r * t + j] * state[j];
+        state = next;
+    }
+    return state;
+}
+inline const FieldT poseidon(const std::vector<FieldT> &inputs) {
+    if (inputs.size() >= 6) throw std::invalid_argument("poseidon: a hash takes 1 .. 5 inputs");
+    return poseidon_permutation(inputs)[0];
 }
 
 // ------------------------------------------------------------------------------------------ Merkle path

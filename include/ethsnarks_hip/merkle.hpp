@@ -9,6 +9,8 @@
 //   tree.proof(i) / tree.proofs(indices);              leaf, address bits, path (level 0 first)
 //   tree.fill_witnesses(indices, d_w, row_elems);      inputs of merkle_path_authenticator for k leaves into a device witness buffer, for
 //                                                      zk_wplan_solve and zk_prove_batch_submit_resident
+//   ethsnarks::MerkleTreeHIP wide(14, 4, MerkleHasher::Poseidon);   the same tree over Poseidon128, node width 2, 3 or 4 (capacity width^depth
+//                                                      <= 2^29); a proof then carries `digits` and width - 1 siblings per level in `path`
 // Every failure is a mtree_error carrying the C ABI's code and zk_last_error()'s text.
 #pragma once
 #include <zkhip.h>
@@ -28,25 +30,34 @@ struct mtree_error : std::runtime_error {
     explicit mtree_error(int c) : std::runtime_error(std::string(zk_strerror(c)) + ": " + zk_last_error()), code(c) {}
 };
 
+enum class MerkleHasher { MiMC = ZK_MTREE_HASH_MIMC, Poseidon = ZK_MTREE_HASH_POSEIDON };
+
 struct MerkleProofHIP {
     zk_fr leaf;
-    std::vector<bool> address;                                   // bit d: the node is the right child on level d
-    std::vector<zk_fr> path;
+    std::vector<bool> address;                                   // width 2 -- bit d: the node is the right child on level d
+    std::vector<uint32_t> digits;                                // any width: the node's position among the children of its parent on level d
+    std::vector<zk_fr> path;                                     // width - 1 siblings per level, level 0 first, in node order
 };
 
 class MerkleTreeHIP {
     zk_mtree *h_ = nullptr;
-    uint32_t depth_ = 0;
+    uint32_t depth_ = 0, width_ = 2;
+    MerkleHasher hasher_ = MerkleHasher::MiMC;
     static void check(int rc) { if (rc != ZK_OK) throw mtree_error(rc); }
 
 public:
     explicit MerkleTreeHIP(uint32_t depth, uint64_t reserve_leaves = 0, int device = 0) : depth_(depth) { check(zk_mtree_create(depth, reserve_leaves, device, &h_)); }
+    MerkleTreeHIP(uint32_t depth, uint32_t width, MerkleHasher hasher, uint64_t reserve_leaves = 0, int device = 0) : depth_(depth), width_(width), hasher_(hasher) {
+        check(zk_mtree_create_ex(depth, width, (int)hasher, reserve_leaves, device, &h_));
+    }
     ~MerkleTreeHIP() { zk_mtree_free(h_); }
     MerkleTreeHIP(const MerkleTreeHIP &) = delete;
     MerkleTreeHIP &operator=(const MerkleTreeHIP &) = delete;
-    MerkleTreeHIP(MerkleTreeHIP &&o) noexcept : h_(o.h_), depth_(o.depth_) { o.h_ = nullptr; }
+    MerkleTreeHIP(MerkleTreeHIP &&o) noexcept : h_(o.h_), depth_(o.depth_), width_(o.width_), hasher_(o.hasher_) { o.h_ = nullptr; }
 
     uint32_t depth() const { return depth_; }
+    uint32_t width() const { return width_; }
+    MerkleHasher hasher() const { return hasher_; }
     uint64_t size() const { uint64_t n = 0; check(zk_mtree_size(h_, &n)); return n; }
     bool empty() const { return size() == 0; }
     zk_mtree *handle() const { return h_; }
@@ -68,19 +79,27 @@ public:
         const size_t k = indices.size();
         std::vector<MerkleProofHIP> out(k);
         if (!k) return out;
-        std::vector<zk_fr> leaves(k), paths(k * depth_);
+        const size_t per = (size_t)depth_ * (width_ - 1);
+        std::vector<zk_fr> leaves(k), paths(k * per);
         check(zk_mtree_paths(h_, indices.data(), (uint32_t)k, leaves[0].data(), paths[0].data()));
         for (size_t j = 0; j < k; j++) {
             out[j].leaf = leaves[j];
-            out[j].path.assign(paths.begin() + (long)(j * depth_), paths.begin() + (long)((j + 1) * depth_));
-            for (uint32_t d = 0; d < depth_; d++) out[j].address.push_back((indices[j] >> d) & 1);
+            out[j].path.assign(paths.begin() + (long)(j * per), paths.begin() + (long)((j + 1) * per));
+            uint64_t a = indices[j];
+            for (uint32_t d = 0; d < depth_; d++, a /= width_) {
+                out[j].digits.push_back((uint32_t)(a % width_));
+                if (width_ == 2) out[j].address.push_back(a & 1);
+            }
         }
         return out;
     }
     MerkleProofHIP proof(uint64_t index) const { return proofs({index})[0]; }
 
-    // the allocation order of merkle_path_authenticator: root, address bits, path, leaf, 29 IVs
-    zk_mtree_layout membership_layout() const { return zk_mtree_layout{1, 2, 2 + depth_, 2 + 2 * depth_, 3 + 2 * depth_, 29}; }
+    // the allocation order of merkle_path_authenticator: root, address bits, path, leaf, 29 IVs; the Poseidon circuit has no IV variables
+    zk_mtree_layout membership_layout() const {
+        if (hasher_ == MerkleHasher::Poseidon) return zk_mtree_layout{1, 2, 2 + depth_, 2 + 2 * depth_, 0, 0};
+        return zk_mtree_layout{1, 2, 2 + depth_, 2 + 2 * depth_, 3 + 2 * depth_, 29};
+    }
     void fill_witnesses(const std::vector<uint64_t> &indices, void *d_w, uint64_t row_elems) const { fill_witnesses(indices, d_w, row_elems, membership_layout()); }
     void fill_witnesses(const std::vector<uint64_t> &indices, void *d_w, uint64_t row_elems, const zk_mtree_layout &layout) const {
         if (!indices.empty()) check(zk_mtree_fill_witnesses(h_, indices.data(), (uint32_t)indices.size(), d_w, row_elems, &layout));

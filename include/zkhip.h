@@ -59,9 +59,10 @@ extern "C" {
 
 /* ABI version of this header: bumped whenever a struct below changes layout or a function changes signature.
  * 3: zk_config = {multi_exp_c, device, shard_rank, shard_count, max_batch, schedule} (24 bytes; rounds 1-2 had 16 / 24).
+ * 4: the Poseidon entry points (zk_poseidon_*, zk_mtree_create_ex, zk_mtree_info); zk_mtree_paths returns width - 1 siblings per level.
  * A client checks zk_abi_version() == ZK_ABI_VERSION once after loading the library, or passes the size of the zk_config
  * it was compiled with to zk_ctx_create_sized (members it does not know read as 0 = their defaults). */
-#define ZK_ABI_VERSION 3
+#define ZK_ABI_VERSION 4
 
 typedef struct zk_pk zk_pk;
 typedef struct zk_vk zk_vk;
@@ -359,10 +360,34 @@ int zk_dev_download(void *dst, const void *src, size_t bytes);
  *                              zk_prove_batch_submit_resident proves.  merkle_path_authenticator's allocation order (root, address bits,
  *                              path, leaf, IVs) is the layout {1, 2, 2 + D, 2 + 2 D, 3 + 2 D, 29}
  *   zk_mimc_constants          host-only: the 91 round constants and 29 level IVs the kernels use, canonical (either may be NULL)
- *   zk_mimc_hash2              out[i] = mimc_hash([left[i], right[i]], iv[i]) on the device, canonical in and out; an operand >= r is ZK_ERR_ARG */
+ *   zk_mimc_hash2              out[i] = mimc_hash([left[i], right[i]], iv[i]) on the device, canonical in and out; an operand >= r is ZK_ERR_ARG
+ *
+ * ---- the same tree over Poseidon (csrc/poseidon.hpp): MerkleHasher_Poseidon of merkletree.py over the reference's DefaultParams = Poseidon128
+ * (Fr, t = 6, 8 full + 57 partial rounds, x^5, constants from blake2b chains; ethsnarks/poseidon/permutation.py, src/gadgets/poseidon.hpp).
+ *   zk_mtree_create_ex         hasher ZK_MTREE_HASH_MIMC (width 2 only) or ZK_MTREE_HASH_POSEIDON (node width 2, 3 or 4, width^depth <= 2^29:
+ *                              depth <= 29, 18, 14); anything else is ZK_ERR_ARG.  zk_mtree_create(d, ..) = zk_mtree_create_ex(d, 2, MIMC, ..).
+ *                              Poseidon: node j of level d + 1 = poseidon([n(d, w j), .., n(d, w j + w - 1)]) (no IV, the depth does not enter);
+ *                              level d stores ceil(n / w^d) nodes, an absent node reads as unique(d, index) as above.  Every call above works
+ *                              for every width with the same codes, capacity width^depth, offsets < width^(depth - level)
+ *   zk_mtree_info              depth, width and hasher of a tree (any of the three may be NULL)
+ *   zk_mtree_paths             at width w: w - 1 siblings per level, the other children of the own parent in node order (paths_canon holds
+ *                              k x depth x (w - 1) elements); the address digit of index i on level d is (i / w^d) % w
+ *   zk_mtree_fill_witnesses    Poseidon at width 2: layout.n_iv must be 0 (ZK_ERR_ARG otherwise: the circuit has no IV variables); the inputs of poseidon_membership_circuit, layout {1, 2, 2 + D, 2 + 2 D, 0, 0};
+ *                              ZK_ERR_ARG at widths 3 and 4 (the reference has no wide path selector to build a circuit from)
+ *   zk_poseidon_constants      host-only: the 65 round constants and the 6 x 6 matrix (row major), canonical (either may be NULL)
+ *   zk_poseidon_hash           out[i] = poseidon(inputs[i n_in .. i n_in + n_in - 1]) on the device: state = the inputs, then zeros; the result is
+ *                              state[0].  Canonical in and out; an operand >= r, n_in = 0 or n_in > 5 is ZK_ERR_ARG
+ *   zk_poseidon_permute        the "chained" form: n full states of six elements through the permutation, in place, canonical
+ * TEST / MEASUREMENT ONLY: ZK_POSEIDON_MIX=lmul | dot6 in the environment makes zk_poseidon_hash and zk_poseidon_permute run the kernel whose
+ * MIX layer is six plain products per row, or the six-term dot product Field::ldot6 (the default, what the tree always uses).  Both give the
+ * same values; the variable exists so that the two forms can be tested and timed against each other in one build. */
+#define ZK_MTREE_HASH_MIMC 0
+#define ZK_MTREE_HASH_POSEIDON 1
 typedef struct zk_mtree zk_mtree;
 typedef struct { uint32_t root_var, addr_var0, path_var0, leaf_var, iv_var0, n_iv; } zk_mtree_layout;
 int zk_mtree_create(uint32_t depth, uint64_t reserve_leaves, int device, zk_mtree **out);
+int zk_mtree_create_ex(uint32_t depth, uint32_t width, int hasher, uint64_t reserve_leaves, int device, zk_mtree **out);
+int zk_mtree_info(const zk_mtree *t, uint32_t *depth, uint32_t *width, int *hasher);
 void zk_mtree_free(zk_mtree *t);
 int zk_mtree_size(const zk_mtree *t, uint64_t *n_leaves);
 int zk_mtree_append(zk_mtree *t, const uint64_t *leaves, uint64_t n, int canonical);
@@ -370,10 +395,13 @@ int zk_mtree_append_resident(zk_mtree *t, const void *d_leaves, uint64_t n, int 
 int zk_mtree_update(zk_mtree *t, const uint64_t *indices, const uint64_t *leaves, uint32_t k, int canonical);
 int zk_mtree_root(const zk_mtree *t, uint64_t root_canon[4]);
 int zk_mtree_node(const zk_mtree *t, uint32_t level, uint64_t offset, uint64_t out_canon[4]);
-int zk_mtree_paths(const zk_mtree *t, const uint64_t *indices, uint32_t k, uint64_t *leaves_canon /* k x 4 */, uint64_t *paths_canon /* k x depth x 4 */);
+int zk_mtree_paths(const zk_mtree *t, const uint64_t *indices, uint32_t k, uint64_t *leaves_canon /* k x 4 */, uint64_t *paths_canon /* k x depth x (width - 1) x 4 */);
 int zk_mtree_fill_witnesses(const zk_mtree *t, const uint64_t *indices, uint32_t k, void *d_w, uint64_t row_elems, const zk_mtree_layout *layout);
 int zk_mimc_constants(uint64_t *round_constants_canon /* 91 x 4 */, uint64_t *ivs_canon /* 29 x 4 */);
 int zk_mimc_hash2(const uint64_t *left, const uint64_t *right, const uint64_t *iv, uint32_t n, int device, uint64_t *out);
+int zk_poseidon_constants(uint64_t *C_canon /* 65 x 4 */, uint64_t *M_canon /* 36 x 4, row major */);
+int zk_poseidon_hash(const uint64_t *inputs /* n x n_in x 4 */, uint32_t n_in, uint32_t n, int device, uint64_t *out /* n x 4 */);
+int zk_poseidon_permute(uint64_t *states /* n x 6 x 4, in place */, uint32_t n, int device);
 
 /* ---- measurement aids (bench.py): kernel launches issued by this library so far; between zk_profile_begin() and
  * zk_profile_end() every launch is bracketed by a HIP event pair on its own stream -- the sum of the kernel durations
@@ -414,6 +442,9 @@ int zk_pairing_tower_op(int op, const uint64_t *a, const uint64_t *b, uint64_t *
  *     17 lmul4(a, .., h)     18 lmul4(a, b, c, lneg_op(d), e, f, g, lneg_op(h))
  *     19 lmul_x2(a, b, c, d) -> (a b, c d): 2 words      20 lmul2_x2(a, .., h) -> (a b + c d, e f + g h): 2 words
  *     21 to_mont(a)  22 from_mont(a)  23 inv(a)
+ *     25 ldot6(a0 .. a5, b0 .. b5) = a0 b0 + .. + a5 b5 with one reduction: 12 operand words, a0 .. a5 then b0 .. b5 (the a loose, the b
+ *        CANONICAL: the precondition of Field::ldot6), one result word.  (24 is not assigned and stays an unknown op: the probe's own
+ *        argument test uses it as the first index past the table.)
  *   ZK_PROBE_FQ2 (operands and result are Fq2 elements):
  *      0 lmul(a, b)  1 lsqr(a)  2 lmul2(a, b, c, d)  3 ladd(a, b)  4 lsub(a, b)  5 lis_zero(a) (0 or 1 in the low limb of c0)
  *      6 ldbl(a)  7 lneg(a)  8 canon(a)  9 inv(canon(a)) (strict result; 0 -> 0: the form pairing.hpp's f2inv uses)
