@@ -1,0 +1,303 @@
+// jubjub.hpp -- Baby JubJub on the device: curve arithmetic, the windowed Pedersen hash and batch EdDSA verification (jubjub.cpp, zk_jj_*,
+// zk_pedersen_*, zk_eddsa_* of include/zkhip.h).  The native side of ethsnarks/jubjub.py, pedersen.py and eddsa.py; no in-circuit gadgets.
+//
+// The curve is the twisted Edwards curve a x^2 + y^2 = 1 + d x^2 y^2 over Fr with a = 168700 (a square) and d = 168696 (a non-square), so the
+// unified addition below is COMPLETE: no input pair on the curve makes a denominator vanish, Z stays non-zero, and the identity, P = Q, P = -Q and
+// the eight low-order points all go through the same instructions.  Points are extended (X : Y : T : Z), x = X/Z, y = Y/Z, T = XY/Z, in the loose
+// Montgomery domain of bn254.hpp.
+//
+//   addition (EtecPoint.add, HWCD 2008 section 3.1):  A = X1 X2, B = Y1 Y2, C = (d T1) T2, D = Z1 Z2, E = (X1 + Y1)(X2 + Y2) - A - B, F = D - C,
+//                                                     G = D + C, H = B - a A;  X3 = E F, Y3 = G H, T3 = E H, Z3 = F G
+//   doubling (EtecPoint.double, dbl-2008-hwcd):       A = X^2, B = Y^2, C = 2 Z^2, D = a A, E = (X + Y)^2 - A - B, G = D + B, F = G - C, H = D - B;
+//                                                     the same four products
+// The second operand of an addition is always a TABLE point, kept in "addend form" (X, Y, d T, Z): the product by d is paid once per table entry
+// instead of once per addition (10 products).  A table point with Z = 1 -- every point of the Pedersen and fixed-base tables -- is three elements
+// (x, y, d x y) and skips D = Z1 (9 products: the mixed addition).  A doubling is 9 products, 8 when the T it would produce is not read (the next
+// step is another doubling).  The products by a and d go through Fr::lmul with a Montgomery constant: see DESIGN 5h.
+//
+// Code size.  jj_add and jj_dbl are real functions, one body each; inside, the four coordinate products and the four output products are ROLLED
+// loops over small arrays, so a body holds four copies of the field product, not ten.  Every product off the hot path (conversions, the curve
+// equation, the inversion, table set-up) goes through the one body of jj_mul.
+//
+// Kernels (one lane per item, workgroups of 64):
+//   k_jj_scalar_mul   n variable-base multiplications, 4-bit windows, a 16-entry table per lane (private memory), scalars of 256 bits
+//   k_jj_point_op     n additions / doublings / negations of affine points
+//   k_jj_pedersen     n windowed Pedersen hashes over a table of affine multiples in device memory, the window count per lane
+//   k_eddsa_verify    n verdicts S B == R + t A, t = H(R, A, M) computed here for the three schemes of eddsa.py
+#pragma once
+#include "bn254.hpp"
+#include "mimc.hpp"
+
+namespace zk {
+namespace jubjub {
+
+constexpr uint32_t BLOCK = 64;
+constexpr uint32_t WIN = 4, TABLE = 1u << WIN, N_WIN = 256 / WIN;   // scalar multiplication: 64 windows of 4 bits cover any 256-bit scalar
+constexpr uint32_t SEG_WINDOWS = 62;                            // Pedersen: windows per base point (pedersen.py:35)
+constexpr uint32_t FIELD_BITS = 254;                            // FQ.bits(): ceil(log2 r) bits, least significant first
+enum { OP_ADD = 0, OP_DOUBLE = 1, OP_NEGATE = 2 };
+enum { SCHEME_MIMC = 0, SCHEME_PURE = 1, SCHEME_HASH = 2 };
+
+#define ZK_JFN inline ZK_HD_NOINLINE
+
+struct jpoint { fe c[4]; };                                     // X, Y, T (or d T: addend form), Z
+
+ZK_HD fe coef_a() {                                             // 168700 R mod r
+    constexpr uint32_t v[8] = {0xfff261e0u, 0x95accf61u, 0x9df7d378u, 0x24780d65u, 0x7e906ae8u, 0xe0ac11b0u, 0x16d3def3u, 0x0f35db22u};
+    fe r; for (int i = 0; i < 8; i++) r.l[i] = v[i]; return r;
+}
+ZK_HD fe coef_d() {                                             // 168696 R mod r
+    constexpr uint32_t v[8] = {0xaff261f5u, 0x2735f484u, 0x9a2e0f63u, 0x70ba1b57u, 0x1e2caa8cu, 0xff41c9a9u, 0x8fe6025fu, 0x07704a8eu};
+    fe r; for (int i = 0; i < 8; i++) r.l[i] = v[i]; return r;
+}
+
+// the one product body of everything that is not the inside of jj_add / jj_dbl / the MiMC rounds
+ZK_JFN fe jj_mul(const fe &a, const fe &b) { return Fr::lmul(a, b); }
+ZK_HD fe jj_to_mont(const fe &a) { fe r2; for (int i = 0; i < 8; i++) r2.l[i] = FrParams::r2(i); return jj_mul(a, r2); }
+// loose Montgomery -> the canonical integer
+ZK_HD fe jj_from_mont(const fe &a) { fe o = Fr::zero(); o.l[0] = 1; return Fr::canon(jj_mul(a, o)); }
+
+ZK_HD void set_identity(jpoint &p) { p.c[0] = Fr::zero(); p.c[1] = Fr::one(); p.c[2] = Fr::zero(); p.c[3] = Fr::one(); }
+
+// p <- p + q.  q: X, Y, d T and -- unless mixed -- Z of the addend; mixed: Z2 = 1 and q has three elements
+ZK_JFN void jj_add(jpoint &p, const fe *q, bool mixed) {
+    fe m[4];
+    const uint32_t np = mixed ? 3 : 4;
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0; i < np; i++) m[i] = Fr::lmul(p.c[i], q[i]);   // X1 X2, Y1 Y2, d T1 T2, Z1 Z2
+    if (mixed) m[3] = p.c[3];
+    const fe s = Fr::lmul(Fr::ladd(p.c[0], p.c[1]), Fr::ladd(q[0], q[1]));
+    const fe e = Fr::lsub(Fr::lsub(s, m[0]), m[1]);
+    const fe f = Fr::lsub(m[3], m[2]), g = Fr::ladd(m[3], m[2]);
+    const fe h = Fr::lsub(m[1], Fr::lmul(coef_a(), m[0]));
+    fe l[4], r[4];
+    l[0] = e; r[0] = f; l[1] = g; r[1] = h; l[2] = e; r[2] = h; l[3] = f; r[3] = g;
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0; i < 4; i++) p.c[i] = Fr::lmul(l[i], r[i]);
+}
+
+// p <- 2 p; need_t false: T is left as it was (stale) -- for a doubling that is followed by another doubling, which does not read it
+ZK_JFN void jj_dbl(jpoint &p, bool need_t) {
+    fe q[3];
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0; i < 3; i++) { const fe &v = p.c[i == 2 ? 3 : i]; q[i] = Fr::lmul(v, v); }   // X^2, Y^2, Z^2
+    const fe t = Fr::ladd(p.c[0], p.c[1]);
+    const fe e = Fr::lsub(Fr::lsub(Fr::lmul(t, t), q[0]), q[1]);
+    const fe d = Fr::lmul(coef_a(), q[0]);
+    const fe g = Fr::ladd(d, q[1]), f = Fr::lsub(g, Fr::ldbl(q[2])), h = Fr::lsub(d, q[1]);
+    fe l[4], r[4];
+    l[0] = e; r[0] = f; l[1] = g; r[1] = h; l[2] = f; r[2] = g; l[3] = e; r[3] = h;     // X, Y, Z, then T
+    const uint32_t np = need_t ? 4 : 3;
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0; i < np; i++) p.c[i == 2 ? 3 : i == 3 ? 2 : i] = Fr::lmul(l[i], r[i]);
+}
+
+// a^(r - 2): 253 squarings and the products of the set bits, two product bodies in a rolled loop.  0 -> 0 (never asked for: Z != 0 on the curve)
+ZK_JFN fe jj_inv(const fe &a) {
+    fe acc = Fr::one(), base = a;
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0; i < FIELD_BITS; i++) {
+        const uint32_t w = FrParams::p(0) - 2;                  // r - 2 differs from r in its lowest limb only (no borrow)
+        const uint32_t limb = i < 32 ? w : i < 64 ? FrParams::p(1) : i < 96 ? FrParams::p(2) : i < 128 ? FrParams::p(3) : i < 160 ? FrParams::p(4)
+                            : i < 192 ? FrParams::p(5) : i < 224 ? FrParams::p(6) : FrParams::p(7);
+        if ((limb >> (i & 31)) & 1) acc = Fr::lmul(acc, base);
+        base = Fr::lmul(base, base);
+    }
+    return acc;
+}
+
+// affine (x, y) in Montgomery form -> extended with T = x y
+ZK_HD void from_affine(jpoint &p, const fe &x, const fe &y) { p.c[0] = x; p.c[1] = y; p.c[2] = jj_mul(x, y); p.c[3] = Fr::one(); }
+// the canonical integers x = X / Z, y = Y / Z: the identity comes out as (0, 1) whichever representative of zero X holds
+ZK_HD void to_affine_int(const jpoint &p, fe &x, fe &y) {
+    const fe zi = jj_inv(p.c[3]);
+    x = jj_from_mont(jj_mul(p.c[0], zi));
+    y = jj_from_mont(jj_mul(p.c[1], zi));
+}
+// a x^2 + y^2 == 1 + d x^2 y^2 (Montgomery in; compared canonical)
+ZK_HD bool on_curve(const fe &x, const fe &y) {
+    const fe x2 = jj_mul(x, x), y2 = jj_mul(y, y);
+    const fe lhs = Fr::ladd(jj_mul(coef_a(), x2), y2), rhs = Fr::ladd(Fr::one(), jj_mul(coef_d(), jj_mul(x2, y2)));
+    return Fr::eq(Fr::canon(lhs), Fr::canon(rhs));
+}
+// projective p == affine (x, y): cross-multiplied, canonical on both sides (a zero held as r compares equal to 0)
+ZK_HD bool equals_affine(const jpoint &p, const fe &x, const fe &y) {
+    return Fr::eq(Fr::canon(p.c[0]), Fr::canon(jj_mul(x, p.c[3]))) && Fr::eq(Fr::canon(p.c[1]), Fr::canon(jj_mul(y, p.c[3])));
+}
+
+// tab[i] = i (x, y) in addend form, i = 0 .. 15 (tab[0] = the identity: the complete addition needs no "digit is zero" branch)
+ZK_HD void build_table(jpoint *tab, const fe &x, const fe &y) {
+    set_identity(tab[0]);
+    from_affine(tab[1], x, y);
+    fe q[3];
+    q[0] = x; q[1] = y; q[2] = jj_mul(coef_d(), tab[1].c[2]);
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 2; i < TABLE; i++) { tab[i] = tab[i - 1]; jj_add(tab[i], q, true); }
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 1; i < TABLE; i++) tab[i].c[2] = jj_mul(coef_d(), tab[i].c[2]);
+}
+ZK_HD uint32_t digit(const uint32_t *limbs, uint32_t j) { return (limbs[j >> 3] >> ((j & 7) * WIN)) & (TABLE - 1); }
+
+ZK_HD void load_point(const fe *__restrict__ src, size_t g, fe &x, fe &y) { x = jj_to_mont(src[2 * g]); y = jj_to_mont(src[2 * g + 1]); }
+
+// out[g] = k[g] (pts[g]); canonical affine in and out, k = any 256-bit integer.  A point off the curve: *bad += 1 and nothing written
+__global__ void __launch_bounds__(BLOCK)
+k_jj_scalar_mul(const fe *__restrict__ pts, const fe *__restrict__ k, uint32_t n, fe *__restrict__ out, uint32_t *__restrict__ bad) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    fe x, y;
+    load_point(pts, g, x, y);
+    if (!on_curve(x, y)) { atomicAdd(bad, 1u); return; }
+    jpoint tab[TABLE];
+    build_table(tab, x, y);
+    jpoint acc;
+    set_identity(acc);
+    const uint32_t *__restrict__ kw = k[g].l;
+#pragma clang loop unroll(disable)
+    for (int j = N_WIN - 1; j >= 0; j--) {
+#pragma clang loop unroll(disable)
+        for (uint32_t b = 0; b < WIN; b++) jj_dbl(acc, b == WIN - 1);
+        jj_add(acc, tab[digit(kw, j)].c, false);
+    }
+    to_affine_int(acc, out[2 * (size_t)g], out[2 * (size_t)g + 1]);
+}
+
+// out[g] = p[g] + q[g] (the unified addition, not the doubling, whatever the operands), 2 p[g] (the doubling) or -p[g]
+__global__ void __launch_bounds__(BLOCK)
+k_jj_point_op(int op, const fe *__restrict__ p, const fe *__restrict__ q, uint32_t n, fe *__restrict__ out, uint32_t *__restrict__ bad) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    fe x, y;
+    load_point(p, g, x, y);
+    bool ok = on_curve(x, y);
+    jpoint a;
+    from_affine(a, x, y);
+    if (op == OP_ADD) {
+        jpoint b;
+        load_point(q, g, x, y);
+        ok = ok && on_curve(x, y);
+        from_affine(b, x, y);
+        b.c[2] = jj_mul(coef_d(), b.c[2]);
+        if (ok) jj_add(a, b.c, false);
+    } else if (op == OP_DOUBLE) {
+        if (ok) jj_dbl(a, true);
+    } else {
+        a.c[0] = Fr::lneg(a.c[0]);
+    }
+    if (!ok) { atomicAdd(bad, 1u); return; }
+    to_affine_int(a, out[2 * (size_t)g], out[2 * (size_t)g + 1]);
+}
+
+// ---- the windowed Pedersen hash (pedersen_hash_windows).  table[(j 4 + m) 3 ..] = (x, y, d x y) of (m + 1) 16^(j % 62) B_(j / 62), Montgomery,
+// canonical; window w of position j adds entry (w & 3), negated when w > 3
+ZK_HD void pedersen_step(jpoint &acc, const fe *__restrict__ table, uint32_t j, uint32_t w) {
+    const fe *__restrict__ e = table + ((size_t)j * 4 + (w & 3)) * 3;
+    const bool neg = w > 3;
+    fe q[3];
+    q[0] = neg ? Fr::lneg(e[0]) : e[0];
+    q[1] = e[1];
+    q[2] = neg ? Fr::lneg(e[2]) : e[2];
+    jj_add(acc, q, true);
+}
+
+// out[g] = the hash of the windows win[g stride .. g stride + count - 1], count = counts[g] (or stride: counts == nullptr); canonical affine.
+// The host has checked every window (<= 7) and count (1 .. min(stride, capacity)); lanes of a wave may run different counts
+__global__ void __launch_bounds__(BLOCK)
+k_jj_pedersen(const fe *__restrict__ table, const uint8_t *__restrict__ win, const uint32_t *__restrict__ counts, uint32_t stride, uint32_t n, fe *__restrict__ out) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    const uint32_t cnt = counts ? counts[g] : stride;
+    const uint8_t *__restrict__ w = win + (size_t)g * stride;
+    jpoint acc;
+    set_identity(acc);
+#pragma clang loop unroll(disable)
+    for (uint32_t j = 0; j < cnt; j++) pedersen_step(acc, table, j, w[j]);
+    to_affine_int(acc, out[2 * (size_t)g], out[2 * (size_t)g + 1]);
+}
+
+// ---- EdDSA.  The bit stream of PureEdDSA / EdDSA.hash_public: bits(R.x) || bits(A.x) || M, a field element as 254 bits least significant
+// first, message bytes most significant bit first, M of the hash scheme the x of a point (254 bits); past the end: zeros (the padding of
+// the last window).  rx, ax, mx: canonical integers as limbs
+struct BitStream {
+    const uint32_t *rx, *ax, *mx;
+    const uint8_t *msg;
+    uint32_t msg_bits;
+    ZK_HD static uint32_t field_bit(const uint32_t *v, uint32_t i) { return (v[i >> 5] >> (i & 31)) & 1; }
+    ZK_HD uint32_t bit(uint32_t i) const {
+        if (i < FIELD_BITS) return field_bit(rx, i);
+        i -= FIELD_BITS;
+        if (i < FIELD_BITS) return field_bit(ax, i);
+        i -= FIELD_BITS;
+        if (mx) return i < FIELD_BITS ? field_bit(mx, i) : 0;
+        return i < msg_bits ? (msg[i >> 3] >> (7 - (i & 7))) & 1 : 0;
+    }
+    ZK_HD uint32_t window(uint32_t j) const { return bit(3 * j) | (bit(3 * j + 1) << 1) | (bit(3 * j + 2) << 2); }
+};
+
+// what the verify kernel knows of a verifier: btab = i B, i = 0 .. 15, as (x, y, d x y) (entry 0 = the identity (0, 1, 0)); rc = the 91 MiMC
+// constants of seed "EdDSA_Verify.RAM"; ram_tab / m_tab = the Pedersen tables of "EdDSA_Verify.RAM" / "EdDSA_Verify.M"
+struct EddsaView {
+    const fe *btab, *rc, *ram_tab, *m_tab;
+    uint32_t scheme, msg_len, ram_windows, m_windows;
+};
+
+ZK_JFN fe jj_mimc_cipher(const fe *__restrict__ rc, const fe &x, const fe &k) { return merkle::mimc_cipher(rc, x, k); }
+
+// verdicts[g] = (s[g] B == R[g] + t A[g]) with t = H(R, A, M) of the scheme; 0 when A or R is not on the curve.  Straus: the 256 doublings are
+// shared, every window adds one multiple of B (the shared table, mixed addition) and one of -A (the lane's own table)
+__global__ void __launch_bounds__(BLOCK)
+k_eddsa_verify(EddsaView v, const fe *__restrict__ A, const fe *__restrict__ R, const fe *__restrict__ s, const void *__restrict__ msgs, uint32_t n, uint8_t *__restrict__ verdicts) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    fe ax, ay, rx, ry;
+    load_point(A, g, ax, ay);
+    load_point(R, g, rx, ry);
+    if (!on_curve(ax, ay) || !on_curve(rx, ry)) { verdicts[g] = 0; return; }
+    fe t;                                                       // the canonical integer
+    if (v.scheme == SCHEME_MIMC) {
+        const fe *__restrict__ m = (const fe *)msgs + (size_t)g * v.msg_len;
+        fe k = Fr::zero();
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 0; i < 4 + v.msg_len; i++) {
+            const fe xi = i == 0 ? rx : i == 1 ? ry : i == 2 ? ax : i == 3 ? ay : jj_to_mont(m[i - 4]);
+            k = Fr::ladd(Fr::ladd(k, xi), jj_mimc_cipher(v.rc, xi, k));
+        }
+        t = jj_from_mont(k);
+    } else {
+        const uint8_t *__restrict__ m = (const uint8_t *)msgs + (size_t)g * v.msg_len;
+        jpoint acc;
+        fe mx, my;
+        if (v.scheme == SCHEME_HASH) {                          // M = pedersen_hash_bytes("EdDSA_Verify.M", msg)
+            set_identity(acc);
+#pragma clang loop unroll(disable)
+            for (uint32_t j = 0; j < v.m_windows; j++) {
+                uint32_t w = 0;
+                for (uint32_t b = 0; b < 3; b++) { const uint32_t i = 3 * j + b; if (i < 8 * v.msg_len) w |= ((m[i >> 3] >> (7 - (i & 7))) & 1u) << b; }
+                pedersen_step(acc, v.m_tab, j, w);
+            }
+            to_affine_int(acc, mx, my);
+        }
+        BitStream bs;
+        bs.rx = R[2 * (size_t)g].l; bs.ax = A[2 * (size_t)g].l; bs.mx = v.scheme == SCHEME_HASH ? mx.l : nullptr; bs.msg = m; bs.msg_bits = 8 * v.msg_len;
+        set_identity(acc);
+#pragma clang loop unroll(disable)
+        for (uint32_t j = 0; j < v.ram_windows; j++) pedersen_step(acc, v.ram_tab, j, bs.window(j));
+        to_affine_int(acc, t, my);
+    }
+    jpoint tab[TABLE];
+    build_table(tab, Fr::lneg(ax), ay);                        // multiples of -A
+    jpoint acc;
+    set_identity(acc);
+    const uint32_t *__restrict__ sw = s[g].l;
+#pragma clang loop unroll(disable)
+    for (int j = N_WIN - 1; j >= 0; j--) {
+#pragma clang loop unroll(disable)
+        for (uint32_t b = 0; b < WIN; b++) jj_dbl(acc, b == WIN - 1);
+        jj_add(acc, v.btab + 3 * (size_t)digit(sw, j), true);
+        jj_add(acc, tab[digit(t.l, j)].c, false);
+    }
+    verdicts[g] = equals_affine(acc, rx, ry) ? 1 : 0;
+}
+
+}  // namespace jubjub
+}  // namespace zk

@@ -29,41 +29,22 @@
 // The kernels that move leaves and paths serve both hashers.
 #pragma once
 #include "bn254.hpp"
+#include "mimc.hpp"
 #include "poseidon.hpp"
 
 namespace zk {
 namespace merkle {
 
-constexpr uint32_t MIMC_ROUNDS = 91;
 constexpr uint32_t MAX_DEPTH = 29;                              // the gadget's IV table has 29 entries (merkle_tree_IVs)
 constexpr uint32_t MAX_WIDTH = 4;                               // Poseidon nodes: 2, 3 or 4 children (merkletree.py:68 with t = 6)
 constexpr uint32_t LEVEL_BLOCK = 64;
 constexpr uint32_t TAIL_BLOCK = 256;                            // a level with at most this many parents goes through the tail kernel
 
-// E_k(x) + k of the reference's mimc(): 91 rounds x <- (x + k + c_i)^7, then + k.  Loose in, loose out.
-ZK_HD fe mimc_cipher(const fe *__restrict__ rc, const fe &x0, const fe &k) {
-    fe x = x0;
-    for (uint32_t i = 0; i < MIMC_ROUNDS; i++) {
-        const fe t = Fr::ladd(Fr::ladd(x, k), rc[i]);
-        const fe t2 = Fr::lsqr(t);
-        const fe t4 = Fr::lsqr(t2);
-        const fe t6 = Fr::lmul(t4, t2);
-        x = Fr::lmul(t6, t);
-    }
-    return Fr::ladd(x, k);
-}
 // Miyaguchi-Preneel over two blocks: k1 = iv + E_iv(l) + l, k2 = k1 + E_k1(r) + r; canonical result
 ZK_HD fe mimc_hash2(const fe *__restrict__ rc, const fe &l, const fe &r, const fe &iv) {
     const fe k1 = Fr::ladd(Fr::ladd(iv, mimc_cipher(rc, l, iv)), l);
     const fe k2 = Fr::ladd(Fr::ladd(k1, mimc_cipher(rc, r, k1)), r);
     return Fr::canon(k2);
-}
-
-ZK_HD bool fr_lt_modulus(const fe &a) {
-    uint64_t br = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) { const uint64_t t = (uint64_t)a.l[i] - FrParams::p(i) - br; br = (t >> 32) & 1; }
-    return br != 0;
 }
 
 // what every kernel knows of a tree: lvl[d] = the nodes of level d (d = 0 .. depth), ph[d (width - 1) + k] = unique(d, cnt_d + k), n = leaves,

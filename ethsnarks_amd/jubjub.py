@@ -1,0 +1,258 @@
+"""Baby JubJub on the device: the curve, the windowed Pedersen hash and batch EdDSA verification (zk_jj_*, zk_pedersen_*, zk_eddsa_* of
+include/zkhip.h; kernels in csrc/jubjub.hpp).
+
+The native surface of the reference's ethsnarks/jubjub.py, pedersen.py and eddsa.py, in bulk form: a point is a pair (x, y) of ints in [0, r),
+the identity is (0, 1).  All curve arithmetic of a call runs in one HIP kernel launch; there is no CPU path and no signer.  A point that is not on
+the curve raises ZkError (ZK_ERR_ARG) in scalar_mul / point_add / point_double / point_neg and as a base point, and gives the verdict False as
+the A or R of a signature -- the reference never checks and divides by zero there; everything on the curve behaves as the reference does.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import fields as F
+from . import prover as P
+
+JUBJUB_Q = F.FR
+JUBJUB_E = 21888242871839275222246405745257275088614511777268538073601725287587578984328
+JUBJUB_C = 8
+JUBJUB_L = JUBJUB_E // JUBJUB_C
+JUBJUB_A = 168700
+JUBJUB_D = 168696
+SEGMENT_WINDOWS = 62
+IDENTITY = (0, 1)
+SCHEMES = {"mimc": 0, "pure": 1, "hash": 2}                     # ZK_EDDSA_*
+_OPS = {"add": 0, "double": 1, "negate": 2}                     # ZK_JJ_OP_*
+_SYMBOLS = ("zk_jj_hash_to_point", "zk_jj_pedersen_basepoint", "zk_jj_point_op", "zk_jj_scalar_mul", "zk_pedersen_create", "zk_pedersen_free",
+            "zk_pedersen_hash", "zk_pedersen_table", "zk_eddsa_create", "zk_eddsa_free", "zk_eddsa_verify_batch")
+
+
+def generator():
+    """Point.generator() of the reference"""
+    return (16540640123574156134436876038791482806971768689494387082833631921987005038935,
+            20819045374670962167435360035096875258406992893633759881276124905556507972311)
+
+
+def _lib():
+    lib = P.load_library(P._lib_path_loaded)
+    missing = [n for n in _SYMBOLS if not hasattr(lib, n)]
+    if missing:
+        raise ImportError("%s has no Baby JubJub entry points (%s ...): it was built without csrc/jubjub.cpp" % (P._lib_path_loaded or P.LIB_PATH, missing[0]))
+    lib.zk_jj_hash_to_point.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p]
+    lib.zk_jj_pedersen_basepoint.argtypes = [C.c_char_p, C.c_uint32, C.c_void_p]
+    lib.zk_pedersen_create.argtypes = [C.c_char_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+    lib.zk_pedersen_free.argtypes = [C.c_void_p]
+    lib.zk_pedersen_free.restype = None
+    lib.zk_pedersen_hash.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    lib.zk_pedersen_table.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    lib.zk_eddsa_create.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
+    lib.zk_eddsa_free.argtypes = [C.c_void_p]
+    lib.zk_eddsa_free.restype = None
+    lib.zk_eddsa_verify_batch.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p]
+    return lib
+
+
+def _name(name):
+    return name.encode("ascii") if isinstance(name, str) else bytes(name)
+
+
+def _point_limbs(points):
+    """[(x, y), ..] -> (n, 8) limbs; values of 256 bits pass (the library answers a coordinate >= r)"""
+    flat = [int(c) for p in points for c in p]
+    return F.ints_to_limbs(flat).reshape(-1, 8) if flat else np.zeros((0, 8), dtype=np.uint64)
+
+
+def _points(arr):
+    v = F.limbs_to_ints(arr)
+    return [(v[2 * i], v[2 * i + 1]) for i in range(len(v) // 2)]
+
+
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def hash_to_point(data):
+    """Point.from_hash(data)"""
+    out = np.zeros(8, dtype=np.uint64)
+    data = bytes(data)
+    P._check(_lib().zk_jj_hash_to_point(data, len(data), _ptr(out)))
+    return _points(out)[0]
+
+
+def pedersen_basepoint(name, i):
+    """pedersen_hash_basepoint(name, i) as an affine point"""
+    out = np.zeros(8, dtype=np.uint64)
+    P._check(_lib().zk_jj_pedersen_basepoint(_name(name), int(i), _ptr(out)))
+    return _points(out)[0]
+
+
+def _point_op(op, p, q, device):
+    a = _point_limbs(p)
+    b = _point_limbs(q) if q is not None else a
+    if len(a) != len(b):
+        raise ValueError("the point lists differ in length")
+    out = np.zeros_like(a)
+    if len(a):
+        P._check(_lib().zk_jj_point_op(_OPS[op], P._p64(a), P._p64(b), C.c_uint32(len(a)), int(device), P._p64(out)))
+    return _points(out)
+
+
+def point_add(p, q, device=0):
+    """[p_i + q_i] through the unified addition (also where p_i == q_i)"""
+    return _point_op("add", p, q, device)
+
+
+def point_double(p, device=0):
+    """[2 p_i] through the dedicated doubling"""
+    return _point_op("double", p, None, device)
+
+
+def point_neg(p, device=0):
+    return _point_op("negate", p, None, device)
+
+
+def scalar_mul(points, scalars, device=0):
+    """[k_i P_i]; k_i any integer in [0, 2^256)"""
+    a = _point_limbs(points)
+    ks = [int(k) for k in scalars]
+    if len(ks) != len(a):
+        raise ValueError("points and scalars differ in length")
+    if any(not 0 <= k < 1 << 256 for k in ks):
+        raise ValueError("a scalar is not in [0, 2^256)")
+    out = np.zeros_like(a)
+    if ks:
+        k = F.ints_to_limbs(ks)
+        P._check(_lib().zk_jj_scalar_mul(P._p64(a), P._p64(k), C.c_uint32(len(ks)), int(device), P._p64(out)))
+    return _points(out)
+
+
+def bits_to_windows(bits):
+    """pedersen_hash_bits: 3-bit windows, the first bit the least significant; a last window of 1 or 2 bits is zero-padded"""
+    bits = [int(b) for b in bits]
+    return [sum(b << k for k, b in enumerate(bits[i:i + 3])) for i in range(0, len(bits), 3)]
+
+
+def bytes_to_bits(data):
+    """most significant bit first within each byte"""
+    return [(byte >> (7 - k)) & 1 for byte in bytes(data) for k in range(8)]
+
+
+def scalars_to_windows(scalars):
+    """pedersen_hash_scalars: per scalar the windows (s >> i) & 7 for i in range(0, s.bit_length(), 3)"""
+    return [(int(s) >> i) & 7 for s in scalars for i in range(0, int(s).bit_length(), 3)]
+
+
+class PedersenHasher:
+    """pedersen_hash_windows(name, ..) for inputs of up to max_bits bits (ceil(max_bits / 3) windows); the table of base-point multiples lives in
+    device memory for the life of the object"""
+
+    def __init__(self, name, max_bits, device=0):
+        self._lib = _lib()
+        self.name = _name(name)
+        self.max_windows = (int(max_bits) + 2) // 3
+        self._h = C.c_void_p()
+        P._check(self._lib.zk_pedersen_create(self.name, self.max_windows, int(device), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            self._lib.zk_pedersen_free(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def hash_windows(self, rows):
+        """[pedersen_hash_windows(name, row) for row in rows]; the rows may differ in length"""
+        rows = [[int(w) for w in r] for r in rows]
+        if not rows:
+            return []
+        stride = max(1, max(len(r) for r in rows))
+        win = np.zeros((len(rows), stride), dtype=np.uint8)
+        for i, r in enumerate(rows):
+            if any(not 0 <= w < 256 for w in r):
+                raise ValueError("a window is not a byte")
+            win[i, :len(r)] = r
+        counts = np.array([len(r) for r in rows], dtype=np.uint32)
+        out = np.zeros((len(rows), 8), dtype=np.uint64)
+        P._check(self._lib.zk_pedersen_hash(self._h, _ptr(win), _ptr(counts), stride, len(rows), _ptr(out)))
+        return _points(out)
+
+    def hash_bits(self, rows):
+        """[pedersen_hash_bits(name, bits) for bits in rows]; bits: a sequence of 0 / 1 or a str of them"""
+        return self.hash_windows([bits_to_windows(r) for r in rows])
+
+    def hash_bytes(self, rows):
+        """[pedersen_hash_bytes(name, data) for data in rows]"""
+        return self.hash_windows([bits_to_windows(bytes_to_bits(r)) for r in rows])
+
+    def hash_scalars(self, rows):
+        """[pedersen_hash_scalars(name, *row) for row in rows]; a row without windows (all scalars 0) hashes to the identity, as in the reference"""
+        wins = [scalars_to_windows(r) for r in rows]
+        full = [i for i, w in enumerate(wins) if w]
+        got = dict(zip(full, self.hash_windows([wins[i] for i in full])))
+        return [got.get(i, IDENTITY) for i in range(len(wins))]
+
+    def table(self, first_window, n_windows):
+        """the table points [(1 .. 4) 16^(j % 62) B_(j / 62)] of n_windows window positions from first_window on"""
+        out = np.zeros((int(n_windows) * 4, 8), dtype=np.uint64)
+        P._check(self._lib.zk_pedersen_table(self._h, int(first_window), int(n_windows), _ptr(out)))
+        pts = _points(out)
+        return [pts[4 * i:4 * i + 4] for i in range(int(n_windows))]
+
+
+class EdDSAVerifier:
+    """Batch verification of one scheme: "mimc" (MiMCEdDSA; a message is msg_len field elements), "pure" (PureEdDSA; msg_len bytes) or "hash"
+    (EdDSA; msg_len bytes).  B=None: the generator.  verify gives the reference's verdict S B == R + H(R, A, M) A for every item"""
+
+    def __init__(self, scheme, B=None, msg_len=1, device=0):
+        self._lib = _lib()
+        self.scheme = scheme
+        self.msg_len = int(msg_len)
+        self._h = C.c_void_p()
+        b = _point_limbs([B]) if B is not None else None
+        P._check(self._lib.zk_eddsa_create(SCHEMES[scheme], _ptr(b) if b is not None else None, self.msg_len, int(device), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            self._lib.zk_eddsa_free(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def verify(self, A, sigs, msgs):
+        """A: one public key per signature (or a single point for all); sigs: [(R, s), ..]; msgs: bytes objects (lists of ints for "mimc")"""
+        sigs = list(sigs)
+        n = len(sigs)
+        if n == 0:
+            return []
+        A = list(A)
+        if len(A) == 2 and not isinstance(A[0], (tuple, list)):
+            A = [tuple(A)] * n
+        msgs = list(msgs)
+        if len(A) != n or len(msgs) != n:
+            raise ValueError("A, sigs and msgs differ in length")
+        a = _point_limbs(A)
+        r = _point_limbs([R for R, _ in sigs])
+        s = F.ints_to_limbs([int(v) for _, v in sigs])
+        if self.scheme == "mimc":
+            if any(len(m) != self.msg_len for m in msgs):
+                raise ValueError("a message does not have msg_len elements")
+            m = F.ints_to_limbs([int(v) for msg in msgs for v in msg])
+        else:
+            if any(len(bytes(m)) != self.msg_len for m in msgs):
+                raise ValueError("a message does not have msg_len bytes")
+            m = np.frombuffer(b"".join(bytes(x) for x in msgs), dtype=np.uint8).copy()
+        out = np.full(n, 255, dtype=np.uint8)
+        P._check(self._lib.zk_eddsa_verify_batch(self._h, _ptr(a), _ptr(r), _ptr(s), _ptr(m), n, _ptr(out)))
+        return [bool(v) for v in out]

@@ -60,9 +60,10 @@ extern "C" {
 /* ABI version of this header: bumped whenever a struct below changes layout or a function changes signature.
  * 3: zk_config = {multi_exp_c, device, shard_rank, shard_count, max_batch, schedule} (24 bytes; rounds 1-2 had 16 / 24).
  * 4: the Poseidon entry points (zk_poseidon_*, zk_mtree_create_ex, zk_mtree_info); zk_mtree_paths returns width - 1 siblings per level.
+ * 5: Baby JubJub (zk_jj_*, zk_pedersen_*, zk_eddsa_*).
  * A client checks zk_abi_version() == ZK_ABI_VERSION once after loading the library, or passes the size of the zk_config
  * it was compiled with to zk_ctx_create_sized (members it does not know read as 0 = their defaults). */
-#define ZK_ABI_VERSION 4
+#define ZK_ABI_VERSION 5
 
 typedef struct zk_pk zk_pk;
 typedef struct zk_vk zk_vk;
@@ -402,6 +403,54 @@ int zk_mimc_hash2(const uint64_t *left, const uint64_t *right, const uint64_t *i
 int zk_poseidon_constants(uint64_t *C_canon /* 65 x 4 */, uint64_t *M_canon /* 36 x 4, row major */);
 int zk_poseidon_hash(const uint64_t *inputs /* n x n_in x 4 */, uint32_t n_in, uint32_t n, int device, uint64_t *out /* n x 4 */);
 int zk_poseidon_permute(uint64_t *states /* n x 6 x 4, in place */, uint32_t n, int device);
+
+/* ---- Baby JubJub (csrc/jubjub.hpp, jubjub.cpp): the native side of ethsnarks/jubjub.py, pedersen.py and eddsa.py.  The curve is
+ * a x^2 + y^2 = 1 + d x^2 y^2 over Fr, a = 168700, d = 168696, order 8 L.  Every field value is canonical (4 x u64 limbs, below r), a point is x
+ * then y (8 limbs); the identity is (0, 1).  Device calls take n items and run ONE kernel launch each, whatever n is.
+ * Codes: ZK_ERR_ARG -- and NOTHING is written -- for a null argument, a coordinate, s or MiMC message element >= r, a window > 7 (among the count
+ * windows of its row), a window count of 0, above the stride or above the hasher's capacity, a name longer than 28 bytes, a base point index
+ * above 0xFFFF, an unknown operation or scheme, msg_len outside 1 .. 4096, max_windows outside 1 .. 15872.
+ * OFF-CURVE POINTS, the one deliberate difference from the reference (which never checks, and whose affine formulas then divide by zero or return
+ * garbage): zk_jj_point_op, zk_jj_scalar_mul and the B of zk_eddsa_create answer ZK_ERR_ARG (and write nothing); zk_eddsa_verify_batch gives
+ * verdict 0 to a signature whose A or R is not on the curve.  Everything ON the curve behaves as the reference: the addition is complete, so the
+ * identity, P + P, P + (-P) and the eight low-order points need no special case; s is not required to be below L (s + L verifies when s does);
+ * low-order A and R are accepted and evaluated.
+ *   zk_jj_hash_to_point        host-only: Point.from_hash -- y = sha256(data) mod r, incremented until x exists; x the root with x > r - x; times 8
+ *   zk_jj_pedersen_basepoint   host-only: from_hash("%-28s%04X" % (name, i)); name is NUL-terminated, at most 28 bytes
+ *   zk_jj_point_op             out[i] = p[i] + q[i] (ZK_JJ_OP_ADD: the unified addition, also when p[i] == q[i]), 2 p[i] (ZK_JJ_OP_DOUBLE: the
+ *                              dedicated doubling) or -p[i] (ZK_JJ_OP_NEGATE); q is read by ZK_JJ_OP_ADD only
+ *   zk_jj_scalar_mul           out[i] = scalars[i] points[i]; a scalar is ANY 256-bit integer (4 limbs; 0, >= L, >= 8 L, 2^256 - 1 are all defined)
+ *   zk_pedersen_create         the hasher of pedersen_hash_windows(name, ..) for up to max_windows windows: the multiples (1 .. 4) 16^j B_s of every
+ *                              window position go to device memory once
+ *   zk_pedersen_hash           n hashes; row i of windows (stride bytes apart, each 0 .. 7) holds counts[i] windows (counts == NULL: stride each).
+ *                              Window w adds ((w & 3) + 1) 16^(j % 62) B_(j / 62), negated when w > 3; a padding window is NOT neutral
+ *   zk_pedersen_table          host-only: the 4 table points of each of n_windows window positions from first_window on (n_windows x 4 x 8 limbs)
+ *   zk_eddsa_create            a verifier for one scheme: ZK_EDDSA_MIMC (MiMCEdDSA: t = mimc_hash([R.x, R.y, A.x, A.y, m..], 0) with the constants of
+ *                              seed "EdDSA_Verify.RAM"; msg_len = field elements per message), ZK_EDDSA_PURE (PureEdDSA: t = the x of
+ *                              pedersen_hash_bits("EdDSA_Verify.RAM", bits(R.x) || bits(A.x) || M); msg_len = bytes per message) or ZK_EDDSA_HASH
+ *                              (EdDSA: as pure with M = the x of pedersen_hash_bytes("EdDSA_Verify.M", msg)).  B == NULL: the generator
+ *   zk_eddsa_verify_batch      verdicts[i] = (s[i] B == R[i] + t A[i]); A, R: n x 8, s: n x 4, msgs: n x msg_len bytes (n x msg_len x 4 limbs for
+ *                              ZK_EDDSA_MIMC).  t is computed on the device
+ * A zk_pedersen and a zk_eddsa are single-threaded like a zk_ctx; their work runs on a stream of their own and is complete when a call returns. */
+#define ZK_JJ_OP_ADD 0
+#define ZK_JJ_OP_DOUBLE 1
+#define ZK_JJ_OP_NEGATE 2
+#define ZK_EDDSA_MIMC 0
+#define ZK_EDDSA_PURE 1
+#define ZK_EDDSA_HASH 2
+typedef struct zk_pedersen zk_pedersen;
+typedef struct zk_eddsa zk_eddsa;
+int zk_jj_hash_to_point(const uint8_t *data, size_t len, uint64_t out[8]);
+int zk_jj_pedersen_basepoint(const char *name, uint32_t i, uint64_t out[8]);
+int zk_jj_point_op(int op, const uint64_t *p /* n x 8 */, const uint64_t *q /* n x 8 */, uint32_t n, int device, uint64_t *out /* n x 8 */);
+int zk_jj_scalar_mul(const uint64_t *points /* n x 8 */, const uint64_t *scalars /* n x 4 */, uint32_t n, int device, uint64_t *out /* n x 8 */);
+int zk_pedersen_create(const char *name, uint32_t max_windows, int device, zk_pedersen **out);
+void zk_pedersen_free(zk_pedersen *h);
+int zk_pedersen_hash(zk_pedersen *h, const uint8_t *windows /* n x stride */, const uint32_t *counts /* n, or NULL */, uint32_t stride, uint32_t n, uint64_t *out /* n x 8 */);
+int zk_pedersen_table(const zk_pedersen *h, uint32_t first_window, uint32_t n_windows, uint64_t *out /* n_windows x 4 x 8 */);
+int zk_eddsa_create(int scheme, const uint64_t *B /* 8 limbs, or NULL */, uint32_t msg_len, int device, zk_eddsa **out);
+void zk_eddsa_free(zk_eddsa *v);
+int zk_eddsa_verify_batch(zk_eddsa *v, const uint64_t *A, const uint64_t *R, const uint64_t *s, const void *msgs, uint32_t n, uint8_t *verdicts /* n */);
 
 /* ---- measurement aids (bench.py): kernel launches issued by this library so far; between zk_profile_begin() and
  * zk_profile_end() every launch is bracketed by a HIP event pair on its own stream -- the sum of the kernel durations
