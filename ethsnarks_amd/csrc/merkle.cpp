@@ -403,6 +403,18 @@ extern "C" int zk_mtree_paths(const zk_mtree *ct, const uint64_t *indices, uint3
     return ZK_OK;
 } ZK_GUARD
 
+namespace {
+// the checks of a membership layout that both fill calls make, before any device work
+int mt_check_layout(const zk_mtree *t, uint64_t row_elems, const zk_mtree_layout *layout) {
+    const uint64_t D = t->depth;
+    if (t->is_poseidon() && layout->n_iv != 0) return mfail(ZK_ERR_ARG, "the Poseidon membership circuit has no IV variables: layout.n_iv must be 0");
+    if (layout->n_iv > MAX_DEPTH || row_elems == 0 || layout->root_var >= row_elems || layout->leaf_var >= row_elems || layout->addr_var0 + D > row_elems ||
+        layout->path_var0 + D > row_elems || (uint64_t)layout->iv_var0 + layout->n_iv > row_elems)
+        return mfail(ZK_ERR_ARG, "the layout names a variable outside the witness row");
+    return ZK_OK;
+}
+}  // namespace
+
 extern "C" int zk_mtree_fill_witnesses(const zk_mtree *ct, const uint64_t *indices, uint32_t k, void *d_w, uint64_t row_elems, const zk_mtree_layout *layout) try {
     zk_mtree *t = const_cast<zk_mtree *>(ct);
     if (!t || (k && !indices) || !d_w || !layout) return mfail(ZK_ERR_ARG, "null argument");
@@ -410,14 +422,41 @@ extern "C" int zk_mtree_fill_witnesses(const zk_mtree *ct, const uint64_t *indic
     if (k == 0) return ZK_OK;
     if (t->n == 0) return mfail(ZK_ERR_ARG, "the tree is empty: it has no root");
     const uint64_t D = t->depth;
-    if (t->is_poseidon() && layout->n_iv != 0) return mfail(ZK_ERR_ARG, "the Poseidon membership circuit has no IV variables: layout.n_iv must be 0");
-    if (layout->n_iv > MAX_DEPTH || row_elems == 0 || layout->root_var >= row_elems || layout->leaf_var >= row_elems || layout->addr_var0 + D > row_elems ||
-        layout->path_var0 + D > row_elems || (uint64_t)layout->iv_var0 + layout->n_iv > row_elems)
-        return mfail(ZK_ERR_ARG, "the layout names a variable outside the witness row");
+    ZK_TRY(mt_check_layout(t, row_elems, layout));
     ZK_TRY(mt_upload_indices(t, indices, k, 0));
     Layout L;
     memcpy(&L, layout, sizeof(L));
     ZK_LAUNCH(k_mtree_fill_witness, zk_div_up((uint64_t)k * (3 + 2 * D + L.n_iv), LEVEL_BLOCK), LEVEL_BLOCK, t->st, t->view(), (const uint64_t *)t->d_scratch, k, (fe *)d_w, row_elems, L);
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipStreamSynchronize(t->st));
+    return ZK_OK;
+} ZK_GUARD
+
+extern "C" int zk_mtree_fill_full_witnesses(const zk_mtree *ct, const uint64_t *indices, uint32_t k, void *d_w, uint64_t row_elems, const zk_mtree_layout *layout,
+                                            uint32_t level_var0, uint32_t level_stride) try {
+    zk_mtree *t = const_cast<zk_mtree *>(ct);
+    if (!t || (k && !indices) || !d_w || !layout) return mfail(ZK_ERR_ARG, "null argument");
+    if (t->width != 2) return mfail(ZK_ERR_ARG, "the membership circuit exists for node width 2 only (there is no wide path selector)");
+    if (k == 0) return ZK_OK;
+    if (t->n == 0) return mfail(ZK_ERR_ARG, "the tree is empty: it has no root");
+    const uint64_t D = t->depth;
+    ZK_TRY(mt_check_layout(t, row_elems, layout));
+    if (!t->is_poseidon() && layout->n_iv < D) return mfail(ZK_ERR_ARG, "a complete MiMC witness reads the level IVs: layout.n_iv must be at least the depth");
+    if (level_stride < (t->is_poseidon() ? POSEIDON_LEVEL_VARS : MIMC_LEVEL_VARS))
+        return mfail(ZK_ERR_ARG, "level_stride is below the variables of one level: 322 (Poseidon) or 736 (MiMC)");
+    const uint64_t lv0 = level_var0, lv1 = lv0 + D * level_stride;                         // the level blocks: [lv0, lv1)
+    if (lv1 > row_elems) return mfail(ZK_ERR_ARG, "the level blocks leave the witness row: level_var0 + depth * level_stride > row_elems");
+    const auto hits = [&](uint64_t v0, uint64_t n) { return n && v0 < lv1 && v0 + n > lv0; };
+    if (hits(0, 1) || hits(layout->root_var, 1) || hits(layout->leaf_var, 1) || hits(layout->addr_var0, D) || hits(layout->path_var0, D) || hits(layout->iv_var0, layout->n_iv))
+        return mfail(ZK_ERR_ARG, "the level blocks overlap an input variable of the layout");
+    ZK_TRY(mt_upload_indices(t, indices, k, 0));
+    Layout L;
+    memcpy(&L, layout, sizeof(L));
+    const TreeView v = t->view();
+    const uint64_t *d_idx = (const uint64_t *)t->d_scratch;
+    ZK_LAUNCH(k_mtree_fill_witness, zk_div_up((uint64_t)k * (3 + 2 * D + L.n_iv), LEVEL_BLOCK), LEVEL_BLOCK, t->st, v, d_idx, k, (fe *)d_w, row_elems, L);
+    if (t->is_poseidon()) ZK_LAUNCH(k_mtree_fill_levels<true>, zk_div_up((uint64_t)k * D, LEVEL_BLOCK), LEVEL_BLOCK, t->st, v, d_idx, k, (fe *)d_w, row_elems, level_var0, level_stride);
+    else ZK_LAUNCH(k_mtree_fill_levels<false>, zk_div_up((uint64_t)k * D, LEVEL_BLOCK), LEVEL_BLOCK, t->st, v, d_idx, k, (fe *)d_w, row_elems, level_var0, level_stride);
     ZK_HIP(hipGetLastError());
     ZK_HIP(hipStreamSynchronize(t->st));
     return ZK_OK;

@@ -19,6 +19,7 @@
 //   k_mtree_set_leaves    scatter updated leaves
 //   k_mtree_gather        leaves and authentication paths of k indices (canonical, for the host)
 //   k_mtree_fill_witness  the membership circuit's inputs of k indices, straight into k rows of a device witness buffer
+//   k_mtree_fill_levels   the rest of that row: one lane per (row, level) writes the level's selector and hash variables (both hashers)
 //   k_mimc_hash2          n independent two-block hashes (test entry point)
 //
 // The same tree over the Poseidon hasher (MerkleHasher_Poseidon, merkletree.py:63-78; the permutation is poseidon.hpp) has node widths
@@ -206,6 +207,69 @@ k_mtree_fill_witness(TreeView t, const uint64_t *__restrict__ idx, uint32_t k, f
     s -= D;
     if (s == 0) { row[L.leaf_var] = t.lvl[0][a]; return; }
     row[L.iv_var0 + (s - 1)] = t.iv[s - 1];
+}
+
+// ---- complete membership witnesses.  Every node of a path is in the tree already, so the D levels of one witness do not wait for each other:
+// one lane per (row, level) reads its own node x = lvl[d][a >> d] and the sibling p, and writes the level's variables in the gadgets'
+// allocation order at row[level_var0 + d level_stride ..]: the six of merkle_path_selector, then the intermediates of ONE ordinary hash.
+// Every stored value is canonical.  A lane streams its 322 or 736 elements as 32-byte stores to consecutive addresses (whole sectors; the
+// lines fill up in L2); its depth is one hash, whatever the size of the circuit.
+constexpr uint32_t SELECTOR_VARS = 6;
+constexpr uint32_t POSEIDON_LEVEL_VARS = SELECTOR_VARS + 3 * poseidon::N_SBOX + 1;            // 322: selector, S-boxes, output
+constexpr uint32_t MIMC_LEVEL_VARS = SELECTOR_VARS + 2 + 2 * 4 * MIMC_ROUNDS;                  // 736: selector, outputs[0..1], 2 x 91 x (a, b, c, d)
+
+// left_a, left_b, left, right_a, right_b, right (MerklePathSelector) for a bit that is 0 or 1: products by the bit are selections
+ZK_HD fe select(bool c, const fe &a, const fe &b) {              // limb by limb: a choice between two structs would go through memory
+    fe r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) r.l[i] = c ? a.l[i] : b.l[i];
+    return r;
+}
+ZK_HD void store_selector(fe *__restrict__ o, bool bit, const fe &x, const fe &p, fe &left, fe &right) {
+    const fe z = Fr::zero();
+    left = select(bit, p, x); right = select(bit, x, p);
+    o[0] = select(bit, z, x); o[1] = select(bit, p, z); o[2] = left;
+    o[3] = select(bit, x, z); o[4] = select(bit, z, p); o[5] = right;
+}
+
+// MiMC_e7_gadget over message x0 with key k: (a, b, c, d) of every round at o[4 i ..], canonical; returns the loose result (the last d)
+ZK_HD fe mimc_cipher_traced(const fe *__restrict__ rc, const fe &x0, const fe &k, fe *__restrict__ o) {
+    fe x = x0;
+    for (uint32_t i = 0; i < MIMC_ROUNDS; i++) {
+        const fe t = Fr::ladd(Fr::ladd(x, k), rc[i]);
+        const fe a = Fr::lsqr(t);
+        const fe b = Fr::lsqr(a);
+        const fe c = Fr::lmul(a, b);
+        x = Fr::lmul(c, t);
+        if (i + 1 == MIMC_ROUNDS) x = Fr::ladd(x, k);
+        o[4 * i] = Fr::canon(a); o[4 * i + 1] = Fr::canon(b); o[4 * i + 2] = Fr::canon(c); o[4 * i + 3] = Fr::canon(x);
+    }
+    return x;
+}
+
+template <bool POSEIDON>
+__global__ void __launch_bounds__(LEVEL_BLOCK)
+k_mtree_fill_levels(TreeView t, const uint64_t *__restrict__ idx, uint32_t k, fe *__restrict__ w, uint64_t row_elems, uint32_t level_var0, uint32_t level_stride) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t D = t.depth;
+    if (g >= (uint64_t)k * D) return;
+    const uint32_t i = (uint32_t)(g / D), d = (uint32_t)(g % D);
+    const uint64_t ad = idx[i] >> d;                             // the own node on level d
+    fe *__restrict__ o = w + (size_t)i * row_elems + level_var0 + (size_t)d * level_stride;
+    fe left, right;
+    store_selector(o, ad & 1, t.lvl[d][ad], node_or_placeholder(t, d, ad ^ 1), left, right);
+    o += SELECTOR_VARS;
+    if constexpr (POSEIDON) {
+        fe x[poseidon::T] = {left, right, Fr::zero(), Fr::zero(), Fr::zero(), Fr::zero()};
+        poseidon::permute_traced<poseidon::POSEIDON_MIX_DOT6>(t.pc, x, o);
+        o[3 * poseidon::N_SBOX] = Fr::canon(x[0]);
+    } else {
+        const fe iv = t.iv[d];
+        const fe k1 = Fr::ladd(Fr::ladd(iv, mimc_cipher_traced(t.rc, left, iv, o + 2)), left);
+        o[0] = Fr::canon(k1);
+        const fe k2 = Fr::ladd(Fr::ladd(k1, mimc_cipher_traced(t.rc, right, k1, o + 2 + 4 * MIMC_ROUNDS)), right);
+        o[1] = Fr::canon(k2);
+    }
 }
 
 // out[i] = mimc_hash([l[i], r[i]], iv[i]); canonical in and out (the host has checked the operands against r)

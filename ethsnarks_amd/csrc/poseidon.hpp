@@ -74,6 +74,44 @@ ZK_HD void permute(const fe *__restrict__ pc, fe (&x)[T]) {
     }
 }
 
+constexpr uint32_t N_SBOX = ROUNDS_F * T + ROUNDS_P;             // 105 S-boxes, three variables each (FifthPower_gadget: x2, x4, x5)
+
+// permute() with the intermediates of every S-box stored, canonical, in the order the S-boxes run: out[3 s .. 3 s + 2] = x^2, x^4, x^5 of
+// S-box s, x the state element after ARK -- the variables Poseidon128's gadget allocates, in its allocation order (merkle.hpp writes a
+// membership witness with it).  The same rolled loops; the squarings of pow5 are the stored x^2 and x^4.  Loose in, loose out
+template <bool DOT6>
+ZK_HD void permute_traced(const fe *__restrict__ pc, fe (&x)[T], fe *__restrict__ out) {
+    const fe *__restrict__ M = pc + ROUNDS;
+#pragma clang loop unroll(disable)
+    for (uint32_t r = 0; r < ROUNDS; r++) {
+        const fe c = pc[r];
+#pragma unroll
+        for (uint32_t j = 0; j < T; j++) x[j] = Fr::ladd(x[j], c);
+        const bool full = r < ROUNDS_F / 2 || r >= ROUNDS_F / 2 + ROUNDS_P;
+#pragma clang loop unroll(disable)
+        for (uint32_t j = 0; j < T; j++) {
+            if (j == 0 || full) {
+                const fe x2 = Fr::lsqr(x[0]), x4 = Fr::lsqr(x2);
+                x[0] = Fr::lmul(x4, x[0]);
+                out[0] = Fr::canon(x2); out[1] = Fr::canon(x4); out[2] = Fr::canon(x[0]);
+                out += 3;
+            }
+            turn(x);
+        }
+        fe y[T];
+#pragma unroll
+        for (uint32_t j = 0; j < T; j++) y[j] = Fr::zero();
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 0; i < T; i++) {
+            const fe o = DOT6 ? Fr::ldot6(x, M + T * i) : mix_row_lmul(x, M + T * i);
+            turn(y);
+            y[T - 1] = o;
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < T; j++) x[j] = y[j];
+    }
+}
+
 // out[g] = poseidon(in[g n_in .. g n_in + n_in - 1]); canonical in and out (the host has checked the operands against r and 1 <= n_in <= 5)
 template <bool DOT6>
 __global__ void __launch_bounds__(BLOCK)

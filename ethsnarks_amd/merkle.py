@@ -3,7 +3,9 @@
 The surface of the reference's ethsnarks/merkletree.py (MerkleTree over MerkleHasher_MiMC, width 2): append, update, proof, root,
 leaf(depth, offset) -- plus the bulk forms a GPU needs: extend, update_many, proofs, and fill_witnesses, which writes the inputs of the
 membership circuit (gadgets.merkle_membership_circuit) for k leaves straight into a device witness buffer, ready for
-prover.WitnessPlan.solve and ProverContext.submit_batch(device_ptr=...).  All hashing runs in HIP kernels; there is no CPU path.
+prover.WitnessPlan.solve and ProverContext.submit_batch(device_ptr=...).  fill_full_witnesses writes the COMPLETE witness instead -- every node
+of a path is in the tree, so one lane per (row, level) computes the level's selector and hash variables and nothing is left for the planner:
+tree -> fill_full_witnesses -> submit_batch(device_ptr=...).  All hashing runs in HIP kernels; there is no CPU path.
 
 MerkleTree(n, hasher="poseidon", width=w) is the reference's MerkleTree over MerkleHasher_Poseidon (csrc/poseidon.hpp): n = w^depth leaf slots,
 proofs with w - 1 siblings per level; poseidon_hash / poseidon_permute / poseidon_constants expose the permutation itself.
@@ -20,7 +22,8 @@ from . import prover as P
 MAX_DEPTH = 29
 _SYMBOLS = ("zk_mtree_create", "zk_mtree_free", "zk_mtree_size", "zk_mtree_append", "zk_mtree_append_resident", "zk_mtree_update",
             "zk_mtree_root", "zk_mtree_node", "zk_mtree_paths", "zk_mtree_fill_witnesses", "zk_mimc_constants", "zk_mimc_hash2",
-            "zk_mtree_create_ex", "zk_mtree_info", "zk_poseidon_constants", "zk_poseidon_hash", "zk_poseidon_permute")
+            "zk_mtree_create_ex", "zk_mtree_info", "zk_poseidon_constants", "zk_poseidon_hash", "zk_poseidon_permute",
+            "zk_mtree_fill_full_witnesses")
 HASHERS = {"mimc": 0, "poseidon": 1}                          # ZK_MTREE_HASH_*
 
 
@@ -35,6 +38,18 @@ def membership_layout(depth, hasher="mimc"):
     if hasher == "poseidon":
         return Layout(1, 2, 2 + depth, 2 + 2 * depth, 0, 0)
     return Layout(1, 2, 2 + depth, 2 + 2 * depth, 3 + 2 * depth, 29)
+
+
+LEVEL_VARS = {"mimc": 736, "poseidon": 322}                  # selector + hash variables of one level (csrc/merkle.hpp)
+
+
+def membership_full_layout(depth, hasher="mimc"):
+    """(Layout, level_var0, level_stride, row_elems) of the complete witness of merkle_membership_circuit / poseidon_membership_circuit: the
+    inputs of membership_layout, then per level the six selector variables and the hash gadget's variables, in allocation order"""
+    layout = membership_layout(depth, hasher)
+    level_var0 = 3 + 2 * depth + layout.n_iv
+    stride = LEVEL_VARS[hasher]
+    return layout, level_var0, stride, level_var0 + stride * depth
 
 
 def _lib():
@@ -252,6 +267,31 @@ class MerkleTree:
             raise ValueError("the device buffer is smaller than k rows")
         if len(idx):
             P._check(P._lib.zk_mtree_fill_witnesses(self._h, P._p64(idx), C.c_uint32(len(idx)), C.c_void_p(ptr), C.c_uint64(row_elems), C.byref(layout)))
+
+    def fill_full_witnesses(self, indices, device_buffer, r1cs_or_layout=None, row_elems=None, level_var0=None, level_stride=None):
+        """rows 0 .. k - 1 of a device witness buffer get the COMPLETE witness of the membership circuit of the given leaves (Montgomery,
+        canonical): what fill_witnesses writes, and every level's selector and hash variables, computed from the nodes of the tree -- byte for
+        byte what WitnessPlan.solve would leave, ready for submit_batch(device_ptr=...).  Arguments as fill_witnesses; level_var0 and
+        level_stride place the level blocks (default: the allocation order, membership_full_layout)."""
+        _, var0, stride, _ = membership_full_layout(self.depth, self.hasher)
+        if isinstance(r1cs_or_layout, Layout):
+            layout = r1cs_or_layout
+            if row_elems is None:
+                raise ValueError("a Layout needs row_elems")
+        else:
+            layout = membership_layout(self.depth, self.hasher)
+            if row_elems is None:
+                if r1cs_or_layout is None:
+                    raise ValueError("give the constraint system, or a Layout and row_elems")
+                row_elems = r1cs_or_layout.V + 1
+        level_var0 = var0 if level_var0 is None else int(level_var0)
+        level_stride = stride if level_stride is None else int(level_stride)
+        idx = np.ascontiguousarray([int(i) for i in indices], dtype=np.uint64)
+        ptr = device_buffer.ptr if isinstance(device_buffer, P.DeviceBuffer) else int(device_buffer)
+        if isinstance(device_buffer, P.DeviceBuffer) and len(idx) * int(row_elems) * 32 > device_buffer.nbytes:
+            raise ValueError("the device buffer is smaller than k rows")
+        P._check(_lib().zk_mtree_fill_full_witnesses(self._h, P._p64(idx), C.c_uint32(len(idx)), C.c_void_p(ptr), C.c_uint64(row_elems), C.byref(layout),
+                                                     C.c_uint32(level_var0), C.c_uint32(level_stride)))
 
     def close(self):
         if getattr(self, "_h", None) is not None and P._lib is not None:

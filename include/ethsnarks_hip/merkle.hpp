@@ -9,6 +9,8 @@
 //   tree.proof(i) / tree.proofs(indices);              leaf, address bits, path (level 0 first)
 //   tree.fill_witnesses(indices, d_w, row_elems);      inputs of merkle_path_authenticator for k leaves into a device witness buffer, for
 //                                                      zk_wplan_solve and zk_prove_batch_submit_resident
+//   tree.fill_full_witnesses(indices, d_w, row_elems); the COMPLETE witness of the membership circuit instead (selector and hash variables of
+//                                                      every level, computed from the tree's nodes): nothing is left for zk_wplan_solve
 //   ethsnarks::MerkleTreeHIP wide(14, 4, MerkleHasher::Poseidon);   the same tree over Poseidon128, node width 2, 3 or 4 (capacity width^depth
 //                                                      <= 2^29); a proof then carries `digits` and width - 1 siblings per level in `path`
 // Every failure is a mtree_error carrying the C ABI's code and zk_last_error()'s text.
@@ -103,6 +105,17 @@ public:
     void fill_witnesses(const std::vector<uint64_t> &indices, void *d_w, uint64_t row_elems) const { fill_witnesses(indices, d_w, row_elems, membership_layout()); }
     void fill_witnesses(const std::vector<uint64_t> &indices, void *d_w, uint64_t row_elems, const zk_mtree_layout &layout) const {
         if (!indices.empty()) check(zk_mtree_fill_witnesses(h_, indices.data(), (uint32_t)indices.size(), d_w, row_elems, &layout));
+    }
+
+    // the complete witness: per level the six selector variables and the hash gadget's, 736 (MiMC) or 322 (Poseidon), after the inputs
+    uint32_t level_stride() const { return hasher_ == MerkleHasher::Poseidon ? 322 : 736; }
+    uint32_t level_var0() const { return 3 + 2 * depth_ + membership_layout().n_iv; }
+    uint64_t full_row_elems() const { return (uint64_t)level_var0() + (uint64_t)level_stride() * depth_; }
+    void fill_full_witnesses(const std::vector<uint64_t> &indices, void *d_w, uint64_t row_elems) const {
+        fill_full_witnesses(indices, d_w, row_elems, membership_layout(), level_var0(), level_stride());
+    }
+    void fill_full_witnesses(const std::vector<uint64_t> &indices, void *d_w, uint64_t row_elems, const zk_mtree_layout &layout, uint32_t var0, uint32_t stride) const {
+        if (!indices.empty()) check(zk_mtree_fill_full_witnesses(h_, indices.data(), (uint32_t)indices.size(), d_w, row_elems, &layout, var0, stride));
     }
 };
 

@@ -61,9 +61,10 @@ extern "C" {
  * 3: zk_config = {multi_exp_c, device, shard_rank, shard_count, max_batch, schedule} (24 bytes; rounds 1-2 had 16 / 24).
  * 4: the Poseidon entry points (zk_poseidon_*, zk_mtree_create_ex, zk_mtree_info); zk_mtree_paths returns width - 1 siblings per level.
  * 5: Baby JubJub (zk_jj_*, zk_pedersen_*, zk_eddsa_*).
+ * 6: zk_mtree_fill_full_witnesses.
  * A client checks zk_abi_version() == ZK_ABI_VERSION once after loading the library, or passes the size of the zk_config
  * it was compiled with to zk_ctx_create_sized (members it does not know read as 0 = their defaults). */
-#define ZK_ABI_VERSION 5
+#define ZK_ABI_VERSION 6
 
 typedef struct zk_pk zk_pk;
 typedef struct zk_vk zk_vk;
@@ -360,6 +361,17 @@ int zk_dev_download(void *dst, const void *src, size_t bytes);
  *                              variable indices of the layout -- and nothing else of the row.  What zk_wplan_solve completes and
  *                              zk_prove_batch_submit_resident proves.  merkle_path_authenticator's allocation order (root, address bits,
  *                              path, leaf, IVs) is the layout {1, 2, 2 + D, 2 + 2 D, 3 + 2 D, 29}
+ *   zk_mtree_fill_full_witnesses   the COMPLETE witness of the membership circuit for each of k indices: what zk_mtree_fill_witnesses writes, and
+ *                              for every level d the level's variables in the gadgets' allocation order at level_var0 + d level_stride: the six of
+ *                              merkle_path_selector (left_a, left_b, left, right_a, right_b, right), then
+ *                                MiMC      outputs[0], outputs[1], 91 x (a, b, c, d) of cipher 0, 91 x (a, b, c, d) of cipher 1: 736 variables
+ *                                Poseidon  105 x (x2, x4, x5) of the S-boxes in round order, the output: 322 variables
+ *                              One lane per (row, level) computes them from the nodes the tree holds, so nothing is left for zk_wplan_solve:
+ *                              variables 0 .. level_var0 + D level_stride - 1 of the allocation order (MiMC: level_var0 = 3 + 2 D + 29, Poseidon:
+ *                              3 + 2 D) are all written, canonical Montgomery, byte-identical to what zk_wplan_solve leaves; nothing else of the
+ *                              buffer is.  ZK_ERR_ARG, before any device work: node width 3 or 4, an empty tree, an index >= the size,
+ *                              level_stride below 736 / 322, level blocks that leave the row or overlap an input variable of the layout,
+ *                              n_iv != 0 (Poseidon) or n_iv < D (MiMC: the IVs are read).  k = 0 does nothing
  *   zk_mimc_constants          host-only: the 91 round constants and 29 level IVs the kernels use, canonical (either may be NULL)
  *   zk_mimc_hash2              out[i] = mimc_hash([left[i], right[i]], iv[i]) on the device, canonical in and out; an operand >= r is ZK_ERR_ARG
  *
@@ -398,6 +410,8 @@ int zk_mtree_root(const zk_mtree *t, uint64_t root_canon[4]);
 int zk_mtree_node(const zk_mtree *t, uint32_t level, uint64_t offset, uint64_t out_canon[4]);
 int zk_mtree_paths(const zk_mtree *t, const uint64_t *indices, uint32_t k, uint64_t *leaves_canon /* k x 4 */, uint64_t *paths_canon /* k x depth x (width - 1) x 4 */);
 int zk_mtree_fill_witnesses(const zk_mtree *t, const uint64_t *indices, uint32_t k, void *d_w, uint64_t row_elems, const zk_mtree_layout *layout);
+int zk_mtree_fill_full_witnesses(const zk_mtree *t, const uint64_t *indices, uint32_t k, void *d_w, uint64_t row_elems,
+                                 const zk_mtree_layout *layout, uint32_t level_var0, uint32_t level_stride);
 int zk_mimc_constants(uint64_t *round_constants_canon /* 91 x 4 */, uint64_t *ivs_canon /* 29 x 4 */);
 int zk_mimc_hash2(const uint64_t *left, const uint64_t *right, const uint64_t *iv, uint32_t n, int device, uint64_t *out);
 int zk_poseidon_constants(uint64_t *C_canon /* 65 x 4 */, uint64_t *M_canon /* 36 x 4, row major */);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """dev tool: the measurements of profiles/poseidon.txt -- the Poseidon hash kernel in both MIX forms (Fr::ldot6 against six lmul per row), builds
 and single appends of the Poseidon tree at widths 2 and 4 beside the MiMC tree in the same run, and membership proofs per second of the Poseidon
-circuit beside the MiMC circuit.
+circuit beside the MiMC circuit, through the planner (fill_witnesses -> WitnessPlan.solve) and straight from the tree (fill_full_witnesses).
 usage: python tools/poseidon_bench.py [--log-hashes 20] [--reps 5] [--no-proofs]"""
 import argparse
 import ctypes as C
@@ -131,6 +131,30 @@ def main():
         print("  non-zeros of A + B + C: %d (%.1f per constraint)" % (nnz, nnz / r.nC))
         print("membership proofs, %s depth 29 (%d constraints, domain 2^%d), k = %d: median %.2f ms (min %.2f, max %.2f, %d reps) = %.0f proofs/s"
               % (hasher, r.nC, r.domain_size.bit_length() - 1, k, med, lo, hi, a.reps * 2, 1e3 * k / med))
+        # ---- the same proofs with the complete witness straight from the tree: fill_full_witnesses -> submit_batch -> collect
+        solved = buf.download((k, r.V + 1, 4))
+
+        def full_chain():
+            t.fill_full_witnesses(idx, buf, r)
+            ctx.submit_batch(None, device_ptr=buf.ptr, k=k)
+            ctx.collect_batch(k)
+        buf.upload(np.zeros((k, r.V + 1, 4), dtype=np.uint64))
+        t.fill_full_witnesses(idx, buf, r)
+        assert np.array_equal(buf.download((k, r.V + 1, 4)), solved)   # the rows the planner left, byte for byte
+        fmed, flo, fhi = wall_ms(full_chain, a.reps * 2, warm=2)
+        parts = [("fill_full_witnesses", lambda: t.fill_full_witnesses(idx, buf, r)),
+                 ("submit_batch + collect_batch", lambda: (ctx.submit_batch(None, device_ptr=buf.ptr, k=k), ctx.collect_batch(k)))]
+        print("  parts, %s, full witness: " % hasher + "; ".join("%s median %.2f ms (min %.2f, max %.2f)" % ((name,) + wall_ms(fn, a.reps * 2, warm=1)) for name, fn in parts))
+        print("membership proofs from full witnesses, %s depth 29 (%d constraints), k = %d: median %.2f ms (min %.2f, max %.2f, %d reps) = %.0f proofs/s (%.2f x the chain above)"
+              % (hasher, r.nC, k, fmed, flo, fhi, a.reps * 2, 1e3 * k / fmed, med / fmed))
+        # ... and the call alone at k = 4096 (every leaf of the tree once): a throughput figure
+        kk = 4096
+        big = P.DeviceBuffer(32 * (r.V + 1) * kk)
+        all_idx = list(range(kk))
+        bmed, blo, bhi = wall_ms(lambda: t.fill_full_witnesses(all_idx, big, r), a.reps, warm=1)
+        print("fill_full_witnesses, %s depth 29, k = %d: median %.2f ms (min %.2f, max %.2f, %d reps) = %.0f witnesses/s, %.1f GB/s written"
+              % (hasher, kk, bmed, blo, bhi, a.reps, 1e3 * kk / bmed, 32e-6 * (r.V + 1) * kk / bmed))
+        big.free()
         ctx.close(); plan.close(); t.close(); buf.free()
 
 
