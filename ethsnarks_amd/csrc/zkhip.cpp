@@ -1880,7 +1880,8 @@ k_witness_tape(const uint32_t *__restrict__ tape, uint32_t n_records, const fe *
 
 struct zk_wplan {
     int device = 0;
-    uint32_t nC = 0, V = 0, n_records = 0;
+    uint32_t nC = 0, V = 0, n_records = 0;                           // (a wide plan: its program is the tape, its passes the records)
+    zk_wplan_stats stats = {};                                       // kind 0: tape, 1: wide (wplan_wide.hpp)
     uint32_t *d_tape = nullptr, *d_viol = nullptr;
     fe *d_coefs = nullptr;
     hipStream_t st = nullptr;
@@ -1892,6 +1893,8 @@ struct zk_wplan {
         if (st) hipStreamDestroy(st);
     }
 };
+
+#include "wplan_wide.hpp"
 
 extern "C" int zk_wplan_create(const zk_csr *A, const zk_csr *B, const zk_csr *C, uint32_t nC, uint32_t V,
                                const uint8_t *known, int device, zk_wplan **out) try {
@@ -1906,6 +1909,7 @@ extern "C" int zk_wplan_create_hinted(const zk_csr *A, const zk_csr *B, const zk
     std::vector<uint8_t> have(known, known + (size_t)V + 1);
     have[0] = 1;                                                     // the constant ONE
     std::vector<uint32_t> tape;
+    uint32_t products = 0;                                           // (zk_wplan_info: field products per witness)
     std::vector<fe> coefs;                                           // distinct coefficients (and inverses), Montgomery
     auto coef_index = [&](const fe &c) -> uint32_t {                 // (linear search from the back: gadget circuits reuse few values)
         for (size_t i = coefs.size(); i-- > 0 && coefs.size() - i <= 64;) if (Fr::eq(coefs[i], c)) return (uint32_t)i;
@@ -1975,11 +1979,12 @@ extern "C" int zk_wplan_create_hinted(const zk_csr *A, const zk_csr *B, const zk
                 if (col == 0) { kind = 3; ci = coef_index(cf); }                    // coef * ONE: the coefficient itself
                 else if (Fr::eq(cf, one)) kind = 0;
                 else if (Fr::eq(cf, minus_one)) kind = 1;
-                else { kind = 2; ci = coef_index(cf); }
+                else { kind = 2; ci = coef_index(cf); products++; }
                 if (ci >= (1u << 24)) return fail(ZK_ERR_ARG, "witness plan: more than 2^24 distinct coefficients");
                 terms[q].push_back(col | kind << 28);                               // (the cache slot is decided when the term's record is laid out)
                 terms[q].push_back(ci);
             }
+        products += (!terms[0].empty() && !terms[1].empty()) + has_inv;
         // records of at most WP_NA / WP_NB / WP_NC terms; all but the last are partial
         size_t done[3] = {0, 0, 0};
         for (;;) {
@@ -2017,12 +2022,37 @@ extern "C" int zk_wplan_create_hinted(const zk_csr *A, const zk_csr *B, const zk
     if (coefs.empty()) coefs.push_back(one);
     std::unique_ptr<zk_wplan> p(new zk_wplan());
     p->device = device; p->nC = nC; p->V = V; p->n_records = n_records;
+    p->stats.records_or_passes = n_records; p->stats.products = products;
     int rc = dev_upload(&p->d_tape, tape.data(), tape.size());
     if (rc == ZK_OK) rc = dev_upload(&p->d_coefs, coefs.data(), coefs.size());
     if (rc == ZK_OK && hipMalloc(&p->d_viol, 4) != hipSuccess) rc = ZK_ERR_NOMEM;
     if (rc == ZK_OK && hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking) != hipSuccess) rc = ZK_ERR_HIP;
     if (rc != ZK_OK) return rc;
     *out = p.release();
+    return ZK_OK;
+} ZK_GUARD
+extern "C" int zk_wplan_create_wide(const zk_csr *A, const zk_csr *B, const zk_csr *C, uint32_t nC, uint32_t V, const uint8_t *known,
+                                    const zk_whint *hints, uint32_t n_hints, uint32_t lanes, int device, zk_wplan **out) try {
+    if (!A || !B || !C || !known || !out || (n_hints && !hints)) return fail(ZK_ERR_ARG, "null argument");
+    if (A->n_rows != nC || B->n_rows != nC || C->n_rows != nC) return fail(ZK_ERR_ARG, "CSR row counts must equal nC");
+    if (V >= (1u << 28)) return fail(ZK_ERR_ARG, "witness plan: more than 2^28 variables");
+    if (lanes < 4 || lanes > 64 || (lanes & (lanes - 1))) return fail(ZK_ERR_ARG, "witness plan (wide): lanes must be 4, 8, 16, 32 or 64");
+    ZK_TRY(use_device(device));
+    WidePlanHost h;
+    ZK_TRY(wide_compile(A, B, C, nC, V, known, hints, n_hints, lanes, h));
+    std::unique_ptr<zk_wplan> p(new zk_wplan());
+    p->device = device; p->nC = nC; p->V = V; p->n_records = h.st.records_or_passes; p->stats = h.st;
+    int rc = dev_upload(&p->d_tape, h.prog.data(), h.prog.size());
+    if (rc == ZK_OK) rc = dev_upload(&p->d_coefs, h.coefs.data(), h.coefs.size());
+    if (rc == ZK_OK && hipMalloc(&p->d_viol, 4) != hipSuccess) rc = ZK_ERR_NOMEM;
+    if (rc == ZK_OK && hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking) != hipSuccess) rc = ZK_ERR_HIP;
+    if (rc != ZK_OK) return rc;
+    *out = p.release();
+    return ZK_OK;
+} ZK_GUARD
+extern "C" int zk_wplan_info(const zk_wplan *p, zk_wplan_stats *out) try {
+    if (!p || !out) return fail(ZK_ERR_ARG, "null argument");
+    *out = p->stats;
     return ZK_OK;
 } ZK_GUARD
 extern "C" void zk_wplan_free(zk_wplan *p) try { delete p; } ZK_GUARD_VOID
@@ -2032,6 +2062,10 @@ extern "C" int zk_wplan_solve(zk_wplan *p, void *d_w, uint32_t k, uint32_t *viol
     if (!p || !d_w || !k) return fail(ZK_ERR_ARG, "bad argument");
     ZK_TRY(use_device(p->device));
     ZK_HIP(hipMemsetAsync(p->d_viol, 0, 4, p->st));
+    if (p->stats.kind == 1) {                                        // wide plan: a wave holds 64 / lanes witnesses
+        const uint32_t lanes_log2 = (uint32_t)__builtin_ctz(p->stats.lanes);
+        ZK_LAUNCH_SYNC(k_witness_wide, zk_div_up(k, 64u >> lanes_log2), 64, p->st, (const uint32_t *)p->d_tape, p->n_records, (const fe *)p->d_coefs, (fe *)d_w, p->V + 1, k, lanes_log2, p->d_viol);
+    } else
     ZK_LAUNCH(k_witness_tape, zk_div_up(k, 64), 64, p->st, (const uint32_t *)p->d_tape, p->n_records, (const fe *)p->d_coefs, (fe *)d_w, p->V + 1, k, p->d_viol);
     uint32_t v = 0;
     ZK_HIP(hipMemcpyAsync(&v, p->d_viol, 4, hipMemcpyDeviceToHost, p->st));

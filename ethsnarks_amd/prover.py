@@ -65,7 +65,7 @@ EXPORTS = [
     "zk_prove_batch", "zk_prove_batch_submit", "zk_prove_batch_submit_resident", "zk_prove_batch_collect",
     "zk_pk_load_raw_full", "zk_pk_save_raw_full", "zk_pk_is_full", "zk_keygen_full",
     "zk_prove_zk", "zk_prove_zk_batch", "zk_prove_zk_batch_submit", "zk_prove_zk_batch_submit_resident", "zk_prove_zk_batch_collect",
-    "zk_wplan_create", "zk_wplan_create_hinted", "zk_wplan_solve", "zk_wplan_free", "zk_dev_alloc", "zk_dev_free", "zk_dev_upload", "zk_dev_download",
+    "zk_wplan_create", "zk_wplan_create_hinted", "zk_wplan_create_wide", "zk_wplan_info", "zk_wplan_solve", "zk_wplan_free", "zk_dev_alloc", "zk_dev_free", "zk_dev_upload", "zk_dev_download",
     "zk_chain_submit", "zk_chain_device", "zk_h_from_chains_submit", "zk_h_device", "zk_chain_wait", "zk_prove_submit_with_h", "zk_prove_submit_defer_h", "zk_prove_submit_h", "zk_prove_abort",
     "zk_prove_submit_pinned", "zk_prove_batch_submit_pinned", "zk_host_alloc", "zk_host_free", "zk_host_register", "zk_host_unregister",
     "zk_prove_submit_resident", "zk_prove_stage", "zk_prove_stage_pinned", "zk_prove_submit_staged", "zk_ctx_info", "zk_ctx_table_info", "zk_ctx_partials_device", "zk_prove_collect_device", "zk_prove_combine_device", "zk_launch_count", "zk_profile_begin", "zk_profile_end", "zk_device_info", "zk_device_pci_bus_id",
@@ -778,11 +778,17 @@ class DeviceBuffer:
             pass
 
 
+class ZkWplanStats(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("kind", "lanes", "records_or_passes", "levels", "ops", "dots", "steps", "max_level_ops", "lds_slots", "products")]
+
+
 class WitnessPlan:
     """zk_wplan: the constraint system as a witness program (forward substitution), run on the GPU for k witnesses at a time.
-    `known`: indices of the variables the caller supplies (ONE is implied)."""
+    `known`: indices of the variables the caller supplies (ONE is implied).  lanes=None: the tape plan, one lane per witness (MiMC-like
+    chains of short rows); lanes = 4 .. 64 (a power of two): the wide plan, that many lanes per witness, for systems with long linear
+    combinations (Poseidon) -- same rows, same violation counts, same refusals."""
 
-    def __init__(self, r1cs, known, device=0, bit_hints=(), inv_hints=(), nonzero_hints=()):
+    def __init__(self, r1cs, known, device=0, bit_hints=(), inv_hints=(), nonzero_hints=(), lanes=None):
         """bit_hints: (src, first, count) triples -- w[first + i] = bit i of w[src] (ZK_WHINT_BITS: advice the constraints only check);
         inv_hints: (src, dst) pairs -- w[dst] = 1 / w[src], 0 for 0 (ZK_WHINT_INV); nonzero_hints: (src, dst) -- w[dst] = [w[src] != 0]
         (ZK_WHINT_NONZERO): the M and Y of the reference's IsNonZero gadget, src/gadgets/isnonzero.cpp:48-60"""
@@ -793,10 +799,23 @@ class WitnessPlan:
         a, b, c = _csr_structs(r1cs, keep)
         h = C.c_void_p()
         hints = np.asarray([[1, s_, f_, n_] for s_, f_, n_ in bit_hints] + [[2, s_, d_, 1] for s_, d_ in inv_hints] + [[3, s_, d_, 1] for s_, d_ in nonzero_hints], dtype=np.uint32).reshape(-1, 4)
-        _check(lib.zk_wplan_create_hinted(C.byref(a), C.byref(b), C.byref(c), C.c_uint32(r1cs.nC), C.c_uint32(r1cs.V),
-                                          flags.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                          hints.ctypes.data_as(C.c_void_p) if len(hints) else None, C.c_uint32(len(hints)), device, C.byref(h)))
+        if lanes is None:
+            _check(lib.zk_wplan_create_hinted(C.byref(a), C.byref(b), C.byref(c), C.c_uint32(r1cs.nC), C.c_uint32(r1cs.V),
+                                              flags.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                              hints.ctypes.data_as(C.c_void_p) if len(hints) else None, C.c_uint32(len(hints)), device, C.byref(h)))
+        else:
+            if not isinstance(lanes, (int, np.integer)) or isinstance(lanes, bool) or not 0 <= lanes < 2 ** 32:
+                raise ZkError(1, "witness plan (wide): lanes must be 4, 8, 16, 32 or 64")
+            _check(lib.zk_wplan_create_wide(C.byref(a), C.byref(b), C.byref(c), C.c_uint32(r1cs.nC), C.c_uint32(r1cs.V),
+                                            flags.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                            hints.ctypes.data_as(C.c_void_p) if len(hints) else None, C.c_uint32(len(hints)), C.c_uint32(lanes), device, C.byref(h)))
         self._h, self.r1cs = h, r1cs
+
+    def info(self):
+        """zk_wplan_info as a dict: kind (0 tape, 1 wide), lanes, records_or_passes, levels, ops, dots, steps, max_level_ops, lds_slots, products"""
+        st = ZkWplanStats()
+        _check(_lib.zk_wplan_info(self._h, C.byref(st)))
+        return {n: int(getattr(st, n)) for n, _ in st._fields_}
 
     def solve(self, device_ptr, k):
         """complete k witnesses in place (device memory); returns the number of violated check constraints"""

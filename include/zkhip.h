@@ -333,6 +333,21 @@ int zk_wplan_create(const zk_csr *A, const zk_csr *B, const zk_csr *C, uint32_t 
 typedef struct { uint32_t kind, src, first, count; } zk_whint;
 int zk_wplan_create_hinted(const zk_csr *A, const zk_csr *B, const zk_csr *C, uint32_t nC, uint32_t V, const uint8_t *known,
                            const zk_whint *hints, uint32_t n_hints, int device, zk_wplan **out);
+/* ... as a WIDE plan: `lanes` lanes (a power of two, 4 .. 64; a wave holds 64 / lanes witnesses) work on ONE witness.  Same semantics, same
+ * refusals and messages as zk_wplan_create_hinted (n_hints = 0 with hints = NULL is the hint-free form): the constraints are classified in the
+ * given order by the same rule, so the completed rows are byte-identical and the violation counts equal.  Each linear combination becomes
+ * chunked dot products of up to 8 terms, identical combinations of neighbouring constraints are evaluated once, and independent operations
+ * run side by side, level by level (csrc/wplan_wide.hpp).  For systems with WIDE rows (Poseidon: 63-term rows with general coefficients); a
+ * chain of short rows (MiMC) has nothing to spread and is faster on the tape plan, which stays the default.
+ * ZK_ERR_ARG: lanes not one of 4, 8, 16, 32, 64; a system whose temporaries do not fit the group's share of LDS (32 x lanes values) -- the
+ * message names the level and the slots it needs.  zk_wplan_solve and zk_wplan_free take either kind of plan.
+ *   zk_wplan_info   kind 0: tape (records_or_passes = records, products), kind 1: wide (passes, dataflow levels, operations = dots + steps +
+ *                   hint operations, the widest level, the peak of LDS slots in use); products = field products of the constraint
+ *                   evaluation per witness (coefficient products, a x b, the division by the target's coefficient), after deduplication */
+typedef struct { uint32_t kind, lanes, records_or_passes, levels, ops, dots, steps, max_level_ops, lds_slots, products; } zk_wplan_stats;
+int zk_wplan_create_wide(const zk_csr *A, const zk_csr *B, const zk_csr *C, uint32_t nC, uint32_t V, const uint8_t *known,
+                         const zk_whint *hints, uint32_t n_hints, uint32_t lanes, int device, zk_wplan **out);
+int zk_wplan_info(const zk_wplan *plan, zk_wplan_stats *out);
 int zk_wplan_solve(zk_wplan *plan, void *d_w, uint32_t k, uint32_t *violations);
 void zk_wplan_free(zk_wplan *plan);
 int zk_dev_alloc(size_t bytes, int device, void **out);

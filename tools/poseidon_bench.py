@@ -50,13 +50,15 @@ def main():
     ap.add_argument("--log-hashes", type=int, default=20)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-proofs", action="store_true")
+    ap.add_argument("--lanes", type=int, default=None, help="the chain leg's WitnessPlan: lanes per witness of the wide plan (default: the tape plan)")
+    ap.add_argument("--chain-only", action="store_true", help="only the membership-proof chain legs")
     a = ap.parse_args()
     P.load_library()
     lib = P._lib
     print("library:", lib.zk_version().decode(), "| device:", P.device_info(0))
     # ---- independent hashes, both MIX forms (kernel time; the entry point's copies are not the kernel's)
     n = 1 << a.log_hashes
-    for n_in in (2, 4):
+    for n_in in () if a.chain_only else (2, 4):
         rows = random_limbs(n * n_in, 10 + n_in)
         out = np.zeros((n, 4), dtype=np.uint64)
         call = lambda: P._check(lib.zk_poseidon_hash(P._p64(rows), C.c_uint32(n_in), C.c_uint32(n), 0, P._p64(out)))
@@ -71,7 +73,7 @@ def main():
                   % (a.log_hashes, n_in, mix, med, lo, hi, a.reps, n / med / 1e3, n * products / med / 1e6, products))
     # ---- tree builds from a device buffer (Montgomery leaves), MiMC beside Poseidon in the same run
     trees = [("mimc", 2, 29), ("poseidon", 2, 29), ("poseidon", 4, 14)]
-    for lg in (16, 20):
+    for lg in () if a.chain_only else (16, 20):
         n = 1 << lg
         buf = P.DeviceBuffer(32 * n)
         buf.upload(random_limbs(n, lg))
@@ -94,7 +96,7 @@ def main():
                   % (lg, hasher, w, depth, statistics.median(ts), min(ts), max(ts), a.reps, launches[-1], nodes))
         buf.free()
     # ---- one append at full depth: the latency floor, one dependent hash chain per level
-    for hasher, w, depth in trees:
+    for hasher, w, depth in () if a.chain_only else trees:
         t = M.MerkleTree(w ** depth, reserve=1 << 12, width=w, hasher=hasher)
         t.extend(random_limbs(1000, 5))
         leaf = random_limbs(1, 6)
@@ -110,7 +112,8 @@ def main():
         n_sup = 1 + 1 + 29 + 29 + 1 + (29 if hasher == "mimc" else 0)
         pk, _ = P.keygen(r, seed=5)
         ctx = P.ProverContext(pk, r, max_batch=k)
-        plan = P.WitnessPlan(r, list(range(n_sup)))
+        plan = P.WitnessPlan(r, list(range(n_sup)), lanes=a.lanes)
+        print("  witness plan, %s: %s" % (hasher, plan.info()))
         t = M.MerkleTree(1 << 29, hasher=hasher)
         t.extend(random_limbs(4096, 7))
         idx = [(i * 127) % 4096 for i in range(k)]
