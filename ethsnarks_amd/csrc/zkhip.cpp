@@ -1881,6 +1881,7 @@ k_witness_tape(const uint32_t *__restrict__ tape, uint32_t n_records, const fe *
 struct zk_wplan {
     int device = 0;
     uint32_t nC = 0, V = 0, n_records = 0;                           // (a wide plan: its program is the tape, its passes the records)
+    size_t n_words = 0, n_coefs = 0;                                 // what d_tape and d_coefs hold (zk_wplan_probe_program)
     zk_wplan_stats stats = {};                                       // kind 0: tape, 1: wide (wplan_wide.hpp)
     uint32_t *d_tape = nullptr, *d_viol = nullptr;
     fe *d_coefs = nullptr;
@@ -2042,6 +2043,7 @@ extern "C" int zk_wplan_create_wide(const zk_csr *A, const zk_csr *B, const zk_c
     ZK_TRY(wide_compile(A, B, C, nC, V, known, hints, n_hints, lanes, h));
     std::unique_ptr<zk_wplan> p(new zk_wplan());
     p->device = device; p->nC = nC; p->V = V; p->n_records = h.st.records_or_passes; p->stats = h.st;
+    p->n_words = h.prog.size(); p->n_coefs = h.coefs.size();
     int rc = dev_upload(&p->d_tape, h.prog.data(), h.prog.size());
     if (rc == ZK_OK) rc = dev_upload(&p->d_coefs, h.coefs.data(), h.coefs.size());
     if (rc == ZK_OK && hipMalloc(&p->d_viol, 4) != hipSuccess) rc = ZK_ERR_NOMEM;
@@ -2056,6 +2058,20 @@ extern "C" int zk_wplan_info(const zk_wplan *p, zk_wplan_stats *out) try {
     return ZK_OK;
 } ZK_GUARD
 extern "C" void zk_wplan_free(zk_wplan *p) try { delete p; } ZK_GUARD_VOID
+// TEST INFRASTRUCTURE: what a wide plan uploaded, read back from device memory -- the pass records ([pass][word][lane in group], the empty
+// last pass included), then the coefficient table the records index (8 words per entry, Montgomery).  *n_words is set whenever the plan is
+// a wide one, so a caller can size its buffer from a first call with cap = 0.
+extern "C" int zk_wplan_probe_program(const zk_wplan *p, uint32_t *words, size_t cap, size_t *n_words) try {
+    if (!p || !n_words) return fail(ZK_ERR_ARG, "null argument");
+    if (p->stats.kind != 1) return fail(ZK_ERR_ARG, "witness plan probe: a tape plan has no lane program");
+    const size_t n = p->n_words + 8 * p->n_coefs;
+    *n_words = n;
+    if (!words || cap < n) return fail(ZK_ERR_ARG, "witness plan probe: the buffer is shorter than the program");
+    ZK_TRY(use_device(p->device));
+    ZK_HIP(hipMemcpy(words, p->d_tape, 4 * p->n_words, hipMemcpyDeviceToHost));
+    ZK_HIP(hipMemcpy(words + p->n_words, p->d_coefs, 32 * p->n_coefs, hipMemcpyDeviceToHost));
+    return ZK_OK;
+} ZK_GUARD
 // d_w: k witnesses, (V + 1) x 32 bytes each, contiguous, device memory, Montgomery; the supplied variables (and ONE at index
 // 0) filled in.  Completes them in place; *violations = constraints (over all k) that introduce nothing and do not hold.
 extern "C" int zk_wplan_solve(zk_wplan *p, void *d_w, uint32_t k, uint32_t *violations) try {

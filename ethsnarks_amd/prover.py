@@ -54,7 +54,7 @@ class ZkTimings(C.Structure):
         return {n: float(getattr(self, n)) for n, _ in self._fields_}
 
 
-ABI_VERSION = 6          # include/zkhip.h ZK_ABI_VERSION
+ABI_VERSION = 7          # include/zkhip.h ZK_ABI_VERSION
 
 EXPORTS = [
     "zk_version", "zk_abi_version", "zk_strerror", "zk_last_error", "zk_device_count",
@@ -65,7 +65,7 @@ EXPORTS = [
     "zk_prove_batch", "zk_prove_batch_submit", "zk_prove_batch_submit_resident", "zk_prove_batch_collect",
     "zk_pk_load_raw_full", "zk_pk_save_raw_full", "zk_pk_is_full", "zk_keygen_full",
     "zk_prove_zk", "zk_prove_zk_batch", "zk_prove_zk_batch_submit", "zk_prove_zk_batch_submit_resident", "zk_prove_zk_batch_collect",
-    "zk_wplan_create", "zk_wplan_create_hinted", "zk_wplan_create_wide", "zk_wplan_info", "zk_wplan_solve", "zk_wplan_free", "zk_dev_alloc", "zk_dev_free", "zk_dev_upload", "zk_dev_download",
+    "zk_wplan_create", "zk_wplan_create_hinted", "zk_wplan_create_wide", "zk_wplan_info", "zk_wplan_solve", "zk_wplan_free", "zk_wplan_probe_program", "zk_dev_alloc", "zk_dev_free", "zk_dev_upload", "zk_dev_download",
     "zk_chain_submit", "zk_chain_device", "zk_h_from_chains_submit", "zk_h_device", "zk_chain_wait", "zk_prove_submit_with_h", "zk_prove_submit_defer_h", "zk_prove_submit_h", "zk_prove_abort",
     "zk_prove_submit_pinned", "zk_prove_batch_submit_pinned", "zk_host_alloc", "zk_host_free", "zk_host_register", "zk_host_unregister",
     "zk_prove_submit_resident", "zk_prove_stage", "zk_prove_stage_pinned", "zk_prove_submit_staged", "zk_ctx_info", "zk_ctx_table_info", "zk_ctx_partials_device", "zk_prove_collect_device", "zk_prove_combine_device", "zk_launch_count", "zk_profile_begin", "zk_profile_end", "zk_device_info", "zk_device_pci_bus_id",
@@ -822,6 +822,19 @@ class WitnessPlan:
         bad = C.c_uint32(0)
         _check(_lib.zk_wplan_solve(self._h, C.c_void_p(device_ptr), C.c_uint32(k), C.byref(bad)))
         return int(bad.value)
+
+    def probe_program(self):
+        """zk_wplan_probe_program (test infrastructure): (records, coefs) of a wide plan as uploaded -- records: uint32 (passes + 1, 19, lanes),
+        coefs: uint32 (n, 8), Montgomery limbs"""
+        n = C.c_size_t(0)
+        rc = _lib.zk_wplan_probe_program(self._h, None, C.c_size_t(0), C.byref(n))
+        if n.value == 0:
+            _check(rc)
+        words = np.zeros(n.value, dtype=np.uint32)
+        _check(_lib.zk_wplan_probe_program(self._h, _p32(words), C.c_size_t(words.size), C.byref(n)))
+        st = self.info()
+        n_prog = (st["records_or_passes"] + 1) * 19 * st["lanes"]
+        return words[:n_prog].reshape(st["records_or_passes"] + 1, 19, st["lanes"]), words[n_prog:].reshape(-1, 8)
 
     def close(self):
         if getattr(self, "_h", None) is not None and _lib is not None:

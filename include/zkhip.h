@@ -64,7 +64,7 @@ extern "C" {
  * 6: zk_mtree_fill_full_witnesses.
  * A client checks zk_abi_version() == ZK_ABI_VERSION once after loading the library, or passes the size of the zk_config
  * it was compiled with to zk_ctx_create_sized (members it does not know read as 0 = their defaults). */
-#define ZK_ABI_VERSION 6
+#define ZK_ABI_VERSION 7
 
 typedef struct zk_pk zk_pk;
 typedef struct zk_vk zk_vk;
@@ -350,6 +350,11 @@ int zk_wplan_create_wide(const zk_csr *A, const zk_csr *B, const zk_csr *C, uint
 int zk_wplan_info(const zk_wplan *plan, zk_wplan_stats *out);
 int zk_wplan_solve(zk_wplan *plan, void *d_w, uint32_t k, uint32_t *violations);
 void zk_wplan_free(zk_wplan *plan);
+/* TEST INFRASTRUCTURE, nothing on the proving path calls it: the program of a WIDE plan copied back from device memory, as 32-bit words --
+ * the pass records in the layout at the top of csrc/wplan_wide.hpp ([pass][word of the record][lane in group], (passes + 1) x 19 x lanes words:
+ * the program ends in one empty pass), then the coefficient table that the records index, 8 words per entry (Montgomery).  *n_words receives
+ * the number of words whenever the plan is a wide one.  ZK_ERR_ARG for a tape plan and for cap < *n_words (nothing is copied). */
+int zk_wplan_probe_program(const zk_wplan *plan, uint32_t *words, size_t cap, size_t *n_words);
 int zk_dev_alloc(size_t bytes, int device, void **out);
 int zk_dev_free(void *p);
 int zk_dev_upload(void *dst, const void *src, size_t bytes);

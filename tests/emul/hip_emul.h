@@ -5,7 +5,7 @@
 // `pytest -m "not gpu"` in a container that has no GPU.  The same kernel sources are compiled with
 // g++ -DZK_EMUL into tests/emul/libzkhip_emul.so; a "launch" runs the blocks one after another, the
 // threads of a block either sequentially (kernels without block barriers) or as cooperative fibers that
-// yield at __syncthreads() (kernels with barriers).  The product (libzkhip.so) never sees this file, the
+// yield at __syncthreads() (kernels with barriers; ascending lane order, or descending with ZK_EMUL_LANE_ORDER=reverse).  The product (libzkhip.so) never sees this file, the
 // Python package never loads the emulation library, and nothing here is ever timed or shipped.
 #pragma once
 #include <atomic>
@@ -118,10 +118,15 @@ void launch(bool needs_sync, dim3 grid, dim3 block, Body body) {
     for (unsigned bxy = 0; bxy < grid.x * grid.y; bxy++) {
         const unsigned bx = bxy % grid.x, by = bxy / grid.x;
         for (unsigned tx = 0; tx < block.x; tx++) fiber_init(g_fibers[tx], g_stacks.data() + (size_t)tx * FIBER_STACK);
+        // ZK_EMUL_LANE_ORDER=reverse (read at every launch): each sweep resumes the fibers from the last lane down.  A kernel whose result
+        // depends on the order in which the lanes run between two barriers then gives another answer than in the default, ascending sweep.
+        const char *order = getenv("ZK_EMUL_LANE_ORDER");
+        const bool reverse = order && !strcmp(order, "reverse");
         bool any = true;
         while (any) {
             any = false;
-            for (unsigned tx = 0; tx < block.x; tx++) {
+            for (unsigned i = 0; i < block.x; i++) {
+                const unsigned tx = reverse ? block.x - 1 - i : i;
                 Fiber &f = g_fibers[tx];
                 if (f.done) continue;
                 threadIdx = dim3(tx); blockIdx = dim3(bx, by); blockDim = block; gridDim = grid;
