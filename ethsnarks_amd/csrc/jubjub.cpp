@@ -3,6 +3,7 @@
 // Host-only work, done once per context with the strict field operations: hash-to-point (sha256, the from_y rule, a Tonelli-Shanks root, times the
 // cofactor), the Pedersen tables (1 .. 4) 16^j B_s as affine points, the 16 multiples of the EdDSA base point, the MiMC constants of the seed
 // "EdDSA_Verify.RAM".  Per item the host only compares limbs with r; every field operation of a batch runs in ONE kernel launch.
+#include <algorithm>
 #include <memory>
 #include <string>
 #include <vector>
@@ -17,6 +18,7 @@ using namespace zk;
 using namespace zk::jubjub;
 
 static_assert(ZK_JJ_OP_ADD == OP_ADD && ZK_JJ_OP_DOUBLE == OP_DOUBLE && ZK_JJ_OP_NEGATE == OP_NEGATE, "zkhip.h and jubjub.hpp number the point operations alike");
+static_assert(sizeof(zk_eddsa_layout) == sizeof(FillLayout) && sizeof(FillLayout) == 19 * sizeof(uint32_t), "zkhip.h and jubjub.hpp lay the witness row out alike");
 static_assert(ZK_EDDSA_MIMC == SCHEME_MIMC && ZK_EDDSA_PURE == SCHEME_PURE && ZK_EDDSA_HASH == SCHEME_HASH, "zkhip.h and jubjub.hpp number the schemes alike");
 
 namespace {
@@ -202,7 +204,8 @@ struct zk_pedersen {
 struct zk_eddsa {
     int device = 0;
     uint32_t scheme = 0, msg_len = 0, ram_windows = 0, m_windows = 0;
-    DevBuf consts, scratch;                                     // consts: btab | rc | ram table | m table
+    DevBuf consts, scratch;                                     // consts: btab | rc | ram table | m table | the 2-bit windows of B (MiMC)
+    const fe *fbtab = nullptr;                                  // (0 .. 3) 4^i B, i = 0 .. 126: the tables of the circuit's fixed_base_mul
     EddsaView view;
     hipStream_t st = nullptr;
     ~zk_eddsa() { if (st) (void)hipStreamDestroy(st); }
@@ -348,14 +351,28 @@ extern "C" int zk_eddsa_create(int scheme, const uint64_t *B, uint32_t msg_len, 
         pedersen_table("EdDSA_Verify.RAM", v->ram_windows, ram);
         if (scheme == SCHEME_HASH) { v->m_windows = (8 * msg_len + 2) / 3; pedersen_table("EdDSA_Verify.M", v->m_windows, mt); }
     }
-    std::vector<fe> all(btab);
+    std::vector<fe> all(btab), fb;
+    if (scheme == SCHEME_MIMC) {                                // window i of the circuit's fixed-base multiplication: identity, P, 2 P, 3 P, P = 4^i B
+        std::vector<jpoint> w;
+        w.reserve(4 * FB_WINDOWS);
+        jpoint cur = mult[1];
+        for (uint32_t i = 0; i < FB_WINDOWS; i++) {
+            jpoint m2 = cur; jj_dbl(m2, true);
+            jpoint m3 = m2; host_add(m3, cur);
+            w.push_back(mult[0]); w.push_back(cur); w.push_back(m2); w.push_back(m3);
+            cur = m2; jj_dbl(cur, true);
+        }
+        to_entries(w, fb);
+    }
     const size_t o_rc = all.size(); all.insert(all.end(), rc.begin(), rc.end());
     const size_t o_ram = all.size(); all.insert(all.end(), ram.begin(), ram.end());
     const size_t o_m = all.size(); all.insert(all.end(), mt.begin(), mt.end());
+    const size_t o_fb = all.size(); all.insert(all.end(), fb.begin(), fb.end());
     ZK_HIP(hipStreamCreateWithFlags(&v->st, hipStreamNonBlocking));
     ZK_TRY(v->consts.upload(all.data(), sizeof(fe) * all.size()));
     const fe *d = (const fe *)v->consts.p;
     v->view.btab = d; v->view.rc = d + o_rc; v->view.ram_tab = d + o_ram; v->view.m_tab = d + o_m;
+    if (scheme == SCHEME_MIMC) v->fbtab = d + o_fb;
     v->view.scheme = v->scheme; v->view.msg_len = msg_len; v->view.ram_windows = v->ram_windows; v->view.m_windows = v->m_windows;
     *out = v.release();
     return ZK_OK;
@@ -385,6 +402,62 @@ extern "C" int zk_eddsa_verify_batch(zk_eddsa *v, const uint64_t *A, const uint6
     ZK_HIP(hipMemcpyAsync(dS, s, sb, hipMemcpyHostToDevice, v->st));
     ZK_HIP(hipMemcpyAsync(dM, msgs, mb, hipMemcpyHostToDevice, v->st));
     ZK_LAUNCH(k_eddsa_verify, zk_div_up(n, BLOCK), BLOCK, v->st, v->view, (const fe *)dA, (const fe *)dR, (const fe *)dS, (const void *)dM, n, (uint8_t *)dV);
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipMemcpyAsync(verdicts, dV, n, hipMemcpyDeviceToHost, v->st));
+    ZK_HIP(hipStreamSynchronize(v->st));
+    return ZK_OK;
+} ZK_GUARD
+
+namespace {
+// every segment of the layout inside variables 1 .. n_vars, n_vars + 1 <= row_elems, no two segments overlapping.  The three blocks of a step
+// of the variable-base multiplication must lie, disjoint, within one stride of the lowest of them
+bool layout_fits(const FillLayout &L, uint32_t msg_len, uint64_t row_elems) {
+    if (L.msg_len != msg_len || (uint64_t)L.n_vars + 1 > row_elems) return false;
+    uint32_t range_vars = 0;
+    for (uint32_t i = 1; i + 1 < FIELD_BITS; i++) range_vars += modulus_m1_bit(i);
+    if (range_vars != T_RANGE_VARS) return false;
+    const uint64_t step0 = std::min(L.doubler_var0, std::min(L.cond_var0, L.adder_var0));
+    struct Seg { uint64_t at, len; };
+    const Seg step[3] = {{L.doubler_var0, DBL_VARS}, {L.cond_var0, 2}, {L.adder_var0, ADD_VARS}};
+    for (int i = 0; i < 3; i++) {
+        if (step[i].at + step[i].len > step0 + L.step_stride) return false;
+        for (int j = 0; j < i; j++) if (step[i].at < step[j].at + step[j].len && step[j].at < step[i].at + step[i].len) return false;
+    }
+    std::vector<Seg> segs = {{L.ax_var, 2}, {L.msg_var0, msg_len}, {L.rx_var, 2}, {L.s_bit0, FIELD_BITS}, {L.iv_var, 1}, {L.validator_var0, VALIDATOR_VARS},
+                             {L.window_var0, 2 * FB_WINDOWS}, {L.fixed_adder_var0, ADD_VARS * (FB_WINDOWS - 1)},
+                             {L.mimc_var0, (uint64_t)(4 + msg_len) * (1 + MIMC_ROUND_VARS)}, {L.t_bit0, T_BITS_VARS}, {L.t_range_var0, T_RANGE_VARS},
+                             {L.cond0_var, 2}, {step0, (uint64_t)N_STEPS * L.step_stride}, {L.last_adder_var0, ADD_VARS}};
+    std::sort(segs.begin(), segs.end(), [](const Seg &a, const Seg &b) { return a.at < b.at; });
+    uint64_t end = 1;                                           // variable 0 is ONE
+    for (const Seg &g : segs) {
+        if (g.at < end) return false;
+        end = g.at + g.len;
+    }
+    return end <= (uint64_t)L.n_vars + 1;
+}
+}  // namespace
+
+extern "C" int zk_eddsa_fill_witnesses(zk_eddsa *v, const uint64_t *A, const uint64_t *R, const uint64_t *s, const uint64_t *msgs, uint32_t n, void *d_w,
+                                       uint64_t row_elems, const zk_eddsa_layout *layout, uint8_t *verdicts) try {
+    if (!v || !A || !R || !s || !msgs || !d_w || !layout || !verdicts) return jfail(ZK_ERR_ARG, "null argument");
+    if (v->scheme != SCHEME_MIMC) return jfail(ZK_ERR_ARG, "only a ZK_EDDSA_MIMC verifier has a circuit to fill witnesses of");
+    FillLayout L;
+    memcpy(&L, layout, sizeof(L));
+    if (!layout_fits(L, v->msg_len, row_elems)) return jfail(ZK_ERR_ARG, "the layout does not fit the verifier's msg_len, overlaps itself or leaves the row");
+    if (n == 0) return ZK_OK;
+    if (!all_below_modulus(A, 2 * (uint64_t)n) || !all_below_modulus(R, 2 * (uint64_t)n)) return jfail(ZK_ERR_ARG, "a coordinate is not below the Fr modulus");
+    if (!all_below_modulus(msgs, (uint64_t)n * v->msg_len)) return jfail(ZK_ERR_ARG, "a message element is not below the Fr modulus");
+    ZK_TRY(jj_use_device(v->device));
+    const size_t pb = 2 * sizeof(fe) * (size_t)n, sb = sizeof(fe) * (size_t)n, mb = sb * v->msg_len;
+    ZK_TRY(v->scratch.ensure(2 * pb + sb + mb + align32(n)));
+    char *d = (char *)v->scratch.p;
+    char *dA = d, *dR = d + pb, *dS = d + 2 * pb, *dM = dS + sb, *dV = dM + mb;
+    ZK_HIP(hipMemcpyAsync(dA, A, pb, hipMemcpyHostToDevice, v->st));
+    ZK_HIP(hipMemcpyAsync(dR, R, pb, hipMemcpyHostToDevice, v->st));
+    ZK_HIP(hipMemcpyAsync(dS, s, sb, hipMemcpyHostToDevice, v->st));
+    ZK_HIP(hipMemcpyAsync(dM, msgs, mb, hipMemcpyHostToDevice, v->st));
+    ZK_LAUNCH(k_eddsa_fill, zk_div_up(n, BLOCK), BLOCK, v->st, v->view, v->fbtab, L, (const fe *)dA, (const fe *)dR, (const fe *)dS, (const fe *)dM, n, (fe *)d_w,
+              row_elems, (uint8_t *)dV);
     ZK_HIP(hipGetLastError());
     ZK_HIP(hipMemcpyAsync(verdicts, dV, n, hipMemcpyDeviceToHost, v->st));
     ZK_HIP(hipStreamSynchronize(v->st));

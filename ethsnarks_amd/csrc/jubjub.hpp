@@ -1,5 +1,6 @@
 // jubjub.hpp -- Baby JubJub on the device: curve arithmetic, the windowed Pedersen hash and batch EdDSA verification (jubjub.cpp, zk_jj_*,
-// zk_pedersen_*, zk_eddsa_* of include/zkhip.h).  The native side of ethsnarks/jubjub.py, pedersen.py and eddsa.py; no in-circuit gadgets.
+// zk_pedersen_*, zk_eddsa_* of include/zkhip.h).  The native side of ethsnarks/jubjub.py, pedersen.py and eddsa.py, and the witness of the
+// MiMC-EdDSA circuit whose gadgets are ethsnarks_amd/jubjub_gadgets.py.
 //
 // The curve is the twisted Edwards curve a x^2 + y^2 = 1 + d x^2 y^2 over Fr with a = 168700 (a square) and d = 168696 (a non-square), so the
 // unified addition below is COMPLETE: no input pair on the curve makes a denominator vanish, Z stays non-zero, and the identity, P = Q, P = -Q and
@@ -24,6 +25,7 @@
 //   k_jj_point_op     n additions / doublings / negations of affine points
 //   k_jj_pedersen     n windowed Pedersen hashes over a table of affine multiples in device memory, the window count per lane
 //   k_eddsa_verify    n verdicts S B == R + t A, t = H(R, A, M) computed here for the three schemes of eddsa.py
+//   k_eddsa_fill      n complete witness rows of the MiMC-EdDSA circuit, one field inversion per row (at the end of this file)
 #pragma once
 #include "bn254.hpp"
 #include "mimc.hpp"
@@ -297,6 +299,227 @@ k_eddsa_verify(EddsaView v, const fe *__restrict__ A, const fe *__restrict__ R, 
         jj_add(acc, tab[digit(t.l, j)].c, false);
     }
     verdicts[g] = equals_affine(acc, rx, ry) ? 1 : 0;
+}
+
+// ---- the complete witness of the MiMC-EdDSA circuit (ethsnarks_amd/jubjub_gadgets.py, eddsa_mimc_circuit): one lane per signature writes its
+// row of the device witness buffer.  FillLayout is zk_eddsa_layout of zkhip.h: the front end defines the row, the kernel takes every offset from
+// it.  The host has checked that the segments lie inside the row and do not overlap.
+//
+// ONE inversion per witness.  The circuit's point gadgets (PointDoubler, PointAdder) name the AFFINE result of every step of three chains: the
+// 253 doublings of A, the 253 additions of the variable-base multiplication, the 126 additions of the fixed-base one -- plus the three
+// doublings of the validator and the closing R + t A.  The lane walks every chain in extended coordinates (jj_dbl / jj_add: complete, so no
+// step has a special case) and parks (X, Y) of each step in the step's own x3, y3 slots, Z in its first slot and the running product of all
+// Z so far in its second.  After one jj_inv of the final product the steps are visited backwards (Montgomery's trick: 1 / Z_i = inverse *
+// prefix_i, inverse *= Z_i) and x3, y3 become affine; a last forward pass fills each gadget's products of affine inputs (alpha .. delta,
+// beta .. tau) and the conditional points.  The 1 / x of NotLowOrder's IsNonZero joins the same product (its Y and M slots hold the prefix and
+// the value).  Per witness, msg_len = 1: 14 816 field products, of which 381 are the inversion.
+struct FillLayout {
+    uint32_t msg_len, n_vars, ax_var, msg_var0, rx_var, s_bit0, iv_var, validator_var0, window_var0, fixed_adder_var0, mimc_var0, t_bit0,
+             t_range_var0, cond0_var, doubler_var0, cond_var0, adder_var0, step_stride, last_adder_var0;
+};
+constexpr uint32_t FB_WINDOWS = FIELD_BITS / 2, N_STEPS = FIELD_BITS - 1;   // 127 two-bit windows of s; 253 doubler / conditional / adder steps
+constexpr uint32_t DBL_VARS = 6, ADD_VARS = 7, VALIDATOR_VARS = 3 * DBL_VARS + 4, T_BITS_VARS = 3 * FIELD_BITS - 1, T_RANGE_VARS = 99;
+constexpr uint32_t MIMC_ROUND_VARS = 4 * merkle::MIMC_ROUNDS;
+
+ZK_HD uint32_t int_bit(const uint32_t *v, uint32_t i) { return (v[i >> 5] >> (i & 31)) & 1; }
+// bit i of r - 1 (r is odd: only the lowest limb differs from r's)
+ZK_HD uint32_t modulus_m1_bit(uint32_t i) {
+    const uint32_t limb = i < 32 ? FrParams::p(0) - 1 : i < 64 ? FrParams::p(1) : i < 96 ? FrParams::p(2) : i < 128 ? FrParams::p(3) : i < 160 ? FrParams::p(4)
+                        : i < 192 ? FrParams::p(5) : i < 224 ? FrParams::p(6) : FrParams::p(7);
+    return (limb >> (i & 31)) & 1;
+}
+ZK_HD fe bit_fe(uint32_t b) { return b ? Fr::one() : Fr::zero(); }
+
+// one step of a chain: park the projective point in the gadget's block of nv variables and take its Z into the running product
+ZK_JFN void park_point(fe *blk, uint32_t nv, const jpoint &p, fe &run) {
+    blk[nv - 2] = p.c[0]; blk[nv - 1] = p.c[1]; blk[0] = p.c[3]; blk[1] = run;
+    run = Fr::lmul(run, p.c[3]);
+}
+// the way back: inv = 1 / (the product up to and including this step) on entry, 1 / (the product before it) on return
+ZK_JFN void unpark_point(fe *blk, uint32_t nv, fe &inv) {
+    const fe zi = Fr::lmul(inv, blk[1]);
+    inv = Fr::lmul(inv, blk[0]);
+    blk[nv - 2] = Fr::canon(Fr::lmul(blk[nv - 2], zi));
+    blk[nv - 1] = Fr::canon(Fr::lmul(blk[nv - 1], zi));
+}
+// PointDoubler's alpha = x x, beta = y y, gamma = d alpha beta, delta = 2 x y
+ZK_JFN void fill_doubler(fe *blk, const fe &x, const fe &y) {
+    const fe al = Fr::lmul(x, x), be = Fr::lmul(y, y), xy = Fr::lmul(x, y);
+    blk[0] = Fr::canon(al); blk[1] = Fr::canon(be);
+    blk[2] = Fr::canon(Fr::lmul(Fr::lmul(coef_d(), al), be));
+    blk[3] = Fr::canon(Fr::ldbl(xy));
+}
+// PointAdder's beta = x1 y2, gamma = y1 x2, delta = y1 y2, epsilon = x1 x2, tau = delta epsilon
+ZK_JFN void fill_adder(fe *blk, const fe &x1, const fe &y1, const fe &x2, const fe &y2) {
+    const fe de = Fr::lmul(y1, y2), ep = Fr::lmul(x1, x2);
+    blk[0] = Fr::canon(Fr::lmul(x1, y2)); blk[1] = Fr::canon(Fr::lmul(y1, x2));
+    blk[2] = Fr::canon(de); blk[3] = Fr::canon(ep);
+    blk[4] = Fr::canon(Fr::lmul(de, ep));
+}
+// one element through the cipher with its 91 x (a, b, c, d) stored (MiMCe7_round: a = t^2, b = a^2, c = a b, d = c t, the last d + k); E_k(x) + k
+ZK_JFN fe mimc_cipher_rounds(const fe *__restrict__ rc, const fe &x0, const fe &k, fe *rounds) {
+    fe x = x0;
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0; i < merkle::MIMC_ROUNDS; i++) {
+        const fe t = Fr::ladd(Fr::ladd(x, k), rc[i]);
+        const fe a = Fr::lmul(t, t), b = Fr::lmul(a, a), c = Fr::lmul(a, b);
+        x = Fr::lmul(c, t);
+        if (i == merkle::MIMC_ROUNDS - 1) x = Fr::ladd(x, k);
+        fe *o = rounds + 4 * i;
+        o[0] = Fr::canon(a); o[1] = Fr::canon(b); o[2] = Fr::canon(c); o[3] = Fr::canon(x);
+    }
+    return x;
+}
+
+// fbtab: FB_WINDOWS x 4 entries (x, y, d x y) of m 4^i B, m = 0 .. 3 (m = 0: the identity), canonical Montgomery.  s: any 256-bit integer.
+// A or R off the curve or s >= 2^254: verdict 0 and the row is not touched.  Otherwise the whole row, and verdict = (lhs == rhs)
+__global__ void __launch_bounds__(BLOCK)
+k_eddsa_fill(EddsaView v, const fe *__restrict__ fbtab, FillLayout L, const fe *__restrict__ A, const fe *__restrict__ R, const fe *__restrict__ s,
+             const fe *__restrict__ msgs, uint32_t n, fe *d_w, uint64_t row_elems, uint8_t *__restrict__ verdicts) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    fe ax, ay, rx, ry;
+    load_point(A, g, ax, ay);
+    load_point(R, g, rx, ry);
+    const uint32_t *__restrict__ sw = s[g].l;
+    if (!on_curve(ax, ay) || !on_curve(rx, ry) || (sw[7] >> 30)) { verdicts[g] = 0; return; }
+    ax = Fr::canon(ax); ay = Fr::canon(ay); rx = Fr::canon(rx); ry = Fr::canon(ry);
+    fe *row = d_w + (size_t)g * row_elems;
+    const uint32_t n_hash = 4 + L.msg_len;
+
+    // ---- the inputs
+    row[0] = Fr::one();
+    row[L.ax_var] = ax; row[L.ax_var + 1] = ay; row[L.rx_var] = rx; row[L.rx_var + 1] = ry;
+    row[L.iv_var] = Fr::zero();
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0; i < FIELD_BITS; i++) row[L.s_bit0 + i] = bit_fe(int_bit(sw, i));
+
+    // ---- t = the hash, its rounds stored; outputs[i] = key + E_key(x_i) + key + x_i
+    fe k = Fr::zero();
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0; i < n_hash; i++) {
+        fe xi;
+        if (i < 4) xi = i == 0 ? rx : i == 1 ? ry : i == 2 ? ax : ay;
+        else { xi = Fr::canon(jj_to_mont(msgs[(size_t)g * L.msg_len + (i - 4)])); row[L.msg_var0 + (i - 4)] = xi; }
+        const fe e = mimc_cipher_rounds(v.rc, xi, k, row + L.mimc_var0 + n_hash + (size_t)i * MIMC_ROUND_VARS);
+        k = Fr::ladd(Fr::ladd(k, xi), e);
+        row[L.mimc_var0 + i] = Fr::canon(k);
+    }
+    const fe t = jj_from_mont(k);                               // the canonical integer: its bits are the canonical decomposition
+    {
+        fe *tb = row + L.t_bit0, *res = tb + FIELD_BITS, *cmp = res + (FIELD_BITS - 1);
+        uint32_t run = 1, eq = int_bit(t.l, FIELD_BITS - 1), slot = 0;
+#pragma clang loop unroll(disable)
+        for (int i = FIELD_BITS - 1; i >= 0; i--) {             // from the top bit down
+            const uint32_t b = int_bit(t.l, i), c = modulus_m1_bit(i) ? 1u : b;
+            tb[i] = bit_fe(b); cmp[i] = bit_fe(c);
+            run &= c;
+            if (i < (int)FIELD_BITS - 1) res[i] = bit_fe(run);  // results[i] = comparisons[i] * results[i + 1] (results[253] = comparisons[253])
+            if (i < (int)FIELD_BITS - 1 && i > 0 && modulus_m1_bit(i)) { eq &= b; row[L.t_range_var0 + slot++] = bit_fe(eq); }
+        }
+    }
+
+    // ---- the chains, projective
+    fe run = Fr::one();
+    jpoint p;
+    fe *val = row + L.validator_var0;
+    from_affine(p, rx, ry);
+#pragma clang loop unroll(disable)
+    for (uint32_t j = 0; j < 3; j++) { jj_dbl(p, false); park_point(val + DBL_VARS * j, DBL_VARS, p, run); }
+    {                                                           // IsNonZero(x of 8 R): Y holds the prefix, M the value (1 in the place of 0)
+        const bool nz = !Fr::is_zero(Fr::canon(p.c[0]));
+        const fe x8 = nz ? p.c[0] : Fr::one();
+        val[3 * DBL_VARS] = run; val[3 * DBL_VARS + 1] = x8;
+        run = Fr::lmul(run, x8);
+    }
+    {                                                           // fixed base: window i adds entry (s >> 2 i) & 3 of its row
+        const fe *e = fbtab + 3 * (size_t)(int_bit(sw, 0) | (int_bit(sw, 1) << 1));
+        row[L.window_var0] = e[0]; row[L.window_var0 + 1] = e[1];
+        from_affine(p, e[0], e[1]);
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 1; i < FB_WINDOWS; i++) {
+            e = fbtab + 3 * ((size_t)4 * i + (int_bit(sw, 2 * i) | (int_bit(sw, 2 * i + 1) << 1)));
+            row[L.window_var0 + 2 * i] = e[0]; row[L.window_var0 + 2 * i + 1] = e[1];
+            jj_add(p, e, true);
+            park_point(row + L.fixed_adder_var0 + ADD_VARS * (size_t)(i - 1), ADD_VARS, p, run);
+        }
+    }
+    {                                                           // variable base: D = 2^i A, S += bit_i ? D : identity (the same instructions either way)
+        jpoint d;
+        from_affine(d, ax, ay);
+        const uint32_t b0 = int_bit(t.l, 0);
+        row[L.cond0_var] = b0 ? ax : Fr::zero(); row[L.cond0_var + 1] = b0 ? ay : Fr::one();
+        from_affine(p, row[L.cond0_var], row[L.cond0_var + 1]);
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 1; i <= N_STEPS; i++) {
+            const size_t off = (size_t)(i - 1) * L.step_stride;
+            jj_dbl(d, true);
+            park_point(row + L.doubler_var0 + off, DBL_VARS, d, run);
+            const bool b = int_bit(t.l, i);
+            fe q[4];
+            q[0] = b ? d.c[0] : Fr::zero(); q[1] = b ? d.c[1] : Fr::one(); q[2] = b ? jj_mul(coef_d(), d.c[2]) : Fr::zero(); q[3] = b ? d.c[3] : Fr::one();
+            jj_add(p, q, false);
+            park_point(row + L.adder_var0 + off, ADD_VARS, p, run);
+        }
+        fe q[3];                                                // rhs = R + t A
+        q[0] = rx; q[1] = ry; q[2] = jj_mul(coef_d(), jj_mul(rx, ry));
+        jj_add(p, q, true);
+        park_point(row + L.last_adder_var0, ADD_VARS, p, run);
+    }
+
+    // ---- one inversion, then the way back
+    fe inv = jj_inv(run);
+    unpark_point(row + L.last_adder_var0, ADD_VARS, inv);
+#pragma clang loop unroll(disable)
+    for (uint32_t i = N_STEPS; i >= 1; i--) {
+        const size_t off = (size_t)(i - 1) * L.step_stride;
+        unpark_point(row + L.adder_var0 + off, ADD_VARS, inv);
+        unpark_point(row + L.doubler_var0 + off, DBL_VARS, inv);
+    }
+#pragma clang loop unroll(disable)
+    for (uint32_t i = FB_WINDOWS - 1; i >= 1; i--) unpark_point(row + L.fixed_adder_var0 + ADD_VARS * (size_t)(i - 1), ADD_VARS, inv);
+    {
+        fe *blk8 = val + 2 * DBL_VARS;                          // still projective: X, Y at [4], [5], Z at [0]
+        const bool nz = !Fr::is_zero(Fr::canon(blk8[4]));
+        const fe xi = Fr::lmul(inv, val[3 * DBL_VARS]);         // 1 / X (or 1 / 1)
+        inv = Fr::lmul(inv, val[3 * DBL_VARS + 1]);
+        val[3 * DBL_VARS] = bit_fe(nz);
+        val[3 * DBL_VARS + 1] = nz ? Fr::canon(Fr::lmul(blk8[0], xi)) : Fr::zero();   // 1 / x = Z / X
+    }
+#pragma clang loop unroll(disable)
+    for (int j = 2; j >= 0; j--) unpark_point(val + DBL_VARS * j, DBL_VARS, inv);
+
+    // ---- the products of affine inputs
+    fill_doubler(val, rx, ry);
+    fill_doubler(val + DBL_VARS, val[4], val[5]);
+    fill_doubler(val + 2 * DBL_VARS, val[DBL_VARS + 4], val[DBL_VARS + 5]);
+    val[3 * DBL_VARS + 2] = Fr::canon(jj_mul(rx, rx)); val[3 * DBL_VARS + 3] = Fr::canon(jj_mul(ry, ry));
+    {
+        const fe *prev = row + L.window_var0;                   // adder i: (window 0 | the previous sum) + window i + 1
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 0; i + 1 < FB_WINDOWS; i++) {
+            fe *blk = row + L.fixed_adder_var0 + ADD_VARS * (size_t)i;
+            const fe *w = row + L.window_var0 + 2 * (size_t)(i + 1);
+            fill_adder(blk, prev[0], prev[1], w[0], w[1]);
+            prev = blk + ADD_VARS - 2;
+        }
+    }
+    {
+        const fe *dprev = row + L.ax_var, *sprev = row + L.cond0_var;
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 1; i <= N_STEPS; i++) {
+            const size_t off = (size_t)(i - 1) * L.step_stride;
+            fe *dbl = row + L.doubler_var0 + off, *cond = row + L.cond_var0 + off, *add = row + L.adder_var0 + off;
+            fill_doubler(dbl, dprev[0], dprev[1]);
+            const bool b = int_bit(t.l, i);
+            cond[0] = b ? dbl[4] : Fr::zero(); cond[1] = b ? dbl[5] : Fr::one();
+            fill_adder(add, sprev[0], sprev[1], cond[0], cond[1]);
+            dprev = dbl + DBL_VARS - 2; sprev = add + ADD_VARS - 2;
+        }
+        fill_adder(row + L.last_adder_var0, rx, ry, sprev[0], sprev[1]);
+    }
+    const fe *lhs = row + L.fixed_adder_var0 + ADD_VARS * (size_t)(FB_WINDOWS - 2) + ADD_VARS - 2, *rhs = row + L.last_adder_var0 + ADD_VARS - 2;
+    verdicts[g] = Fr::eq(lhs[0], rhs[0]) && Fr::eq(lhs[1], rhs[1]) ? 1 : 0;
 }
 
 }  // namespace jubjub

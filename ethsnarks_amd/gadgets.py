@@ -220,11 +220,11 @@ class MiMCe7Round:
 
 
 class MiMCe7Gadget:
-    """MiMC_gadget<MiMCe7_round>, src/gadgets/mimc.hpp:186-275"""
+    """MiMC_gadget<MiMCe7_round>, src/gadgets/mimc.hpp:186-275.  constants: the round constants of another seed (default: those of "mimc")"""
 
-    def __init__(self, pb, x, k):
+    def __init__(self, pb, x, k, constants=None):
         self.rounds = []
-        cs = _consts()
+        cs = _consts() if constants is None else constants
         for i, C in enumerate(cs):
             rx = x if i == 0 else self.rounds[-1].result()
             self.rounds.append(MiMCe7Round(pb, rx, k, C, i == len(cs) - 1))
@@ -242,15 +242,15 @@ class MiMCe7Gadget:
 
 
 class MiMCe7HashGadget:
-    """MiyaguchiPreneel_OWF<MiMC_e7_gadget>, src/gadgets/onewayfunction.hpp:67-127"""
+    """MiyaguchiPreneel_OWF<MiMC_e7_gadget>, src/gadgets/onewayfunction.hpp:67-127.  constants: as MiMCe7Gadget"""
 
-    def __init__(self, pb, iv, messages):
+    def __init__(self, pb, iv, messages, constants=None):
         self.pb, self.iv, self.messages = pb, iv, list(messages)
         self.outputs = pb.allocate_array(len(self.messages))
         self.ciphers = []
         for i, m in enumerate(self.messages):
             key = iv if i == 0 else self.outputs[i - 1]
-            self.ciphers.append(MiMCe7Gadget(pb, m, key))
+            self.ciphers.append(MiMCe7Gadget(pb, m, key, constants))
 
     def result(self):
         return self.outputs[-1]

@@ -5,12 +5,16 @@ The native surface of the reference's ethsnarks/jubjub.py, pedersen.py and eddsa
 the identity is (0, 1).  All curve arithmetic of a call runs in one HIP kernel launch; there is no CPU path and no signer.  A point that is not on
 the curve raises ZkError (ZK_ERR_ARG) in scalar_mul / point_add / point_double / point_neg and as a base point, and gives the verdict False as
 the A or R of a signature -- the reference never checks and divides by zero there; everything on the curve behaves as the reference does.
+
+EdDSAVerifier("mimc").circuit() is the R1CS that proves such a signature (jubjub_gadgets.eddsa_mimc_circuit) and fill_witnesses writes the
+complete witness rows of a batch into the device buffer that ProverContext.submit_batch(device_ptr=...) proves from.  There is no signer.
 """
 import ctypes as C
 
 import numpy as np
 
 from . import fields as F
+from . import jubjub_gadgets as JG
 from . import prover as P
 
 JUBJUB_Q = F.FR
@@ -24,7 +28,12 @@ IDENTITY = (0, 1)
 SCHEMES = {"mimc": 0, "pure": 1, "hash": 2}                     # ZK_EDDSA_*
 _OPS = {"add": 0, "double": 1, "negate": 2}                     # ZK_JJ_OP_*
 _SYMBOLS = ("zk_jj_hash_to_point", "zk_jj_pedersen_basepoint", "zk_jj_point_op", "zk_jj_scalar_mul", "zk_pedersen_create", "zk_pedersen_free",
-            "zk_pedersen_hash", "zk_pedersen_table", "zk_eddsa_create", "zk_eddsa_free", "zk_eddsa_verify_batch")
+            "zk_pedersen_hash", "zk_pedersen_table", "zk_eddsa_create", "zk_eddsa_free", "zk_eddsa_verify_batch", "zk_eddsa_fill_witnesses")
+
+
+class EddsaLayout(C.Structure):
+    """zk_eddsa_layout: where the segments of a witness row of the MiMC-EdDSA circuit start (jubjub_gadgets.EddsaLayout, field for field)"""
+    _fields_ = [(n, C.c_uint32) for n in JG.LAYOUT_FIELDS]
 
 
 def generator():
@@ -49,6 +58,7 @@ def _lib():
     lib.zk_eddsa_free.argtypes = [C.c_void_p]
     lib.zk_eddsa_free.restype = None
     lib.zk_eddsa_verify_batch.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p]
+    lib.zk_eddsa_fill_witnesses.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     return lib
 
 
@@ -213,6 +223,8 @@ class EdDSAVerifier:
         self._lib = _lib()
         self.scheme = scheme
         self.msg_len = int(msg_len)
+        self.B = (int(B[0]), int(B[1])) if B is not None else None
+        self._circuit = None
         self._h = C.c_void_p()
         b = _point_limbs([B]) if B is not None else None
         P._check(self._lib.zk_eddsa_create(SCHEMES[scheme], _ptr(b) if b is not None else None, self.msg_len, int(device), C.byref(self._h)))
@@ -230,18 +242,62 @@ class EdDSAVerifier:
     def __exit__(self, *a):
         self.close()
 
-    def verify(self, A, sigs, msgs):
-        """A: one public key per signature (or a single point for all); sigs: [(R, s), ..]; msgs: bytes objects (lists of ints for "mimc")"""
+    def _items(self, A, sigs, msgs):
         sigs = list(sigs)
         n = len(sigs)
-        if n == 0:
-            return []
         A = list(A)
         if len(A) == 2 and not isinstance(A[0], (tuple, list)):
             A = [tuple(A)] * n
         msgs = list(msgs)
         if len(A) != n or len(msgs) != n:
             raise ValueError("A, sigs and msgs differ in length")
+        return A, sigs, msgs, n
+
+    def _circuit_object(self):
+        if self.scheme != "mimc":
+            raise NotImplementedError('only the "mimc" scheme has a circuit; the Pedersen hash of "%s" has no gadget here' % self.scheme)
+        if self._circuit is None:
+            self._circuit = JG.EddsaMimcCircuit(self.msg_len, self.B)
+        return self._circuit
+
+    def circuit(self):
+        """(R1CS, layout) of the circuit that accepts this verifier's signatures: jubjub_gadgets.eddsa_mimc_circuit for its msg_len and B.  Public
+        inputs: A.x, A.y, the message elements.  layout: a jubjub_gadgets.EddsaLayout; a witness row has layout.n_vars + 1 elements"""
+        c = self._circuit_object()
+        return c.r1cs(), c.layout
+
+    def fill_witnesses(self, A, sigs, msgs, out=None, row_elems=None, layout=None):
+        """The complete witness rows of the circuit for a batch, written on the device, Montgomery, ready for submit_batch(device_ptr=...):
+        row i of `out` (a prover.DeviceBuffer or a device address; None: a new DeviceBuffer) belongs to signature i.  Returns (verdicts, out).
+        A wrong signature still gets its row (only the two closing constraints fail; the prover refuses a batch that holds it: ZK_ERR_DEGREE); an item with A or R off the curve or s >= 2^254 gets the
+        verdict False and its row is left as it was.  s may be any integer below 2^256.  A, sigs, msgs as verify()"""
+        c = self._circuit_object()
+        A, sigs, msgs, n = self._items(A, sigs, msgs)
+        lay = c.layout if layout is None else layout
+        if row_elems is None:
+            row_elems = lay.n_vars + 1
+        if any(len(m) != self.msg_len for m in msgs):
+            raise ValueError("a message does not have msg_len elements")
+        if out is None:
+            out = P.DeviceBuffer(32 * int(row_elems) * max(n, 1))
+        if isinstance(out, P.DeviceBuffer) and n * int(row_elems) * 32 > out.nbytes:
+            raise ValueError("the device buffer is smaller than n rows")
+        ptr = out.ptr if isinstance(out, P.DeviceBuffer) else int(out)
+        a = _point_limbs(A)
+        r = _point_limbs([R for R, _ in sigs])
+        s = F.ints_to_limbs([int(v) for _, v in sigs]) if n else np.zeros((0, 4), dtype=np.uint64)
+        m = F.ints_to_limbs([int(v) for msg in msgs for v in msg]) if n else np.zeros((0, 4), dtype=np.uint64)
+        verdicts = np.full(max(n, 1), 255, dtype=np.uint8)
+        P._check(self._lib.zk_eddsa_fill_witnesses(self._h, _ptr(a), _ptr(r), _ptr(s), _ptr(m), n, C.c_void_p(ptr), C.c_uint64(int(row_elems)),
+                                                   C.byref(EddsaLayout(*lay)), _ptr(verdicts)))
+        return [bool(v) for v in verdicts[:n]], out
+
+    def verify(self, A, sigs, msgs):
+        """A: one public key per signature (or a single point for all); sigs: [(R, s), ..]; msgs: bytes objects (lists of ints for "mimc")"""
+        sigs = list(sigs)
+        if len(sigs) == 0:
+            return []
+        A, sigs, msgs, n = self._items(A, sigs, msgs)
         a = _point_limbs(A)
         r = _point_limbs([R for R, _ in sigs])
         s = F.ints_to_limbs([int(v) for _, v in sigs])

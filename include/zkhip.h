@@ -62,9 +62,11 @@ extern "C" {
  * 4: the Poseidon entry points (zk_poseidon_*, zk_mtree_create_ex, zk_mtree_info); zk_mtree_paths returns width - 1 siblings per level.
  * 5: Baby JubJub (zk_jj_*, zk_pedersen_*, zk_eddsa_*).
  * 6: zk_mtree_fill_full_witnesses.
+ * 7: zk_wplan_probe_program.
+ * 8: zk_eddsa_fill_witnesses and zk_eddsa_layout.
  * A client checks zk_abi_version() == ZK_ABI_VERSION once after loading the library, or passes the size of the zk_config
  * it was compiled with to zk_ctx_create_sized (members it does not know read as 0 = their defaults). */
-#define ZK_ABI_VERSION 7
+#define ZK_ABI_VERSION 8
 
 typedef struct zk_pk zk_pk;
 typedef struct zk_vk zk_vk;
@@ -465,6 +467,21 @@ int zk_poseidon_permute(uint64_t *states /* n x 6 x 4, in place */, uint32_t n, 
  *                              (EdDSA: as pure with M = the x of pedersen_hash_bytes("EdDSA_Verify.M", msg)).  B == NULL: the generator
  *   zk_eddsa_verify_batch      verdicts[i] = (s[i] B == R[i] + t A[i]); A, R: n x 8, s: n x 4, msgs: n x msg_len bytes (n x msg_len x 4 limbs for
  *                              ZK_EDDSA_MIMC).  t is computed on the device
+ *   zk_eddsa_fill_witnesses    (ZK_EDDSA_MIMC only) for each of n signatures the COMPLETE witness row of the MiMC-EdDSA circuit -- eddsa_mimc_circuit of
+ *                              ethsnarks_amd/jubjub_gadgets.py: PointValidator(R), fixed_base_mul(B, the 254 bits of s), the MiMC hash, field2bits_strict
+ *                              and a range check of the bits of t, ScalarMult(A, bits of t), PointAdder(R, t A), lhs == rhs -- into row i of a device
+ *                              buffer (row_elems Fr elements apart), canonical Montgomery: what zk_wplan_solve leaves and
+ *                              zk_prove_batch_submit_resident reads, every element equal to the front end's generate_r1cs_witness.  The front
+ *                              end defines the row: zk_eddsa_layout names the variable index of the first element of every segment (and the
+ *                              stride of the 253 doubler / conditional / adder steps), n_vars + 1 elements in all; the kernel computes no offset
+ *                              of its own.  verdicts[i] is what zk_eddsa_verify_batch answers for the item.  A WELL-FORMED WRONG signature gets
+ *                              its full row and verdict 0: only the two closing equalities fail.  A MALFORMED item -- A or R off the curve, or
+ *                              s >= 2^254 (s is ANY 256-bit integer here, not required to be below r) -- gets verdict 0 and its row is NOT
+ *                              TOUCHED.  An R of low order gets its row and the verifier's verdict, but the circuit's PointValidator rejects it.
+ *                              ZK_ERR_ARG and nothing written: another scheme, layout.msg_len != the verifier's, n_vars + 1 > row_elems, a
+ *                              segment outside variables 1 .. n_vars or overlapping another, a coordinate or message element >= r.
+ *                              One lane per signature walks the three point chains (253 doublings of A, 253 + 126 additions) projectively and
+ *                              pays ONE field inversion per witness, whatever the number of bits (csrc/jubjub.hpp)
  * A zk_pedersen and a zk_eddsa are single-threaded like a zk_ctx; their work runs on a stream of their own and is complete when a call returns. */
 #define ZK_JJ_OP_ADD 0
 #define ZK_JJ_OP_DOUBLE 1
@@ -485,6 +502,16 @@ int zk_pedersen_table(const zk_pedersen *h, uint32_t first_window, uint32_t n_wi
 int zk_eddsa_create(int scheme, const uint64_t *B /* 8 limbs, or NULL */, uint32_t msg_len, int device, zk_eddsa **out);
 void zk_eddsa_free(zk_eddsa *v);
 int zk_eddsa_verify_batch(zk_eddsa *v, const uint64_t *A, const uint64_t *R, const uint64_t *s, const void *msgs, uint32_t n, uint8_t *verdicts /* n */);
+/* first variable of each segment of a witness row (variable 0 is ONE): A.x, A.y | msg_len message elements | R.x, R.y | 254 bits of s | the zero IV |
+ * validator: 3 x 6 doubler variables, Y, M, xx, yy | 127 x (x, y) window lookups | 126 x 7 fixed-base adder variables | 4 + msg_len hash outputs, then
+ * (4 + msg_len) x 91 x (a, b, c, d) | 254 bits of t, 253 results, 254 comparisons | 99 range-check products | conditionals[0] (2) | per step
+ * i = 1 .. 253 at + (i - 1) step_stride: 6 doubler, 2 conditional, 7 adder variables | the 7 variables of the last adder */
+typedef struct {
+    uint32_t msg_len, n_vars, ax_var, msg_var0, rx_var, s_bit0, iv_var, validator_var0, window_var0, fixed_adder_var0, mimc_var0, t_bit0,
+             t_range_var0, cond0_var, doubler_var0, cond_var0, adder_var0, step_stride, last_adder_var0;
+} zk_eddsa_layout;
+int zk_eddsa_fill_witnesses(zk_eddsa *v, const uint64_t *A /* n x 8 */, const uint64_t *R /* n x 8 */, const uint64_t *s /* n x 4 */, const uint64_t *msgs /* n x msg_len x 4 */,
+                            uint32_t n, void *d_w, uint64_t row_elems, const zk_eddsa_layout *layout, uint8_t *verdicts /* n */);
 
 /* ---- measurement aids (bench.py): kernel launches issued by this library so far; between zk_profile_begin() and
  * zk_profile_end() every launch is bracketed by a HIP event pair on its own stream -- the sum of the kernel durations

@@ -1,0 +1,104 @@
+"""The witness fill of the MiMC-EdDSA circuit (zk_eddsa_fill_witnesses, csrc/jubjub.hpp k_eddsa_fill) on the device: kernel time by the library's
+event pairs after a warm-up call at n = 1, 32, 1 024 and 2^14, the field products per witness from the formulas, the fraction of a product-chain
+rate (tools/mulbench, "mul chain 8 waves/SIMD", passed as --chain in G/s) that the kernel reaches, the time of submit_batch + collect for the
+same k on the same circuit, and the front end's generate_r1cs_witness per signature on the CPU.  Prints the table and, with --out, also writes it to that file: profiles/eddsa_circuit.txt is such a run.
+
+    python tools/eddsa_circuit_bench.py --chain 142.4 --out profiles/eddsa_circuit.txt
+"""
+import argparse
+import os
+import random
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+from ethsnarks_amd import fields as F, jubjub as J, prover as P   # noqa: E402
+import jubjub_cases as JC                                         # noqa: E402
+
+INV = 254 + bin(F.FR - 2).count("1")                               # jj_inv: a squaring per bit, a product per set bit
+DBL, DBL_T, ADD, MIXED, CURVE = 8, 9, 10, 9, 5
+
+
+def products(msg_len):
+    """field products of one lane of k_eddsa_fill, part by part"""
+    steps, fixed, parked = 253, 126, 3 + 126 + 2 * 253 + 1
+    return {
+        "inputs: conversions, two curve equations": 4 + 2 * CURVE + msg_len,
+        "MiMC, (4 + m) x 91 x 4, and t": (4 + msg_len) * 91 * 4 + 1,
+        "validator: three doublings, x of 8 R": 1 + 3 * (DBL + 1) + 1,
+        "fixed base: 126 mixed additions": 1 + fixed * (MIXED + 1),
+        "variable base: 253 x (doubling, d T, addition), R + t A": 2 + steps * (DBL_T + 1 + 1 + ADD + 1) + 2 + MIXED + 1,
+        "the inversion": INV,
+        "the way back: 4 per parked point, 3 for 1 / x": 4 * parked + 3,
+        "gadget products: 5 per doubler, 5 per adder, xx, yy": 5 * (3 + steps) + 5 * (fixed + steps + 1) + 2,
+    }
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--chain", type=float, required=True, help="product-chain rate of the same session in G products/s")
+    ap.add_argument("--sizes", type=int, nargs="*", default=[1, 32, 1024, 1 << 14])
+    ap.add_argument("--prove-up-to", type=int, default=32, help="largest k that is also proven (submit_batch + collect)")
+    ap.add_argument("--msg-len", type=int, default=1)
+    ap.add_argument("--out", help="also write every printed line to this file")
+    a = ap.parse_args()
+    out = open(a.out, "w") if a.out else None
+
+    def emit(line):
+        print(line, flush=True)
+        if out:
+            out.write(line + "\n")
+            out.flush()
+    L = J._lib()
+    parts = products(a.msg_len)
+    total = sum(parts.values())
+    emit("%s, chain rate %.2f G products/s, msg_len %d" % (L.zk_version().decode(), a.chain, a.msg_len))
+    for label, v in parts.items():
+        emit("    %6d  %s" % (v, label))
+    emit("    %6d  products per witness, %d inversion" % (total, 1))
+    prng = random.Random(8)
+    signed = [JC.sign("mimc", JC.make_msg("mimc", a.msg_len, prng), prng.randrange(1, JC.L)) for _ in range(32)]
+    signed = [(A, (R, s % (1 << 254)), m) for A, (R, s), m in signed]
+    with J.EdDSAVerifier("mimc", msg_len=a.msg_len) as v:
+        r, lay = v.circuit()
+        c = v._circuit
+        t0 = time.perf_counter()
+        for A, (R, s), m in signed[:8]:
+            c.assign(A, R, s, m)
+        t_front = (time.perf_counter() - t0) / 8
+        emit("circuit: %d variables, %d constraints, domain 2^%d, a row of %.1f KB; the front end's generate_r1cs_witness: %.1f ms per signature on the CPU"
+              % (r.V, r.nC, r.domain_size.bit_length() - 1, 32 * (r.V + 1) / 1024, 1e3 * t_front))
+        pk, _ = P.keygen(r, seed=41)
+        for n in a.sizes:
+            items = [signed[i % 32] for i in range(n)]
+            A, sigs, msgs = [x[0] for x in items], [x[1] for x in items], [x[2] for x in items]
+            buf = P.DeviceBuffer(32 * (r.V + 1) * n)
+            verdicts, _ = v.fill_witnesses(A, sigs, msgs, buf)           # warm-up: code object, scratch
+            P.profile_begin()
+            t0 = time.perf_counter()
+            verdicts, _ = v.fill_witnesses(A, sigs, msgs, buf)
+            wall = 1e3 * (time.perf_counter() - t0)
+            ms, launches, _ = P.profile_end()
+            rate = n * total / (ms * 1e-3) / 1e9
+            line = "fill n = %6d: kernel %9.3f ms (%d launch), call %9.3f ms, %9.0f witnesses/s, %6.2f G products/s = %.3f of the chain rate" % (
+                n, ms, launches, wall, n / (ms * 1e-3), rate, rate / a.chain)
+            assert sum(verdicts) == sum(JC.verify("mimc", x[0], x[1], x[2]) for x in items[:32]) * (n // 32) + sum(
+                JC.verify("mimc", x[0], x[1], x[2]) for x in items[:n % 32])
+            if n <= a.prove_up_to:
+                ctx = P.ProverContext(pk, r, max_batch=n)
+                ctx.submit_batch(None, device_ptr=buf.ptr, k=n)
+                ctx.collect_batch(n)                                     # warm-up
+                t0 = time.perf_counter()
+                ctx.submit_batch(None, device_ptr=buf.ptr, k=n)
+                ctx.collect_batch(n)
+                line += "; submit_batch + collect %9.3f ms" % (1e3 * (time.perf_counter() - t0))
+                ctx.close()
+            emit(line)
+            buf.free()
+    if out:
+        out.close()
+
+
+if __name__ == "__main__":
+    main()
