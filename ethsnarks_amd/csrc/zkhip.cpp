@@ -24,6 +24,7 @@
 #include "msm.hpp"
 #include "keygen.hpp"
 #include "blind.hpp"
+#include "hlagrange.hpp"
 #include "../../include/zkhip.h"
 #include <errno.h>
 #include <sys/random.h>
@@ -599,6 +600,18 @@ template <class T> int dev_upload(T **dst, const T *src, size_t n) {
     return ZK_OK;
 }
 struct Range { uint32_t lo, hi; uint32_t n() const { return hi - lo; } };
+uint64_t csr_hash(const zk_csr *m, uint32_t a, uint32_t b, uint32_t c) {          // FNV-style hash over the words of the matrix and the circuit's shape
+    uint64_t h = 1469598103934665603ull;
+    auto eat = [&](const void *p, size_t n) {            // n: a multiple of 4; one multiplication per 32-bit word
+        const uint32_t *q = (const uint32_t *)p;
+        for (size_t i = 0; i < n / 4; i++) { h ^= q[i]; h *= 1099511628211ull; h ^= h >> 29; }
+    };
+    const uint32_t shape[4] = {m->n_rows, a, b, c};
+    eat(shape, sizeof(shape));
+    const uint32_t nnz = m->row_ptr[m->n_rows];
+    eat(m->row_ptr, 4 * (size_t)(m->n_rows + 1)); eat(m->col, 4 * (size_t)nnz); eat(m->coeff, 32 * (size_t)nnz);
+    return h;
+}
 Range shard_range(uint32_t n, uint32_t rank, uint32_t count) {
     return Range{(uint32_t)((uint64_t)n * rank / count), (uint32_t)((uint64_t)n * (rank + 1) / count)};
 }
@@ -629,6 +642,12 @@ struct DeviceTables {
     uint32_t cW = 0;                                   // window bits of the shared witness sort and of the tables it drives
     uint32_t plog = 0;                                 // memory-frugal tables: every 2^plog-th window only (MsmShape::plog); 0 = all W windows
     uint64_t table_bytes = 0, full_table_bytes = 0;    // what the four tables take, and what they would take with every window
+    // the H-query in coset-Lagrange bases (hlagrange.hpp): tH holds the m bases Q_j and tL the V + 1 bases L_v - K_v instead of
+    // the key's H- and L-query.  They depend on the circuit's C matrix as well as on the key: `circ` (a hash of it) is part of what a context
+    // looks its tables up by.  lag_req: what the contexts of this set asked for (a set whose tables came out frugal proves in the key's bases)
+    bool lag_req = false, lag = false;
+    uint64_t circ = 0;
+    double lag_ms = 0;                                 // what the transform of the bases took, once (zk_ctx_hlagrange_info)
     bool key_alive = true;                             // false once zk_pk_free has run: the last context to go takes the tables along
     int refs = 0;
     // device memory of the set; leaves the caller's current device as it found it (zk_pk_free runs this from wherever the
@@ -659,6 +678,85 @@ int build_table(typename C::Affine **out, const typename C::Affine *host_bases, 
     if (rc == ZK_OK) { *out = tmp.table; tmp.owns_table = false; }      // keep the table, drop the rest
     tmp.release();
     return rc;
+}
+// the same expansion of bases that already lie in device memory
+template <class C>
+int build_table_dev(typename C::Affine **out, const typename C::Affine *d_bases, uint32_t n, uint32_t cbits, uint32_t plog = 0) {
+    MsmWork<C> tmp;
+    tmp.sh.set(n ? n : 1, cbits, 1, plog);
+    tmp.table_n = n;
+    int rc = ZK_OK;
+    if (hipMalloc(&tmp.table, sizeof(typename C::Affine) * (size_t)(n ? n : 1) * tmp.sh.rows()) != hipSuccess) { (void)hipGetLastError(); rc = fail_msg(ZK_ERR_NOMEM, "out of device memory for the window-multiple tables"); }
+    if (rc == ZK_OK) rc = tmp.precompute(d_bases, n, nullptr);
+    if (rc == ZK_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(ZK_ERR_HIP, "k_msm_precompute failed");
+    if (rc == ZK_OK) { *out = tmp.table; tmp.owns_table = false; }
+    tmp.release();
+    return rc;
+}
+struct DevScratch {                                     // device buffers of one construction step, released with it
+    std::vector<void *> p;
+    template <class T> int get(T **out, size_t n) { ZK_HIP(hipMalloc(out, sizeof(T) * (n ? n : 1))); p.push_back(*out); return ZK_OK; }
+    template <class T> int put(T **out, const T *src, size_t n) { ZK_TRY(get(out, n)); if (n) ZK_HIP(hipMemcpy(*out, src, sizeof(T) * n, hipMemcpyHostToDevice)); return ZK_OK; }
+    ~DevScratch() { for (void *q : p) hipFree(q); }
+};
+// The bases of the four-transform prover (hlagrange.hpp): d_q[0 .. m) = Q_j and d_lk[0 .. V] = L_v - K_v, affine, in device memory
+// of the caller.  H: the key's m - 1 H-query bases, L: its V - nIn L-query bases (host), Cm: the circuit's C matrix.
+// d_lk[v] = L_v - K_v for v <= V, K_v = sum_j C[j][v] Lambda_j: d_lam the m bases Lambda_j (device), L the V - nIn L-query bases (host)
+int hl_column_bases(const G1::Affine *d_lam, const G1::Affine *L, const zk_csr *Cm, uint32_t nIn, uint32_t V, G1::Affine *d_lk) {
+    DevScratch s;
+    G1::Affine *d_l = nullptr; G1::XYZZ *d_part = nullptr;
+    // C by columns, every column cut into chunks of HL_COL_CHUNK entries
+    const uint32_t nnz = Cm->row_ptr[Cm->n_rows];
+    std::vector<uint32_t> cnt(V + 2, 0), row(nnz ? nnz : 1), cb, ce, first(V + 2, 0);
+    std::vector<fe> cf(nnz ? nnz : 1);
+    for (uint32_t k = 0; k < nnz; k++) { if (Cm->col[k] > V) return fail(ZK_ERR_ARG, "CSR column index exceeds the number of variables"); cnt[Cm->col[k] + 1]++; }
+    for (uint32_t v = 0; v <= V; v++) cnt[v + 1] += cnt[v];
+    {
+        std::vector<uint32_t> at(cnt.begin(), cnt.end() - 1);
+        for (uint32_t j = 0; j < Cm->n_rows; j++)
+            for (uint32_t k = Cm->row_ptr[j]; k < Cm->row_ptr[j + 1]; k++) { const uint32_t o = at[Cm->col[k]]++; row[o] = j; memcpy(&cf[o], Cm->coeff + 4 * (size_t)k, 32); }
+    }
+    for (uint32_t v = 0; v <= V; v++) {
+        first[v] = (uint32_t)cb.size();
+        for (uint32_t k = cnt[v]; k < cnt[v + 1]; k += HL_COL_CHUNK) { cb.push_back(k); ce.push_back(k + HL_COL_CHUNK < cnt[v + 1] ? k + HL_COL_CHUNK : cnt[v + 1]); }
+    }
+    first[V + 1] = (uint32_t)cb.size();
+    const uint32_t n_chunks = (uint32_t)cb.size();
+    uint32_t *d_row = nullptr, *d_cb = nullptr, *d_ce = nullptr, *d_first = nullptr; fe *d_cf = nullptr;
+    ZK_TRY(s.put(&d_row, row.data(), nnz)); ZK_TRY(s.put(&d_cf, cf.data(), nnz));
+    ZK_TRY(s.put(&d_cb, cb.data(), n_chunks)); ZK_TRY(s.put(&d_ce, ce.data(), n_chunks)); ZK_TRY(s.put(&d_first, first.data(), first.size()));
+    ZK_TRY(s.put(&d_l, L, V - nIn));
+    ZK_TRY(s.get(&d_part, n_chunks));
+    if (n_chunks) ZK_LAUNCH(k_hl_col_chunks, zk_div_up(n_chunks, 64), 64, nullptr, (const uint32_t *)d_cb, (const uint32_t *)d_ce, n_chunks, (const uint32_t *)d_row,
+                            (const fe *)d_cf, (const G1::Affine *)d_lam, d_part);
+    ZK_LAUNCH(k_hl_col_finish, zk_div_up(V + 1, 64), 64, nullptr, (const uint32_t *)d_first, (const G1::XYZZ *)d_part, (const G1::Affine *)d_l, nIn + 1, V + 1, d_lk);
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipDeviceSynchronize());
+    return ZK_OK;
+}
+// d_out[0 .. m) = Lambda_j (coset = false) or Q_j (coset = true) of the n_in <= m points H (host)
+int hl_group_dft(const G1::Affine *H, uint32_t n_in, uint32_t logm, bool coset, G1::Affine *d_out) {
+    const uint32_t m = 1u << logm;
+    DevScratch s;
+    NttTables tab;
+    struct TabFree { NttTables &t; ~TabFree() { ntt_tables_free(t); } } tab_free{tab};
+    ZK_TRY(ntt_tables_create(tab, logm, nullptr));
+    G1::Affine *d_h = nullptr; G1::XYZZ *d_work = nullptr;
+    ZK_TRY(s.put(&d_h, H, n_in));
+    ZK_TRY(s.get(&d_work, m));
+    ZK_TRY(gdft_run(tab, d_h, n_in, coset, d_work, d_out, nullptr));
+    ZK_HIP(hipDeviceSynchronize());
+    return ZK_OK;
+}
+int hl_transform_bases(const G1::Affine *H, const G1::Affine *L, const zk_csr *Cm, uint32_t logm, uint32_t nIn, uint32_t V,
+                       G1::Affine *d_q, G1::Affine *d_lk) {
+    const uint32_t m = 1u << logm;
+    DevScratch s;
+    G1::Affine *d_lam = nullptr;
+    ZK_TRY(s.get(&d_lam, m));
+    ZK_TRY(hl_group_dft(H, m - 1, logm, true, d_q));
+    ZK_TRY(hl_group_dft(H, m - 1, logm, false, d_lam));
+    return hl_column_bases(d_lam, L, Cm, nIn, V, d_lk);
 }
 void tables_free_locked(DeviceTables *t);
 // The tables belong to the KEY, not to the contexts that use them: the last context of a key leaves them in place (its next context -- the
@@ -773,6 +871,13 @@ struct zk_ctx {
     // (same window bits) the L-query's chunk pieces are folded into the H-query's bucket reduction -- one tail (finalize, heavy, group
     // reduce, tree sums) per proof less; zk_partials then carries the sum in Ht and the point at infinity in Lt.  ZK_NO_MERGE_HL=1: off.
     bool merge_hl = false;
+    // the four-transform prover (hlagrange.hpp): this context's tables hold the H-query in coset-Lagrange bases and the L-query over all V + 1
+    // variables.  l_first: the first variable of the L-query (0, or nIn + 1 in the key's bases).  d_bscale: g^i / (m R), the post-scale of B's inverse
+    // transform; d_hpart: the workgroups' shares of the degree check's two sums; d_tail: h[m-1] per proof; kp, kc, zg: constants of k_hl_tail / k_hl_q_from_h
+    bool lag = false;
+    uint32_t l_first = 0;
+    fe *d_bscale = nullptr, *d_hpart = nullptr, *d_tail = nullptr;
+    fe hl_kp, hl_kc, hl_zg;
     bool cur_merge = false;                    // ... and whether the proof in flight does it (a small synchronous proof keeps two tails: see prove_enqueue)
     // tuning aids, read from the environment ONCE at context creation (never on the proving path)
     bool env_no_direct_h2d = false;            // ZK_NO_DIRECT_H2D: synchronous proofs stage the witness through pinned memory too
@@ -787,7 +892,7 @@ struct zk_ctx {
     ~zk_ctx() {
         set_in_flight(false);
         DeviceScope on(device);
-        void *dev[] = {d_w, d_a, d_t, d_partials};           // d_b, d_c live inside d_a's allocation
+        void *dev[] = {d_w, d_a, d_t, d_partials, d_bscale, d_hpart, d_tail};           // d_b, d_c live inside d_a's allocation
         for (void *p : dev) if (p) hipFree(p);
         if (h_w) hipHostFree(h_w);
         if (d_w2) hipFree(d_w2);
@@ -829,64 +934,82 @@ static int ctx_build(zk_ctx *c, const zk_pk *pk, const zk_csr *A, const zk_csr *
     const uint32_t G = c->cfg.shard_count > 1 ? c->cfg.shard_count : 1, r = G > 1 ? c->cfg.shard_rank : 0;
     c->rA = shard_range((uint32_t)pk->a_val.size(), r, G);
     c->rB = shard_range((uint32_t)pk->b_val.size(), r, G);
-    c->rH = shard_range(m - 1, r, G);
-    c->rL = shard_range(V - nIn, r, G);
+    // unsharded contexts with full tables prove with four transforms; ZK_SIX_TRANSFORMS=1 (read here, at context creation) keeps
+    // the key's own H- and L-query bases and the six transforms
+    const char *six = getenv("ZK_SIX_TRANSFORMS");
+    const bool want_lag = G == 1 && !(six && six[0] && six[0] != '0');
+    const uint64_t circ = want_lag ? csr_hash(C, nIn, V, m) : 0;
+    auto set_ranges = [&](bool lag) {
+        c->lag = lag; c->l_first = lag ? 0 : nIn + 1;
+        c->rH = lag ? Range{0, m} : shard_range(m - 1, r, G);
+        c->rL = lag ? Range{0, V + 1} : shard_range(V - nIn, r, G);
+    };
+    set_ranges(want_lag);
     {   // find or build the shared device tables of this (key, device, shard, window) combination
         std::lock_guard<std::mutex> lk(g_tables_mu);
         DeviceTables *t = nullptr;
         for (DeviceTables *e : g_tables)
-            if (e->pk_id == pk->id && e->device == c->device && e->rank == r && e->count == G && e->cbits == c->cfg.multi_exp_c && e->max_batch == c->max_batch) { t = e; break; }
+            if (e->pk_id == pk->id && e->device == c->device && e->rank == r && e->count == G && e->cbits == c->cfg.multi_exp_c && e->max_batch == c->max_batch
+                && e->lag_req == want_lag && e->circ == circ) { t = e; break; }
         if (!t) {
             std::unique_ptr<DeviceTables, DeviceTablesDeleter> fresh(new DeviceTables());      // (an error or exception below frees what was uploaded)
             t = fresh.get();
             t->pk_id = pk->id; t->device = c->device; t->rank = r; t->count = G; t->cbits = c->cfg.multi_exp_c; t->max_batch = c->max_batch;
             t->zk = pk->full && G == 1;                                 // (sharded contexts prove without zero knowledge only)
-            // The A-, B- and L-query all read the witness: ONE bucket sort of the witness digits drives every query that is
-            // dense in the window it covers.  Unsharded the window is the whole witness; a shard's window is the span of the
-            // witness indices its three base ranges touch (base-range sharding cuts the three queries at about the same place).
-            uint32_t lo = 0xffffffffu, hi = 0;
-            auto span = [&](uint32_t first, uint32_t last) { if (first < lo) lo = first; if (last + 1 > hi) hi = last + 1; };
-            if (c->rA.n()) span(pk->a_idx[c->rA.lo], pk->a_idx[c->rA.hi - 1]);
-            if (c->rB.n()) span(pk->b_idx[c->rB.lo], pk->b_idx[c->rB.hi - 1]);
-            if (c->rL.n()) span(nIn + 1 + c->rL.lo, nIn + c->rL.hi);
-            if (G == 1) { lo = 0; hi = V + 1; }
-            if (lo > hi) lo = hi = 0;
-            t->win_lo = lo; t->win_n = hi - lo;
-            const uint64_t dense = (uint64_t)t->win_n * 7 / 8;
-            const bool can_share = t->win_n >= 64 && !getenv("ZK_NO_SHARED_SORT");
-            t->share_A = can_share && c->rA.n() >= dense;
-            t->share_B = can_share && c->rB.n() >= dense;
-            t->share_L = can_share && c->rL.n() >= dense;
-            if ((int)t->share_A + (int)t->share_B + (int)t->share_L < 2) t->share_A = t->share_B = t->share_L = false;   // nothing to share
-            auto window = [&](uint32_t n) { return t->cbits ? t->cbits : MsmShape::pick_c(n ? n : 1, t->max_batch); };
-            t->cW = window(t->win_n);
-            t->cA = t->share_A ? t->cW : window(c->rA.n()); t->cB = t->share_B ? t->cW : window(c->rB.n());
-            t->cH = window(c->rH.n()); t->cL = t->share_L ? t->cW : window(c->rL.n());
-            {   // make room for this key's tables (5 GB at 2^20, 20 GB at 2^22): idle table sets on this device go first.  If the tables still
-                // do not fit they keep every 2nd, 4th, ... window only (MsmShape::plog: S bucket planes, c S doublings between table rows, the
-                // planes folded on the host) instead of failing the context: the reference's domain goes up to 2^28 (src/stubs.cpp:49-75),
-                // whose full tables would be 16 x the key.  ZK_TABLE_BUDGET=<bytes> (read here, at context creation) stands in for the free
-                // memory: a test aid, and a way to leave room for other tenants of the device.
-                auto rows_of = [&](uint32_t cb, uint32_t plog) { const uint32_t W = 254 / cb + 1, S = 1u << plog; return (uint64_t)((W + S - 1) >> plog); };
-                auto bytes_at = [&](uint32_t plog) {
-                    return 64ull * (rows_of(t->cA, plog) * c->rA.n() + rows_of(t->cH, plog) * c->rH.n() + rows_of(t->cL, plog) * c->rL.n()) + 128ull * rows_of(t->cB, plog) * c->rB.n()
-                           + (t->zk ? 64ull * rows_of(t->cB, plog) * c->rB.n() + (64ull + 128ull) * BLIND_ROWS : 0);   // a zero-knowledge context: B1, delta1, delta2
-                };
-                t->full_table_bytes = bytes_at(0);
-                // what a context needs beside the tables: sort scratch (12 B per entry, two sorts), chunk pieces, polynomials, CSR -- about 16 B per
-                // entry of the four queries plus 8 GB of slack (the figure the eviction loop always kept)
-                const uint64_t entries = 15ull * ((uint64_t)c->rA.n() + c->rB.n() * (t->zk ? 2 : 1) + c->rH.n() + c->rL.n()) * c->max_batch;   // (B1: reduction buffers of its own)
-                const uint64_t reserve = (8ull << 30) + 16ull * entries;
-                size_t mem_free = 0, mem_total = 0;
-                while (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess && t->full_table_bytes + reserve > mem_free && tables_evict_idle_locked(c->device)) {}
-                uint64_t budget = mem_free > reserve ? mem_free - reserve : 0;
-                if (const char *e = getenv("ZK_TABLE_BUDGET")) budget = strtoull(e, nullptr, 10);
-                // (proofs x planes x buckets must fit the sort's 2^20 bucket ids: MsmWork::alloc checks the same)
-                const uint32_t cmax = std::max(std::max(t->cA, t->cB), std::max(t->cH, t->cL));
-                auto sets_fit = [&](uint32_t plog) { return (((uint64_t)c->max_batch << plog) << (cmax - 1)) <= (1ull << 20); };
-                while (bytes_at(t->plog) > budget && t->plog < 4 && sets_fit(t->plog + 1)) t->plog++;
-                t->table_bytes = bytes_at(t->plog);
-            }
+            t->lag_req = want_lag; t->circ = circ;
+            // window bits, shared sort and table rows for the H- and L-query in the given bases
+            auto plan_tables = [&](bool lag) {
+                set_ranges(lag);
+                t->lag = lag; t->plog = 0;
+                // The A-, B- and L-query all read the witness: ONE bucket sort of the witness digits drives every query that is
+                // dense in the window it covers.  Unsharded the window is the whole witness; a shard's window is the span of the
+                // witness indices its three base ranges touch (base-range sharding cuts the three queries at about the same place).
+                uint32_t lo = 0xffffffffu, hi = 0;
+                auto span = [&](uint32_t first, uint32_t last) { if (first < lo) lo = first; if (last + 1 > hi) hi = last + 1; };
+                if (c->rA.n()) span(pk->a_idx[c->rA.lo], pk->a_idx[c->rA.hi - 1]);
+                if (c->rB.n()) span(pk->b_idx[c->rB.lo], pk->b_idx[c->rB.hi - 1]);
+                if (c->rL.n()) span(c->l_first + c->rL.lo, c->l_first + c->rL.hi - 1);
+                if (G == 1) { lo = 0; hi = V + 1; }
+                if (lo > hi) lo = hi = 0;
+                t->win_lo = lo; t->win_n = hi - lo;
+                const uint64_t dense = (uint64_t)t->win_n * 7 / 8;
+                const bool can_share = t->win_n >= 64 && !getenv("ZK_NO_SHARED_SORT");
+                t->share_A = can_share && c->rA.n() >= dense;
+                t->share_B = can_share && c->rB.n() >= dense;
+                t->share_L = can_share && c->rL.n() >= dense;
+                if ((int)t->share_A + (int)t->share_B + (int)t->share_L < 2) t->share_A = t->share_B = t->share_L = false;   // nothing to share
+                auto window = [&](uint32_t n) { return t->cbits ? t->cbits : MsmShape::pick_c(n ? n : 1, t->max_batch); };
+                t->cW = window(t->win_n);
+                t->cA = t->share_A ? t->cW : window(c->rA.n()); t->cB = t->share_B ? t->cW : window(c->rB.n());
+                t->cH = window(c->rH.n()); t->cL = t->share_L ? t->cW : window(c->rL.n());
+                {   // make room for this key's tables (5 GB at 2^20, 20 GB at 2^22): idle table sets on this device go first.  If the tables still
+                    // do not fit they keep every 2nd, 4th, ... window only (MsmShape::plog: S bucket planes, c S doublings between table rows, the
+                    // planes folded on the host) instead of failing the context: the reference's domain goes up to 2^28 (src/stubs.cpp:49-75),
+                    // whose full tables would be 16 x the key.  ZK_TABLE_BUDGET=<bytes> (read here, at context creation) stands in for the free
+                    // memory: a test aid, and a way to leave room for other tenants of the device.
+                    auto rows_of = [&](uint32_t cb, uint32_t plog) { const uint32_t W = 254 / cb + 1, S = 1u << plog; return (uint64_t)((W + S - 1) >> plog); };
+                    auto bytes_at = [&](uint32_t plog) {
+                        return 64ull * (rows_of(t->cA, plog) * c->rA.n() + rows_of(t->cH, plog) * c->rH.n() + rows_of(t->cL, plog) * c->rL.n()) + 128ull * rows_of(t->cB, plog) * c->rB.n()
+                               + (t->zk ? 64ull * rows_of(t->cB, plog) * c->rB.n() + (64ull + 128ull) * BLIND_ROWS : 0);   // a zero-knowledge context: B1, delta1, delta2
+                    };
+                    t->full_table_bytes = bytes_at(0);
+                    // what a context needs beside the tables: sort scratch (12 B per entry, two sorts), chunk pieces, polynomials, CSR -- about 16 B per
+                    // entry of the four queries plus 8 GB of slack (the figure the eviction loop always kept)
+                    const uint64_t entries = 15ull * ((uint64_t)c->rA.n() + c->rB.n() * (t->zk ? 2 : 1) + c->rH.n() + c->rL.n()) * c->max_batch;   // (B1: reduction buffers of its own)
+                    const uint64_t reserve = (8ull << 30) + 16ull * entries;
+                    size_t mem_free = 0, mem_total = 0;
+                    while (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess && t->full_table_bytes + reserve > mem_free && tables_evict_idle_locked(c->device)) {}
+                    uint64_t budget = mem_free > reserve ? mem_free - reserve : 0;
+                    if (const char *e = getenv("ZK_TABLE_BUDGET")) budget = strtoull(e, nullptr, 10);
+                    // (proofs x planes x buckets must fit the sort's 2^20 bucket ids: MsmWork::alloc checks the same)
+                    const uint32_t cmax = std::max(std::max(t->cA, t->cB), std::max(t->cH, t->cL));
+                    auto sets_fit = [&](uint32_t plog) { return (((uint64_t)c->max_batch << plog) << (cmax - 1)) <= (1ull << 20); };
+                    while (bytes_at(t->plog) > budget && t->plog < 4 && sets_fit(t->plog + 1)) t->plog++;
+                    t->table_bytes = bytes_at(t->plog);
+                }
+            };
+            plan_tables(want_lag);
+            if (t->lag && t->plog) plan_tables(false);               // the Lagrange tables would come out frugal: the key's own bases, six transforms
             int rc = dev_upload(&t->dA_idx, pk->a_idx.data() + c->rA.lo, c->rA.n());
             if (rc == ZK_OK) rc = dev_upload(&t->dB_idx, pk->b_idx.data() + c->rB.lo, c->rB.n());
             // window position -> shard entry: consecutive indices need no map (entry = position - off), else an explicit one
@@ -902,10 +1025,22 @@ static int ctx_build(zk_ctx *c, const zk_pk *pk, const zk_csr *A, const zk_csr *
             };
             if (rc == ZK_OK && t->share_A) rc = inverse(pk->a_idx, c->rA, &t->posA, &t->offA);
             if (rc == ZK_OK && t->share_B) rc = inverse(pk->b_idx, c->rB, &t->posB, &t->offB);
-            t->offL = c->rL.n() ? nIn + 1 + c->rL.lo - t->win_lo : 0;
+            t->offL = c->rL.n() ? c->l_first + c->rL.lo - t->win_lo : 0;
             if (rc == ZK_OK) rc = build_table<G1>(&t->tA, pk->a_val.data() + c->rA.lo, c->rA.n(), t->cA, t->plog);
+            if (rc == ZK_OK && t->lag) {                                 // Q_j and L_v - K_v instead of the key's H- and L-query (hlagrange.hpp)
+                const double t0 = now_ms();
+                DevScratch s;
+                G1::Affine *d_q = nullptr, *d_lk = nullptr;
+                rc = s.get(&d_q, m);
+                if (rc == ZK_OK) rc = s.get(&d_lk, (size_t)V + 1);
+                if (rc == ZK_OK) rc = hl_transform_bases(pk->H.data(), pk->L.data(), C, c->logm, nIn, V, d_q, d_lk);
+                t->lag_ms = now_ms() - t0;                              // (hl_transform_bases ends with a device synchronisation)
+                if (rc == ZK_OK) rc = build_table_dev<G1>(&t->tH, d_q, m, t->cH, t->plog);
+                if (rc == ZK_OK) rc = build_table_dev<G1>(&t->tL, d_lk, V + 1, t->cL, t->plog);
+            } else {
             if (rc == ZK_OK) rc = build_table<G1>(&t->tH, pk->H.data() + c->rH.lo, c->rH.n(), t->cH, t->plog);
             if (rc == ZK_OK) rc = build_table<G1>(&t->tL, pk->L.data() + c->rL.lo, c->rL.n(), t->cL, t->plog);
+            }
             if (rc == ZK_OK) rc = build_table<G2>(&t->tB, pk->b_val.data() + c->rB.lo, c->rB.n(), t->cB, t->plog);
             if (rc == ZK_OK && t->zk) {
                 if (pk->b1_val.size() != pk->b_val.size()) rc = fail(ZK_ERR_ARG, "full key: the G1 half of the B-query has another length than the G2 half");
@@ -920,6 +1055,7 @@ static int ctx_build(zk_ctx *c, const zk_pk *pk, const zk_csr *A, const zk_csr *
         }
         t->refs++;
         c->tables = t;
+        set_ranges(t->lag);
     }
     c->dA_idx = c->tables->dA_idx; c->dB_idx = c->tables->dB_idx;
     const DeviceTables *t = c->tables;
@@ -956,6 +1092,11 @@ static int ctx_build(zk_ctx *c, const zk_pk *pk, const zk_csr *A, const zk_csr *
     c->mA.dev_result_pitch = c->mB.dev_result_pitch = c->mH.dev_result_pitch = c->mL.dev_result_pitch = sizeof(zk_partials);
     ZK_HIP(hipHostMalloc(&c->h_w, 32 * (size_t)(V + 1) * KB, hipHostMallocDefault));
     ZK_HIP(hipHostMalloc(&c->h_tail, 32 * (size_t)KB, hipHostMallocDefault));
+    if (c->lag) {
+        ZK_HIP(hipMalloc(&c->d_bscale, 32 * (size_t)m));
+        ZK_HIP(hipMalloc(&c->d_hpart, 2 * 32 * (size_t)zk_div_up(m, HL_PROD_THREADS) * KB));
+        ZK_HIP(hipMalloc(&c->d_tail, 32 * (size_t)KB));
+    }
     // s_main (high priority) carries the short memory- and latency-bound kernels: witness upload, bucket sorts, the H
     // polynomial pipeline; s_acc (low priority) carries the four machine-filling accumulation kernels, each released by
     // the event of its sort; the bucket-reduction tails run on side streams.  The priorities make the dispatcher hand freed
@@ -1001,6 +1142,14 @@ static int ctx_build(zk_ctx *c, const zk_pk *pk, const zk_csr *A, const zk_csr *
     hipEvent_t *ee[] = {&c->ev_start, &c->ev_w, &c->ev_h, &c->ev_a0, &c->ev_a1, &c->ev_b0, &c->ev_b1, &c->ev_l0, &c->ev_l1, &c->ev_h1, &c->ev_h0};
     for (auto e : ee) ZK_HIP(hipEventCreate(e));
     ZK_TRY(ntt_tables_create(c->tab, c->logm, c->s_main));
+    if (c->lag) {
+        const fe g = Fr::from_u64(5), mi = Fr::inv(Fr::from_u64(m)), mz = Fr::mul(mi, c->tab.zinv);
+        ZK_LAUNCH(k_fill_geometric, zk_div_up(zk_div_up(m, 256), 64), 64, c->s_main, c->d_bscale, m, g, Fr::from_mont(mi));   // g^i / (m R)
+        c->hl_kp = Fr::to_mont(Fr::mul(mz, Fr::inv(Fr::pow_u64(g, m - 1))));                                                  // R^2 g^-(m-1) / (m Z(g))
+        c->hl_kc = mz;
+        c->hl_zg = Fr::sub(Fr::pow_u64(g, m), Fr::one());
+        ZK_HIP(hipGetLastError());
+    }
     ZK_HIP(hipStreamSynchronize(c->s_main));
     return ZK_OK;
 }
@@ -1061,6 +1210,38 @@ static int enqueue_compute_h(zk_ctx *c, hipStream_t st) {
     if (k == 1) ZK_HIP(hipMemcpyAsync(c->h_tail, c->d_t + (m - 1), 32, hipMemcpyDeviceToHost, st));
     else ZK_HIP(hipMemcpy2DAsync(c->h_tail, 32, c->d_t + (m - 1), 32 * (size_t)m, 32, k, hipMemcpyDeviceToHost, st));
     ZK_HIP(hipGetLastError());
+    return ZK_OK;
+}
+
+// ---- the same for a context whose H-query lies in coset-Lagrange bases (hlagrange.hpp): FOUR transforms.  The H scalars are the
+// products p_j = A(g w^j) B(g w^j), canonical, in d_t (proof p at d_t + p m); the C row evaluations are scalars of nothing -- their part of h
+// is in the L-query's bases -- and only enter the degree check: h[m-1] as a dot product over p and c, copied to h_tail as above.
+static int enqueue_compute_h4(zk_ctx *c, hipStream_t st) {
+    const uint32_t m = c->m, k = c->cur_batch, ws = c->V + 1;
+    fe *a = c->d_a, *b = c->d_a + (size_t)m * k, *cc = c->d_a + 2 * (size_t)m * k;
+    ZK_TRY(c->cA.enqueue(c->d_w, a, st, k, ws, m, m, c->nIn + 1));
+    ZK_TRY(c->cB.enqueue(c->d_w, b, st, k, ws, m, m, 0));
+    ZK_TRY(c->cC.enqueue(c->d_w, cc, st, k, ws, m, m, 0));
+    NttFuse bscale; bscale.post_alt = c->d_bscale; bscale.alt_from = k;                                 // vectors [k, 2k) are the B polynomials: x 1 / R as well
+    ZK_TRY(ntt_run(c->tab, a, c->d_t, true, nullptr, c->tab.inv_then_coset, st, 2 * k, m, bscale));   // iFFT of A, B (x g^i / m: cosetFFT pre-scale)
+    ZK_TRY(ntt_run(c->tab, c->d_t, a, false, nullptr, nullptr, st, 2 * k, m));                        // FFT: A, B on the coset
+    const uint32_t grid = zk_div_up(m, HL_PROD_THREADS * HL_PROD_PER);
+    ZK_LAUNCH_SYNC(k_hl_product, dim3(grid, k), HL_PROD_THREADS, st, (const fe *)a, (const fe *)b, (const fe *)cc, (const fe *)c->tab.tw_fwd, c->d_t, c->d_hpart, m, m);
+    ZK_LAUNCH_SYNC(k_hl_tail, k, HL_PROD_THREADS, st, (const fe *)c->d_hpart, grid, c->hl_kp, c->hl_kc, c->d_tail);
+    ZK_HIP(hipMemcpyAsync(c->h_tail, c->d_tail, 32 * (size_t)k, hipMemcpyDeviceToHost, st));
+    ZK_HIP(hipGetLastError());
+    return ZK_OK;
+}
+// ... and for an h that arrives as coefficients (zk_prove_submit_h, zk_prove_submit_with_h: the two-step submit, whose h comes from the
+// six-transform chains): p = cosetFFT(Z(g) h + C), C's coefficients from its row evaluations -- two transforms on a path that is rare on an
+// unsharded context.  One proof; d_h may be the context's own d_t.  Result in d_t, Montgomery.
+static int enqueue_h_coefficients_to_coset(zk_ctx *c, const fe *d_h, hipStream_t st) {
+    const uint32_t m = c->m, ws = c->V + 1;
+    fe *cc = c->d_a + 2 * (size_t)m, *ccoef = c->d_t + 2 * (size_t)m;
+    ZK_TRY(c->cC.enqueue(c->d_w, cc, st, 1, ws, m, m, 0));
+    ZK_TRY(ntt_run(c->tab, cc, ccoef, true, nullptr, c->tab.inv_m, st));
+    ZK_LAUNCH(k_hl_q_from_h, zk_div_up(m, 256), 256, st, d_h, m - 1, (const fe *)ccoef, c->hl_zg, c->d_a, m);
+    ZK_TRY(ntt_run(c->tab, c->d_a, c->d_t, false, c->tab.coset_fwd, nullptr, st));
     return ZK_OK;
 }
 
@@ -1191,10 +1372,14 @@ static int prove_enqueue(zk_ctx *c, const uint64_t *witness, int canonical, int 
     hipStream_t hs = split_h ? c->s_h : m;
     auto h_pipeline = [&]() -> int {
         ZK_HIP(hipEventRecord(c->ev_h0, hs));
-        if (!d_h) ZK_TRY(enqueue_compute_h(c, hs));
-        else memset(c->h_tail, 0, 32);                          // the rank that computed h has checked its degree
+        if (!d_h) ZK_TRY(c->lag ? enqueue_compute_h4(c, hs) : enqueue_compute_h(c, hs));
+        else {
+            memset(c->h_tail, 0, 32);                           // the rank that computed h has checked its degree
+            if (c->lag) ZK_TRY(enqueue_h_coefficients_to_coset(c, d_h, hs));
+        }
         ZK_HIP(hipEventRecord(c->ev_h, hs));
-        ZK_TRY(c->mH.enqueue_sort(d_h ? d_h : c->d_t + c->rH.lo, nullptr, c->rH.n(), 0, hs, k, c->m));   // tcc:510-518
+        if (c->lag) ZK_TRY(c->mH.enqueue_sort(c->d_t, nullptr, c->m, d_h ? 0 : 1, hs, k, c->m));         // the m scalars p_j (canonical out of k_hl_product)
+        else ZK_TRY(c->mH.enqueue_sort(d_h ? d_h : c->d_t + c->rH.lo, nullptr, c->rH.n(), 0, hs, k, c->m));   // tcc:510-518
         if (split_h) ZK_HIP(hipEventRecord(c->ev_sort_h, hs));
         return ZK_OK;
     };
@@ -1228,7 +1413,7 @@ static int prove_enqueue(zk_ctx *c, const uint64_t *witness, int canonical, int 
     ZK_HIP(hipEventRecord(c->ev_a0, q));
     ZK_TRY(c->mA.enqueue_reduce(t->share_A ? c->mW.view_for(t->offA, t->posA) : c->mA.view(), q, c->env_tails_on_acc ? q : c->s_a, tail_lanes));    // tcc:488-495
     ZK_HIP(hipEventRecord(c->ev_a1, c->s_a));
-    if (!t->share_L) { ZK_TRY(c->mL.enqueue_sort(c->d_w + (c->nIn + 1) + c->rL.lo, nullptr, c->rL.n(), 0, m, k, ws)); ZK_TRY(release()); }
+    if (!t->share_L) { ZK_TRY(c->mL.enqueue_sort(c->d_w + c->l_first + c->rL.lo, nullptr, c->rL.n(), 0, m, k, ws)); ZK_TRY(release()); }
     // One synchronous proof below ~2^19 constraints is a latency chain: folded into the H-query's reduction the L-query's pieces double the
     // serial additions per bucket at the very end of the proof, while a tail of its own runs early, beside the H pipeline (same-box A/B,
     // tools/dev_sync_latency.py: 2^16 1.60 -> 1.65 ms, 2^18 3.38 -> 3.46 merged; 2^20 9.96 -> 9.94; pipelined 2^20: +2.8 % merged).  Sharded
@@ -1462,6 +1647,36 @@ extern "C" int zk_ctx_info(const zk_ctx *c, uint32_t info[16]) try {
 extern "C" int zk_ctx_table_info(const zk_ctx *c, uint64_t info[4]) try {
     if (!c || !info) return fail(ZK_ERR_ARG, "null argument");
     info[0] = c->tables->table_bytes; info[1] = c->tables->full_table_bytes; info[2] = 1ull << c->tables->plog; info[3] = c->mB.sh.rows();
+    return ZK_OK;
+} ZK_GUARD
+// the H-query in coset-Lagrange bases: {1 if this context proves with four transforms, microseconds the transform of the bases took when the
+// tables were built (once per key and circuit), 0, 0}
+extern "C" int zk_ctx_hlagrange_info(const zk_ctx *c, uint64_t info[4]) try {
+    if (!c || !info) return fail(ZK_ERR_ARG, "null argument");
+    info[0] = c->lag ? 1 : 0; info[1] = (uint64_t)(c->tables->lag_ms * 1000.0); info[2] = 0; info[3] = 0;
+    return ZK_OK;
+} ZK_GUARD
+// test entry points of the per-key transform (hlagrange.hpp): points are affine, 8 x u64 each, Montgomery Fq, (0, 0) = the point at infinity
+extern "C" int zk_hl_probe_dft(const uint64_t *points, uint32_t n, uint32_t logm, int coset, int device, uint64_t *out) try {
+    if (!points || !out || logm > 20 || n > (1u << logm)) return fail(ZK_ERR_ARG, "bad argument");
+    ZK_TRY(use_device(device));
+    const uint32_t m = 1u << logm;
+    DevScratch s;
+    G1::Affine *d_out = nullptr;
+    ZK_TRY(s.get(&d_out, m));
+    ZK_TRY(hl_group_dft((const G1::Affine *)points, n, logm, coset != 0, d_out));
+    ZK_HIP(hipMemcpy(out, d_out, sizeof(G1::Affine) * (size_t)m, hipMemcpyDeviceToHost));
+    return ZK_OK;
+} ZK_GUARD
+extern "C" int zk_hl_probe_columns(const zk_csr *Cm, uint32_t nIn, uint32_t V, const uint64_t *lambda, uint32_t m, const uint64_t *l_bases, int device, uint64_t *out) try {
+    if (!Cm || !lambda || !out || nIn > V || (!l_bases && V != nIn) || Cm->n_rows > m) return fail(ZK_ERR_ARG, "bad argument");
+    ZK_TRY(use_device(device));
+    DevScratch s;
+    G1::Affine *d_lam = nullptr, *d_lk = nullptr;
+    ZK_TRY(s.put(&d_lam, (const G1::Affine *)lambda, m));
+    ZK_TRY(s.get(&d_lk, (size_t)V + 1));
+    ZK_TRY(hl_column_bases(d_lam, (const G1::Affine *)l_bases, Cm, nIn, V, d_lk));
+    ZK_HIP(hipMemcpy(out, d_lk, sizeof(G1::Affine) * ((size_t)V + 1), hipMemcpyDeviceToHost));
     return ZK_OK;
 } ZK_GUARD
 extern "C" int zk_prove_collect(zk_ctx *ctx, zk_partials *out, zk_timings *t) try {

@@ -68,7 +68,7 @@ EXPORTS = [
     "zk_wplan_create", "zk_wplan_create_hinted", "zk_wplan_create_wide", "zk_wplan_info", "zk_wplan_solve", "zk_wplan_free", "zk_wplan_probe_program", "zk_dev_alloc", "zk_dev_free", "zk_dev_upload", "zk_dev_download",
     "zk_chain_submit", "zk_chain_device", "zk_h_from_chains_submit", "zk_h_device", "zk_chain_wait", "zk_prove_submit_with_h", "zk_prove_submit_defer_h", "zk_prove_submit_h", "zk_prove_abort",
     "zk_prove_submit_pinned", "zk_prove_batch_submit_pinned", "zk_host_alloc", "zk_host_free", "zk_host_register", "zk_host_unregister",
-    "zk_prove_submit_resident", "zk_prove_stage", "zk_prove_stage_pinned", "zk_prove_submit_staged", "zk_ctx_info", "zk_ctx_table_info", "zk_ctx_partials_device", "zk_prove_collect_device", "zk_prove_combine_device", "zk_launch_count", "zk_profile_begin", "zk_profile_end", "zk_device_info", "zk_device_pci_bus_id",
+    "zk_prove_submit_resident", "zk_prove_stage", "zk_prove_stage_pinned", "zk_prove_submit_staged", "zk_ctx_info", "zk_ctx_table_info", "zk_ctx_hlagrange_info", "zk_hl_probe_dft", "zk_hl_probe_columns", "zk_ctx_partials_device", "zk_prove_collect_device", "zk_prove_combine_device", "zk_launch_count", "zk_profile_begin", "zk_profile_end", "zk_device_info", "zk_device_pci_bus_id",
     "zk_verify",
     "zk_vctx_create", "zk_vctx_destroy", "zk_verify_batch", "zk_verify_batch_json", "zk_pairing_check", "zk_pairing_tower_op",
     "zk_mtree_create", "zk_mtree_free", "zk_mtree_size", "zk_mtree_append", "zk_mtree_append_resident", "zk_mtree_update", "zk_mtree_root", "zk_mtree_node",
@@ -525,6 +525,9 @@ class ProverContext:
         t = (C.c_uint64 * 4)()
         _check(_lib.zk_ctx_table_info(self._h, t))                      # planes > 1: memory-frugal tables (every planes-th window tabulated)
         d.update(table_bytes=int(t[0]), full_table_bytes=int(t[1]), planes=int(t[2]), table_rows_B=int(t[3]))
+        if hasattr(_lib, "zk_ctx_hlagrange_info"):                      # (absent from older builds of the same ABI)
+            _check(_lib.zk_ctx_hlagrange_info(self._h, t))
+            d.update(four_transforms=bool(t[0]), hlagrange_precompute_ms=int(t[1]) / 1000.0)
         return d
 
     def collect(self):
@@ -849,6 +852,40 @@ class WitnessPlan:
 
 
 # ---- measurement aids
+def _g1_pack(points):
+    from .fields import fq_to_mont
+    flat = []
+    for pt in points:
+        flat += [0, 0] if pt is None else [pt[0], pt[1]]
+    return np.ascontiguousarray(fq_to_mont(flat), dtype=np.uint64).reshape(-1) if flat else np.zeros(8, dtype=np.uint64)
+
+
+def _g1_unpack(arr, n):
+    from .fields import fq_from_mont
+    v = fq_from_mont(np.asarray(arr, dtype=np.uint64).reshape(2 * n, 4))
+    return [None if (v[2 * i], v[2 * i + 1]) == (0, 0) else (v[2 * i], v[2 * i + 1]) for i in range(n)]
+
+
+def hl_probe_dft(points, logm, coset, device=0):
+    """zk_hl_probe_dft: the per-key group transform of the four-transform prover on its own.  points: affine (x, y) ints or None
+    (the point at infinity), at most 2^logm of them; returns the 2^logm output points the same way"""
+    lib = load_library(_lib_path_loaded)
+    m = 1 << logm
+    src, out = _g1_pack(points), np.zeros(8 * m, dtype=np.uint64)
+    _check(lib.zk_hl_probe_dft(_p64(src), C.c_uint32(len(points)), C.c_uint32(logm), int(bool(coset)), int(device), _p64(out)))
+    return _g1_unpack(out, m)
+
+
+def hl_probe_columns(c_matrix, nIn, V, lam, l_bases, device=0):
+    """zk_hl_probe_columns: out[v] = L_v - sum_j C[j][v] lam[j] for v <= V (c_matrix: r1cs.CSR; points as in hl_probe_dft)"""
+    lib = load_library(_lib_path_loaded)
+    rp = np.ascontiguousarray(c_matrix.row_ptr, dtype=np.uint32); co = np.ascontiguousarray(c_matrix.col, dtype=np.uint32); cf = _c64(c_matrix.coeff)
+    cs = ZkCSR(c_matrix.n_rows, _p32(rp), _p32(co), _p64(cf))
+    a, b, out = _g1_pack(lam), _g1_pack(l_bases), np.zeros(8 * (V + 1), dtype=np.uint64)
+    _check(lib.zk_hl_probe_columns(C.byref(cs), C.c_uint32(nIn), C.c_uint32(V), _p64(a), C.c_uint32(len(lam)), _p64(b), int(device), _p64(out)))
+    return _g1_unpack(out, V + 1)
+
+
 def launch_count():
     return int(load_library(_lib_path_loaded).zk_launch_count())
 

@@ -289,6 +289,18 @@ int zk_ctx_info(const zk_ctx *ctx, uint32_t info[16]);
  * with S bucket planes instead of failing; the proof bytes are the same.  ZK_TABLE_BUDGET=<bytes> in the environment at context creation
  * caps the tables below the free device memory. */
 int zk_ctx_table_info(const zk_ctx *ctx, uint64_t info[4]);
+/* The four-transform prover: an unsharded context with full tables keeps the H-query in coset-Lagrange bases (m bases Q_j, scalars
+ * A(g w^j) B(g w^j)) and the L-query over all V + 1 variables (bases L_v - K_v), built once per key AND circuit at context creation and shared
+ * like the other tables; a proof then needs four transforms instead of six and has the same bytes.  ZK_SIX_TRANSFORMS=1 in the environment
+ * at context creation keeps the key's own bases and the six transforms (sharded contexts and frugal tables always do).
+ * info = {1 if this context proves with four transforms, microseconds the transform of the bases took when the tables were built
+ *         (without their window-multiple expansion), 0, 0} */
+int zk_ctx_hlagrange_info(const zk_ctx *ctx, uint64_t info[4]);
+/* test entry points of that transform.  Points are affine, 8 x u64 each (x, y: Montgomery Fq), (0, 0) = the point at infinity.
+ * zk_hl_probe_dft:     out[j] = 1 / (m Z(g)) sum_{i < n} r^(-i) w^(-ij) points[i], j < m = 2^logm, r = g (coset != 0) or 1
+ * zk_hl_probe_columns: out[v] = L_v - sum_j C[j][v] lambda[j], v <= V; L_v = l_bases[v - nIn - 1], the point at infinity for v <= nIn */
+int zk_hl_probe_dft(const uint64_t *points, uint32_t n, uint32_t logm, int coset, int device, uint64_t *out);
+int zk_hl_probe_columns(const zk_csr *C, uint32_t nIn, uint32_t V, const uint64_t *lambda, uint32_t m, const uint64_t *l_bases, int device, uint64_t *out);
 
 /* inputs: nIn Fr elements = witness[1..nIn] (Montgomery unless canonical); returns the JSON length
  * (excluding NUL) through *len; ZK_ERR_BUFFER if cap is too small (len still set) */
