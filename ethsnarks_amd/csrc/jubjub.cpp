@@ -19,6 +19,7 @@ using namespace zk::jubjub;
 
 static_assert(ZK_JJ_OP_ADD == OP_ADD && ZK_JJ_OP_DOUBLE == OP_DOUBLE && ZK_JJ_OP_NEGATE == OP_NEGATE, "zkhip.h and jubjub.hpp number the point operations alike");
 static_assert(sizeof(zk_eddsa_layout) == sizeof(FillLayout) && sizeof(FillLayout) == 19 * sizeof(uint32_t), "zkhip.h and jubjub.hpp lay the witness row out alike");
+static_assert(sizeof(zk_eddsa_pure_layout) == sizeof(PureLayout) && sizeof(PureLayout) == 26 * sizeof(uint32_t), "zkhip.h and jubjub.hpp lay the PureEdDSA witness row out alike");
 static_assert(ZK_EDDSA_MIMC == SCHEME_MIMC && ZK_EDDSA_PURE == SCHEME_PURE && ZK_EDDSA_HASH == SCHEME_HASH, "zkhip.h and jubjub.hpp number the schemes alike");
 
 namespace {
@@ -156,6 +157,23 @@ void pedersen_table(const std::string &name, uint32_t windows, std::vector<fe> &
     }
     to_entries(pts, out);
 }
+// table entries (x, y, d x y) -> the Montgomery form (u, v) = ((1 + y) / (1 - y), u / x) of each point (EdwardsPoint::as_montgomery, scale 1), one
+// inversion for all of them.  No table point has x = 0 or y = 1: each is a multiple below L of a point of prime order
+void montgomery_entries(const std::vector<fe> &entries, std::vector<fe> &out) {
+    const size_t n = entries.size() / 3;
+    std::vector<fe> pre(n);
+    fe run = Fr::one();
+    for (size_t i = 0; i < n; i++) { pre[i] = run; run = Fr::mul(run, Fr::mul(Fr::sub(Fr::one(), entries[3 * i + 1]), entries[3 * i])); }
+    fe inv = Fr::inv(run);
+    out.resize(2 * n);
+    for (size_t i = n; i-- > 0;) {
+        const fe x = entries[3 * i], y = entries[3 * i + 1], omy = Fr::sub(Fr::one(), y);
+        const fe di = Fr::mul(inv, pre[i]);                      // 1 / ((1 - y) x)
+        inv = Fr::mul(inv, Fr::mul(omy, x));
+        const fe u = Fr::mul(Fr::add(Fr::one(), y), Fr::mul(di, x));
+        out[2 * i] = u; out[2 * i + 1] = Fr::mul(u, Fr::mul(di, omy));
+    }
+}
 // C_0 = keccak256(keccak256(seed)), C_{i+1} = keccak256(C_i) (mimc_constants of ethsnarks/mimc/permutation.py), Montgomery
 void mimc_constants(const char *seed, fe *rc) {
     uint8_t dg[32], nx[32];
@@ -204,8 +222,9 @@ struct zk_pedersen {
 struct zk_eddsa {
     int device = 0;
     uint32_t scheme = 0, msg_len = 0, ram_windows = 0, m_windows = 0;
-    DevBuf consts, scratch;                                     // consts: btab | rc | ram table | m table | the 2-bit windows of B (MiMC)
+    DevBuf consts, scratch;                                     // consts: btab | rc | ram table | m table | the 2-bit windows of B (MiMC, pure) | (u, v) of the ram table (pure)
     const fe *fbtab = nullptr;                                  // (0 .. 3) 4^i B, i = 0 .. 126: the tables of the circuit's fixed_base_mul
+    const fe *mtab = nullptr;                                   // the Montgomery form of every ram table point: the lookups of the in-circuit Pedersen hash
     EddsaView view;
     hipStream_t st = nullptr;
     ~zk_eddsa() { if (st) (void)hipStreamDestroy(st); }
@@ -351,8 +370,8 @@ extern "C" int zk_eddsa_create(int scheme, const uint64_t *B, uint32_t msg_len, 
         pedersen_table("EdDSA_Verify.RAM", v->ram_windows, ram);
         if (scheme == SCHEME_HASH) { v->m_windows = (8 * msg_len + 2) / 3; pedersen_table("EdDSA_Verify.M", v->m_windows, mt); }
     }
-    std::vector<fe> all(btab), fb;
-    if (scheme == SCHEME_MIMC) {                                // window i of the circuit's fixed-base multiplication: identity, P, 2 P, 3 P, P = 4^i B
+    std::vector<fe> all(btab), fb, mont;
+    if (scheme != SCHEME_HASH) {                                // window i of the circuit's fixed-base multiplication: identity, P, 2 P, 3 P, P = 4^i B
         std::vector<jpoint> w;
         w.reserve(4 * FB_WINDOWS);
         jpoint cur = mult[1];
@@ -364,15 +383,18 @@ extern "C" int zk_eddsa_create(int scheme, const uint64_t *B, uint32_t msg_len, 
         }
         to_entries(w, fb);
     }
+    if (scheme == SCHEME_PURE) montgomery_entries(ram, mont);
     const size_t o_rc = all.size(); all.insert(all.end(), rc.begin(), rc.end());
     const size_t o_ram = all.size(); all.insert(all.end(), ram.begin(), ram.end());
     const size_t o_m = all.size(); all.insert(all.end(), mt.begin(), mt.end());
     const size_t o_fb = all.size(); all.insert(all.end(), fb.begin(), fb.end());
+    const size_t o_mont = all.size(); all.insert(all.end(), mont.begin(), mont.end());
     ZK_HIP(hipStreamCreateWithFlags(&v->st, hipStreamNonBlocking));
     ZK_TRY(v->consts.upload(all.data(), sizeof(fe) * all.size()));
     const fe *d = (const fe *)v->consts.p;
     v->view.btab = d; v->view.rc = d + o_rc; v->view.ram_tab = d + o_ram; v->view.m_tab = d + o_m;
-    if (scheme == SCHEME_MIMC) v->fbtab = d + o_fb;
+    if (scheme != SCHEME_HASH) v->fbtab = d + o_fb;
+    if (scheme == SCHEME_PURE) v->mtab = d + o_mont;
     v->view.scheme = v->scheme; v->view.msg_len = msg_len; v->view.ram_windows = v->ram_windows; v->view.m_windows = v->m_windows;
     *out = v.release();
     return ZK_OK;
@@ -458,6 +480,60 @@ extern "C" int zk_eddsa_fill_witnesses(zk_eddsa *v, const uint64_t *A, const uin
     ZK_HIP(hipMemcpyAsync(dM, msgs, mb, hipMemcpyHostToDevice, v->st));
     ZK_LAUNCH(k_eddsa_fill, zk_div_up(n, BLOCK), BLOCK, v->st, v->view, v->fbtab, L, (const fe *)dA, (const fe *)dR, (const fe *)dS, (const fe *)dM, n, (fe *)d_w,
               row_elems, (uint8_t *)dV);
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipMemcpyAsync(verdicts, dV, n, hipMemcpyDeviceToHost, v->st));
+    ZK_HIP(hipStreamSynchronize(v->st));
+    return ZK_OK;
+} ZK_GUARD
+
+namespace {
+// the PureEdDSA row: as layout_fits, with the hash's segments sized by the window count of the verifier's msg_len
+bool pure_layout_fits(const PureLayout &L, uint32_t msg_len, uint64_t row_elems) {
+    if (L.msg_len != msg_len || (uint64_t)L.n_vars + 1 > row_elems) return false;
+    const uint64_t W = pure_windows(msg_len), S = (W + SEG_WINDOWS - 1) / SEG_WINDOWS;
+    const uint64_t step0 = std::min(L.doubler_var0, std::min(L.cond_var0, L.adder_var0));
+    struct Seg { uint64_t at, len; };
+    const Seg step[3] = {{L.doubler_var0, DBL_VARS}, {L.cond_var0, 2}, {L.adder_var0, ADD_VARS}};
+    for (int i = 0; i < 3; i++) {
+        if (step[i].at + step[i].len > step0 + L.step_stride) return false;
+        for (int j = 0; j < i; j++) if (step[i].at < step[j].at + step[j].len && step[j].at < step[i].at + step[i].len) return false;
+    }
+    std::vector<Seg> segs = {{L.ax_var, 2}, {L.msg_bit0, 8 * (uint64_t)msg_len}, {L.rx_var, 2}, {L.s_bit0, FIELD_BITS}, {L.pad_bit0, 3 * W - 2 * FIELD_BITS - 8 * (uint64_t)msg_len},
+                             {L.validator_var0, VALIDATOR_VARS}, {L.window_var0, 2 * FB_WINDOWS}, {L.fixed_adder_var0, ADD_VARS * (FB_WINDOWS - 1)},
+                             {L.rx_bit0, T_BITS_VARS}, {L.rx_range_var0, T_RANGE_VARS}, {L.ax_bit0, T_BITS_VARS}, {L.ax_range_var0, T_RANGE_VARS},
+                             {L.hash_window_var0, 2 * W}, {L.mont_adder_var0, MADD_VARS * (W - S)}, {L.converter_var0, 2 * S}, {L.edwards_adder_var0, ADD_VARS * (S - 1)},
+                             {L.t_bit0, T_BITS_VARS}, {L.t_range_var0, T_RANGE_VARS}, {L.cond0_var, 2}, {step0, (uint64_t)N_STEPS * L.step_stride}, {L.last_adder_var0, ADD_VARS}};
+    std::sort(segs.begin(), segs.end(), [](const Seg &a, const Seg &b) { return a.at < b.at; });
+    uint64_t end = 1;                                           // variable 0 is ONE
+    for (const Seg &g : segs) {
+        if (g.len == 0) continue;                               // (no padding bits at this msg_len)
+        if (g.at < end) return false;
+        end = g.at + g.len;
+    }
+    return end <= (uint64_t)L.n_vars + 1;
+}
+}  // namespace
+
+extern "C" int zk_eddsa_fill_pure_witnesses(zk_eddsa *v, const uint64_t *A, const uint64_t *R, const uint64_t *s, const uint8_t *msgs, uint32_t n, void *d_w,
+                                            uint64_t row_elems, const zk_eddsa_pure_layout *layout, uint8_t *verdicts) try {
+    if (!v || !A || !R || !s || !msgs || !d_w || !layout || !verdicts) return jfail(ZK_ERR_ARG, "null argument");
+    if (v->scheme != SCHEME_PURE) return jfail(ZK_ERR_ARG, "only a ZK_EDDSA_PURE verifier has a PureEdDSA circuit to fill witnesses of");
+    PureLayout L;
+    memcpy(&L, layout, sizeof(L));
+    if (!pure_layout_fits(L, v->msg_len, row_elems)) return jfail(ZK_ERR_ARG, "the layout does not fit the verifier's msg_len, overlaps itself or leaves the row");
+    if (n == 0) return ZK_OK;
+    if (!all_below_modulus(A, 2 * (uint64_t)n) || !all_below_modulus(R, 2 * (uint64_t)n)) return jfail(ZK_ERR_ARG, "a coordinate is not below the Fr modulus");
+    ZK_TRY(jj_use_device(v->device));
+    const size_t pb = 2 * sizeof(fe) * (size_t)n, sb = sizeof(fe) * (size_t)n, mb = (size_t)n * v->msg_len, mb_al = align32(mb);
+    ZK_TRY(v->scratch.ensure(2 * pb + sb + mb_al + align32(n)));
+    char *d = (char *)v->scratch.p;
+    char *dA = d, *dR = d + pb, *dS = d + 2 * pb, *dM = dS + sb, *dV = dM + mb_al;
+    ZK_HIP(hipMemcpyAsync(dA, A, pb, hipMemcpyHostToDevice, v->st));
+    ZK_HIP(hipMemcpyAsync(dR, R, pb, hipMemcpyHostToDevice, v->st));
+    ZK_HIP(hipMemcpyAsync(dS, s, sb, hipMemcpyHostToDevice, v->st));
+    ZK_HIP(hipMemcpyAsync(dM, msgs, mb, hipMemcpyHostToDevice, v->st));
+    ZK_LAUNCH(k_eddsa_fill_pure, zk_div_up(n, BLOCK), BLOCK, v->st, v->view, v->fbtab, v->mtab, L, (const fe *)dA, (const fe *)dR, (const fe *)dS, (const uint8_t *)dM, n,
+              (fe *)d_w, row_elems, (uint8_t *)dV);
     ZK_HIP(hipGetLastError());
     ZK_HIP(hipMemcpyAsync(verdicts, dV, n, hipMemcpyDeviceToHost, v->st));
     ZK_HIP(hipStreamSynchronize(v->st));

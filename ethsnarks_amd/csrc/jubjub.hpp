@@ -25,7 +25,8 @@
 //   k_jj_point_op     n additions / doublings / negations of affine points
 //   k_jj_pedersen     n windowed Pedersen hashes over a table of affine multiples in device memory, the window count per lane
 //   k_eddsa_verify    n verdicts S B == R + t A, t = H(R, A, M) computed here for the three schemes of eddsa.py
-//   k_eddsa_fill      n complete witness rows of the MiMC-EdDSA circuit, one field inversion per row (at the end of this file)
+//   k_eddsa_fill      n complete witness rows of the MiMC-EdDSA circuit, one field inversion per row
+//   k_eddsa_fill_pure n complete witness rows of the PureEdDSA circuit (in-circuit Pedersen hash), two field inversions per row (at the end of this file)
 #pragma once
 #include "bn254.hpp"
 #include "mimc.hpp"
@@ -496,6 +497,277 @@ k_eddsa_fill(EddsaView v, const fe *__restrict__ fbtab, FillLayout L, const fe *
     val[3 * DBL_VARS + 2] = Fr::canon(jj_mul(rx, rx)); val[3 * DBL_VARS + 3] = Fr::canon(jj_mul(ry, ry));
     {
         const fe *prev = row + L.window_var0;                   // adder i: (window 0 | the previous sum) + window i + 1
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 0; i + 1 < FB_WINDOWS; i++) {
+            fe *blk = row + L.fixed_adder_var0 + ADD_VARS * (size_t)i;
+            const fe *w = row + L.window_var0 + 2 * (size_t)(i + 1);
+            fill_adder(blk, prev[0], prev[1], w[0], w[1]);
+            prev = blk + ADD_VARS - 2;
+        }
+    }
+    {
+        const fe *dprev = row + L.ax_var, *sprev = row + L.cond0_var;
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 1; i <= N_STEPS; i++) {
+            const size_t off = (size_t)(i - 1) * L.step_stride;
+            fe *dbl = row + L.doubler_var0 + off, *cond = row + L.cond_var0 + off, *add = row + L.adder_var0 + off;
+            fill_doubler(dbl, dprev[0], dprev[1]);
+            const bool b = int_bit(t.l, i);
+            cond[0] = b ? dbl[4] : Fr::zero(); cond[1] = b ? dbl[5] : Fr::one();
+            fill_adder(add, sprev[0], sprev[1], cond[0], cond[1]);
+            dprev = dbl + DBL_VARS - 2; sprev = add + ADD_VARS - 2;
+        }
+        fill_adder(row + L.last_adder_var0, rx, ry, sprev[0], sprev[1]);
+    }
+    const fe *lhs = row + L.fixed_adder_var0 + ADD_VARS * (size_t)(FB_WINDOWS - 2) + ADD_VARS - 2, *rhs = row + L.last_adder_var0 + ADD_VARS - 2;
+    verdicts[g] = Fr::eq(lhs[0], rhs[0]) && Fr::eq(lhs[1], rhs[1]) ? 1 : 0;
+}
+
+// ---- the complete witness of the PureEdDSA circuit (jubjub_gadgets.py, eddsa_pure_circuit): the row of k_eddsa_fill with the windowed Pedersen
+// hash in the place of MiMC.  PureLayout is zk_eddsa_pure_layout of zkhip.h; the host has checked it as it checks FillLayout.
+//
+// TWO inversions per witness, whatever the number of windows.  The hash names, per window past the first of a segment, the AFFINE MONTGOMERY
+// running sum (X3, Y3 of a MontgomeryAdder) and the slope lambda = (v2 - v1) / (u2 - u1) that led to it, and per segment the affine Edwards sum
+// (MontgomeryToEdwards).  The lane walks a segment's running sum in extended Edwards coordinates with the mixed additions of k_jj_pedersen and
+// takes every quotient from (X : Y : Z):  u = (Z + Y) / (Z - Y),  v = u Z / X,  u2 - u = (u2 (Z - Y) - (Z + Y)) / (Z - Y), u2 the tabulated
+// Montgomery x of the next window's table point.  One denominator a step, E = (Z - Y) X D3 with D3 = u2 (Z - Y) - (Z + Y) -- or Z at the end of a
+// segment, where 1 / Z gives the converter's Edwards point -- joins the running product of k_eddsa_fill: 1 / (Z - Y) = X D3 / E,
+// 1 / ((Z - Y) X) = D3 / E, 1 / D3 = (Z - Y) X / E.  (X, Y, Z) wait in the adder's three slots, the prefix product and E in the window's two.
+// The first window of a segment is a table point: its step's denominator is u2 - u0, two table values.  No step has a special case (the argument
+// is at FixedBaseMulZcash in jubjub_gadgets.py and in DESIGN 5k).  The first inversion closes the validator, the fixed-base chain and the hash
+// and yields t; the second closes the variable-base chain, which needs the bits of t.
+struct PureLayout {
+    uint32_t msg_len, n_vars, ax_var, msg_bit0, rx_var, s_bit0, pad_bit0, validator_var0, window_var0, fixed_adder_var0, rx_bit0, rx_range_var0,
+             ax_bit0, ax_range_var0, hash_window_var0, mont_adder_var0, converter_var0, edwards_adder_var0, t_bit0, t_range_var0, cond0_var,
+             doubler_var0, cond_var0, adder_var0, step_stride, last_adder_var0;
+};
+constexpr uint32_t MADD_VARS = 3, SEG_ADDERS = SEG_WINDOWS - 1;
+ZK_HD uint32_t pure_windows(uint32_t msg_len) { return (2 * FIELD_BITS + 8 * msg_len + 2) / 3; }
+
+// field2bits_strict and BitsNotAbove(bits, r - 1) of the canonical integer t: 254 bits, 253 results, 254 comparisons at tb; 99 products at range
+ZK_JFN void fill_strict_bits(fe *tb, fe *range, const uint32_t *t) {
+    fe *res = tb + FIELD_BITS, *cmp = res + (FIELD_BITS - 1);
+    uint32_t run = 1, eq = int_bit(t, FIELD_BITS - 1), slot = 0;
+#pragma clang loop unroll(disable)
+    for (int i = FIELD_BITS - 1; i >= 0; i--) {
+        const uint32_t b = int_bit(t, i), c = modulus_m1_bit(i) ? 1u : b;
+        tb[i] = bit_fe(b); cmp[i] = bit_fe(c);
+        run &= c;
+        if (i < (int)FIELD_BITS - 1) res[i] = bit_fe(run);
+        if (i < (int)FIELD_BITS - 1 && i > 0 && modulus_m1_bit(i)) { eq &= b; range[slot++] = bit_fe(eq); }
+    }
+}
+ZK_HD fe neg_if(const fe &a, bool neg) { return neg ? Fr::lneg(a) : a; }
+
+// mtab: per entry of ram_tab the Montgomery form (u, v) = ((1 + y) / (1 - y), u / x) of the table point, canonical Montgomery.  msgs: msg_len
+// bytes an item.  Malformed items, verdicts and the row's form as k_eddsa_fill
+__global__ void __launch_bounds__(BLOCK)
+k_eddsa_fill_pure(EddsaView v, const fe *__restrict__ fbtab, const fe *__restrict__ mtab, PureLayout L, const fe *__restrict__ A, const fe *__restrict__ R,
+                  const fe *__restrict__ s, const uint8_t *__restrict__ msgs, uint32_t n, fe *d_w, uint64_t row_elems, uint8_t *__restrict__ verdicts) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    fe ax, ay, rx, ry;
+    load_point(A, g, ax, ay);
+    load_point(R, g, rx, ry);
+    const uint32_t *__restrict__ sw = s[g].l;
+    if (!on_curve(ax, ay) || !on_curve(rx, ry) || (sw[7] >> 30)) { verdicts[g] = 0; return; }
+    ax = Fr::canon(ax); ay = Fr::canon(ay); rx = Fr::canon(rx); ry = Fr::canon(ry);
+    fe *row = d_w + (size_t)g * row_elems;
+    BitStream bs;
+    bs.rx = R[2 * (size_t)g].l; bs.ax = A[2 * (size_t)g].l; bs.mx = nullptr; bs.msg = msgs + (size_t)g * L.msg_len; bs.msg_bits = 8 * L.msg_len;
+    const uint32_t W = v.ram_windows, lone = W % SEG_WINDOWS == 1 ? 1u : 0u, n_seg = (W - lone + SEG_WINDOWS - 1) / SEG_WINDOWS;
+
+    // ---- the inputs and the two decompositions that feed the hash
+    row[0] = Fr::one();
+    row[L.ax_var] = ax; row[L.ax_var + 1] = ay; row[L.rx_var] = rx; row[L.rx_var + 1] = ry;
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0; i < FIELD_BITS; i++) row[L.s_bit0 + i] = bit_fe(int_bit(sw, i));
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0; i < bs.msg_bits; i++) row[L.msg_bit0 + i] = bit_fe(bs.bit(2 * FIELD_BITS + i));
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0; i < 3 * W - 2 * FIELD_BITS - bs.msg_bits; i++) row[L.pad_bit0 + i] = Fr::zero();
+    fill_strict_bits(row + L.rx_bit0, row + L.rx_range_var0, bs.rx);
+    fill_strict_bits(row + L.ax_bit0, row + L.ax_range_var0, bs.ax);
+
+    // ---- the first set of chains, projective: validator, fixed base, hash
+    fe run = Fr::one();
+    jpoint p;
+    fe *val = row + L.validator_var0;
+    from_affine(p, rx, ry);
+#pragma clang loop unroll(disable)
+    for (uint32_t j = 0; j < 3; j++) { jj_dbl(p, false); park_point(val + DBL_VARS * j, DBL_VARS, p, run); }
+    {
+        const bool nz = !Fr::is_zero(Fr::canon(p.c[0]));
+        const fe x8 = nz ? p.c[0] : Fr::one();
+        val[3 * DBL_VARS] = run; val[3 * DBL_VARS + 1] = x8;
+        run = Fr::lmul(run, x8);
+    }
+    {
+        const fe *e = fbtab + 3 * (size_t)(int_bit(sw, 0) | (int_bit(sw, 1) << 1));
+        row[L.window_var0] = e[0]; row[L.window_var0 + 1] = e[1];
+        from_affine(p, e[0], e[1]);
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 1; i < FB_WINDOWS; i++) {
+            e = fbtab + 3 * ((size_t)4 * i + (int_bit(sw, 2 * i) | (int_bit(sw, 2 * i + 1) << 1)));
+            row[L.window_var0 + 2 * i] = e[0]; row[L.window_var0 + 2 * i + 1] = e[1];
+            jj_add(p, e, true);
+            park_point(row + L.fixed_adder_var0 + ADD_VARS * (size_t)(i - 1), ADD_VARS, p, run);
+        }
+    }
+    fe *hw = row + L.hash_window_var0, *madd = row + L.mont_adder_var0, *conv = row + L.converter_var0, *ed = row + L.edwards_adder_var0;
+    {
+        jpoint hacc;
+        if (lone) {                                             // the last base point's single window: its converter is the table point itself
+            const uint32_t j = W - 1, w = bs.window(j);
+            const fe *e = v.ram_tab + ((size_t)j * 4 + (w & 3)) * 3;
+            const fe x = Fr::canon(neg_if(e[0], w > 3));
+            conv[0] = x; conv[1] = e[1];
+            from_affine(hacc, x, e[1]);
+        }
+#pragma clang loop unroll(disable)
+        for (uint32_t sg = 0; sg < n_seg; sg++) {
+            const uint32_t j0 = sg * SEG_WINDOWS, m = W - lone - j0 < SEG_WINDOWS ? W - lone - j0 : SEG_WINDOWS;   // m >= 2
+            uint32_t w = bs.window(j0);
+            {
+                const fe *e = v.ram_tab + ((size_t)j0 * 4 + (w & 3)) * 3;
+                from_affine(p, neg_if(e[0], w > 3), e[1]);
+            }
+#pragma clang loop unroll(disable)
+            for (uint32_t k = 0; k < m; k++) {
+                const uint32_t j = j0 + k;
+                const bool last = k + 1 == m;
+                const uint32_t w2 = last ? 0u : bs.window(j + 1);
+                const fe u2 = mtab[((size_t)(last ? j : j + 1) * 4 + (w2 & 3)) * 2];
+                fe E;
+                if (k == 0) E = Fr::lsub(u2, mtab[((size_t)j * 4 + (w & 3)) * 2]);
+                else {
+                    fe *blk = madd + MADD_VARS * (size_t)(sg * SEG_ADDERS + k - 1);
+                    blk[0] = p.c[0]; blk[1] = p.c[1]; blk[2] = p.c[3];
+                    const fe d1 = Fr::lsub(p.c[3], p.c[1]);
+                    const fe d3 = last ? p.c[3] : Fr::lsub(Fr::lmul(u2, d1), Fr::ladd(p.c[3], p.c[1]));
+                    E = Fr::lmul(Fr::lmul(d1, p.c[0]), d3);
+                }
+                hw[2 * (size_t)j] = run; hw[2 * (size_t)j + 1] = E;
+                run = Fr::lmul(run, E);
+                if (!last) { pedersen_step(p, v.ram_tab, j + 1, w2); w = w2; }
+            }
+            if (!lone && sg == 0) hacc = p;
+            else {
+                fe q[4];
+                q[0] = p.c[0]; q[1] = p.c[1]; q[2] = jj_mul(coef_d(), p.c[2]); q[3] = p.c[3];
+                jj_add(hacc, q, false);
+                park_point(ed + ADD_VARS * (size_t)(sg - 1 + lone), ADD_VARS, hacc, run);
+            }
+        }
+    }
+
+    // ---- the first inversion and its way back
+    fe inv = jj_inv(run);
+#pragma clang loop unroll(disable)
+    for (int sg = (int)n_seg - 1; sg >= 0; sg--) {
+        const uint32_t j0 = sg * SEG_WINDOWS, m = W - lone - j0 < SEG_WINDOWS ? W - lone - j0 : SEG_WINDOWS;
+        if (lone || sg > 0) unpark_point(ed + ADD_VARS * (size_t)(sg - 1 + lone), ADD_VARS, inv);
+#pragma clang loop unroll(disable)
+        for (int k = (int)m - 1; k >= 0; k--) {
+            const uint32_t j = j0 + k;
+            const bool last = k + 1 == (int)m;
+            fe *win = hw + 2 * (size_t)j;
+            const fe einv = Fr::lmul(inv, win[0]);              // 1 / E of this step
+            inv = Fr::lmul(inv, win[1]);
+            const uint32_t w = bs.window(j), w2 = last ? 0u : bs.window(j + 1);
+            const fe vown = Fr::canon(neg_if(mtab[((size_t)j * 4 + (w & 3)) * 2 + 1], w > 3));
+            const fe *m2 = mtab + ((size_t)(last ? j : j + 1) * 4 + (w2 & 3)) * 2;
+            const fe u2 = m2[0], v2 = neg_if(m2[1], w2 > 3);
+            if (k == 0) madd[MADD_VARS * (size_t)(sg * SEG_ADDERS)] = Fr::canon(Fr::lmul(Fr::lsub(v2, vown), einv));
+            else {
+                fe *blk = madd + MADD_VARS * (size_t)(sg * SEG_ADDERS + k - 1);
+                const fe X = blk[0], Y = blk[1], Z = blk[2];
+                const fe d1 = Fr::lsub(Z, Y), zpy = Fr::ladd(Z, Y);
+                const fe d3 = last ? Z : Fr::lsub(Fr::lmul(u2, d1), zpy);
+                const fe i2 = Fr::lmul(einv, d3), i1 = Fr::lmul(i2, X);                  // 1 / ((Z - Y) X), 1 / (Z - Y)
+                const fe i3 = Fr::lmul(einv, Fr::lmul(d1, X));                            // 1 / D3
+                const fe vv = Fr::lmul(Fr::lmul(zpy, Z), i2);
+                blk[1] = Fr::canon(Fr::lmul(zpy, i1)); blk[2] = Fr::canon(vv);
+                if (last) {
+                    fe *c = conv + 2 * (size_t)(sg + lone);
+                    c[0] = Fr::canon(Fr::lmul(X, i3)); c[1] = Fr::canon(Fr::lmul(Y, i3));
+                } else blk[MADD_VARS] = Fr::canon(Fr::lmul(Fr::lsub(v2, vv), Fr::lmul(i3, d1)));   // the next adder's lambda
+            }
+            win[0] = bit_fe((w & 3) == 3); win[1] = vown;
+        }
+    }
+    if (lone) {
+        const uint32_t j = W - 1, w = bs.window(j);
+        hw[2 * (size_t)j] = bit_fe((w & 3) == 3);
+        hw[2 * (size_t)j + 1] = Fr::canon(neg_if(mtab[((size_t)j * 4 + (w & 3)) * 2 + 1], w > 3));
+    }
+#pragma clang loop unroll(disable)
+    for (uint32_t i = FB_WINDOWS - 1; i >= 1; i--) unpark_point(row + L.fixed_adder_var0 + ADD_VARS * (size_t)(i - 1), ADD_VARS, inv);
+    {
+        fe *blk8 = val + 2 * DBL_VARS;
+        const bool nz = !Fr::is_zero(Fr::canon(blk8[4]));
+        const fe xi = Fr::lmul(inv, val[3 * DBL_VARS]);
+        inv = Fr::lmul(inv, val[3 * DBL_VARS + 1]);
+        val[3 * DBL_VARS] = bit_fe(nz);
+        val[3 * DBL_VARS + 1] = nz ? Fr::canon(Fr::lmul(blk8[0], xi)) : Fr::zero();
+    }
+#pragma clang loop unroll(disable)
+    for (int j = 2; j >= 0; j--) unpark_point(val + DBL_VARS * j, DBL_VARS, inv);
+
+    // ---- the Edwards adders over the converted segments; t = the x of the last, its bits
+    const uint32_t n_conv = n_seg + lone;
+    {
+        const fe *prev = conv;
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 0; i + 1 < n_conv; i++) {
+            fe *blk = ed + ADD_VARS * (size_t)i;
+            fill_adder(blk, prev[0], prev[1], conv[2 * (size_t)(i + 1)], conv[2 * (size_t)(i + 1) + 1]);
+            prev = blk + ADD_VARS - 2;
+        }
+    }
+    const fe t = jj_from_mont(ed[ADD_VARS * (size_t)(n_conv - 2) + ADD_VARS - 2]);
+    fill_strict_bits(row + L.t_bit0, row + L.t_range_var0, t.l);
+
+    // ---- the second set: variable base and R + t A
+    run = Fr::one();
+    {
+        jpoint d;
+        from_affine(d, ax, ay);
+        const uint32_t b0 = int_bit(t.l, 0);
+        row[L.cond0_var] = b0 ? ax : Fr::zero(); row[L.cond0_var + 1] = b0 ? ay : Fr::one();
+        from_affine(p, row[L.cond0_var], row[L.cond0_var + 1]);
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 1; i <= N_STEPS; i++) {
+            const size_t off = (size_t)(i - 1) * L.step_stride;
+            jj_dbl(d, true);
+            park_point(row + L.doubler_var0 + off, DBL_VARS, d, run);
+            const bool b = int_bit(t.l, i);
+            fe q[4];
+            q[0] = b ? d.c[0] : Fr::zero(); q[1] = b ? d.c[1] : Fr::one(); q[2] = b ? jj_mul(coef_d(), d.c[2]) : Fr::zero(); q[3] = b ? d.c[3] : Fr::one();
+            jj_add(p, q, false);
+            park_point(row + L.adder_var0 + off, ADD_VARS, p, run);
+        }
+        fe q[3];
+        q[0] = rx; q[1] = ry; q[2] = jj_mul(coef_d(), jj_mul(rx, ry));
+        jj_add(p, q, true);
+        park_point(row + L.last_adder_var0, ADD_VARS, p, run);
+    }
+    inv = jj_inv(run);
+    unpark_point(row + L.last_adder_var0, ADD_VARS, inv);
+#pragma clang loop unroll(disable)
+    for (uint32_t i = N_STEPS; i >= 1; i--) {
+        const size_t off = (size_t)(i - 1) * L.step_stride;
+        unpark_point(row + L.adder_var0 + off, ADD_VARS, inv);
+        unpark_point(row + L.doubler_var0 + off, DBL_VARS, inv);
+    }
+
+    // ---- the products of affine inputs
+    fill_doubler(val, rx, ry);
+    fill_doubler(val + DBL_VARS, val[4], val[5]);
+    fill_doubler(val + 2 * DBL_VARS, val[DBL_VARS + 4], val[DBL_VARS + 5]);
+    val[3 * DBL_VARS + 2] = Fr::canon(jj_mul(rx, rx)); val[3 * DBL_VARS + 3] = Fr::canon(jj_mul(ry, ry));
+    {
+        const fe *prev = row + L.window_var0;
 #pragma clang loop unroll(disable)
         for (uint32_t i = 0; i + 1 < FB_WINDOWS; i++) {
             fe *blk = row + L.fixed_adder_var0 + ADD_VARS * (size_t)i;

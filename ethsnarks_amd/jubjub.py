@@ -7,7 +7,9 @@ the curve raises ZkError (ZK_ERR_ARG) in scalar_mul / point_add / point_double /
 the A or R of a signature -- the reference never checks and divides by zero there; everything on the curve behaves as the reference does.
 
 EdDSAVerifier("mimc").circuit() is the R1CS that proves such a signature (jubjub_gadgets.eddsa_mimc_circuit) and fill_witnesses writes the
-complete witness rows of a batch into the device buffer that ProverContext.submit_batch(device_ptr=...) proves from.  There is no signer.
+complete witness rows of a batch into the device buffer that ProverContext.submit_batch(device_ptr=...) proves from.
+EdDSAVerifier("pure").pedersen_circuit() and fill_pedersen_witnesses are the same pair for the reference's PureEdDSA gadget, whose hash is the
+windowed Pedersen hash in the circuit (jubjub_gadgets.eddsa_pure_circuit, k_eddsa_fill_pure).  There is no signer.
 """
 import ctypes as C
 
@@ -28,12 +30,18 @@ IDENTITY = (0, 1)
 SCHEMES = {"mimc": 0, "pure": 1, "hash": 2}                     # ZK_EDDSA_*
 _OPS = {"add": 0, "double": 1, "negate": 2}                     # ZK_JJ_OP_*
 _SYMBOLS = ("zk_jj_hash_to_point", "zk_jj_pedersen_basepoint", "zk_jj_point_op", "zk_jj_scalar_mul", "zk_pedersen_create", "zk_pedersen_free",
-            "zk_pedersen_hash", "zk_pedersen_table", "zk_eddsa_create", "zk_eddsa_free", "zk_eddsa_verify_batch", "zk_eddsa_fill_witnesses")
+            "zk_pedersen_hash", "zk_pedersen_table", "zk_eddsa_create", "zk_eddsa_free", "zk_eddsa_verify_batch", "zk_eddsa_fill_witnesses",
+            "zk_eddsa_fill_pure_witnesses")
 
 
 class EddsaLayout(C.Structure):
     """zk_eddsa_layout: where the segments of a witness row of the MiMC-EdDSA circuit start (jubjub_gadgets.EddsaLayout, field for field)"""
     _fields_ = [(n, C.c_uint32) for n in JG.LAYOUT_FIELDS]
+
+
+class EddsaPureLayout(C.Structure):
+    """zk_eddsa_pure_layout: the segments of a witness row of the PureEdDSA circuit (jubjub_gadgets.EddsaPureLayout, field for field)"""
+    _fields_ = [(n, C.c_uint32) for n in JG.PURE_LAYOUT_FIELDS]
 
 
 def generator():
@@ -59,6 +67,7 @@ def _lib():
     lib.zk_eddsa_free.restype = None
     lib.zk_eddsa_verify_batch.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p]
     lib.zk_eddsa_fill_witnesses.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.zk_eddsa_fill_pure_witnesses.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     return lib
 
 
@@ -225,6 +234,7 @@ class EdDSAVerifier:
         self.msg_len = int(msg_len)
         self.B = (int(B[0]), int(B[1])) if B is not None else None
         self._circuit = None
+        self._pedersen_circuit = None
         self._h = C.c_void_p()
         b = _point_limbs([B]) if B is not None else None
         P._check(self._lib.zk_eddsa_create(SCHEMES[scheme], _ptr(b) if b is not None else None, self.msg_len, int(device), C.byref(self._h)))
@@ -290,6 +300,48 @@ class EdDSAVerifier:
         verdicts = np.full(max(n, 1), 255, dtype=np.uint8)
         P._check(self._lib.zk_eddsa_fill_witnesses(self._h, _ptr(a), _ptr(r), _ptr(s), _ptr(m), n, C.c_void_p(ptr), C.c_uint64(int(row_elems)),
                                                    C.byref(EddsaLayout(*lay)), _ptr(verdicts)))
+        return [bool(v) for v in verdicts[:n]], out
+
+    def _pedersen_circuit_object(self):
+        if self.scheme != "pure":
+            raise NotImplementedError('only the "pure" scheme has a circuit with the Pedersen hash in it; "mimc" has circuit(), "hash" has '
+                                      'jubjub_gadgets.EddsaHashCircuit and no device fill')
+        if self._pedersen_circuit is None:
+            self._pedersen_circuit = JG.EddsaPureCircuit(self.msg_len, self.B)
+        return self._pedersen_circuit
+
+    def pedersen_circuit(self):
+        """(R1CS, layout) of the PureEdDSA circuit that accepts this verifier's signatures: jubjub_gadgets.eddsa_pure_circuit for its msg_len and
+        B.  Public inputs: A.x, A.y, the 8 msg_len message bits.  layout: a jubjub_gadgets.EddsaPureLayout; a row has layout.n_vars + 1 elements.
+        (circuit() keeps its meaning: the MiMC circuit, which only "mimc" has)"""
+        c = self._pedersen_circuit_object()
+        return c.r1cs(), c.layout
+
+    def fill_pedersen_witnesses(self, A, sigs, msgs, out=None, row_elems=None, layout=None):
+        """fill_witnesses for the PureEdDSA circuit: the complete rows of a batch written on the device, Montgomery, ready for
+        submit_batch(device_ptr=...).  Returns (verdicts, out).  A wrong signature still gets its row; an item with A or R off the curve or
+        s >= 2^254 gets the verdict False and its row is left as it was.  A, sigs, msgs as verify(); the circuit, unlike verify(), refuses an R of
+        low order and takes any s below 2^254"""
+        c = self._pedersen_circuit_object()
+        A, sigs, msgs, n = self._items(A, sigs, msgs)
+        lay = c.layout if layout is None else layout
+        if row_elems is None:
+            row_elems = lay.n_vars + 1
+        msgs = [bytes(m) for m in msgs]
+        if any(len(m) != self.msg_len for m in msgs):
+            raise ValueError("a message does not have msg_len bytes")
+        if out is None:
+            out = P.DeviceBuffer(32 * int(row_elems) * max(n, 1))
+        if isinstance(out, P.DeviceBuffer) and n * int(row_elems) * 32 > out.nbytes:
+            raise ValueError("the device buffer is smaller than n rows")
+        ptr = out.ptr if isinstance(out, P.DeviceBuffer) else int(out)
+        a = _point_limbs(A)
+        r = _point_limbs([R for R, _ in sigs])
+        s = F.ints_to_limbs([int(v) for _, v in sigs]) if n else np.zeros((0, 4), dtype=np.uint64)
+        m = np.frombuffer(b"".join(msgs), dtype=np.uint8).copy() if n else np.zeros(1, dtype=np.uint8)
+        verdicts = np.full(max(n, 1), 255, dtype=np.uint8)
+        P._check(self._lib.zk_eddsa_fill_pure_witnesses(self._h, _ptr(a), _ptr(r), _ptr(s), _ptr(m), n, C.c_void_p(ptr), C.c_uint64(int(row_elems)),
+                                                        C.byref(EddsaPureLayout(*lay)), _ptr(verdicts)))
         return [bool(v) for v in verdicts[:n]], out
 
     def verify(self, A, sigs, msgs):

@@ -64,9 +64,10 @@ extern "C" {
  * 6: zk_mtree_fill_full_witnesses.
  * 7: zk_wplan_probe_program.
  * 8: zk_eddsa_fill_witnesses and zk_eddsa_layout.
+ * 9: zk_eddsa_fill_pure_witnesses and zk_eddsa_pure_layout.
  * A client checks zk_abi_version() == ZK_ABI_VERSION once after loading the library, or passes the size of the zk_config
  * it was compiled with to zk_ctx_create_sized (members it does not know read as 0 = their defaults). */
-#define ZK_ABI_VERSION 8
+#define ZK_ABI_VERSION 9
 
 typedef struct zk_pk zk_pk;
 typedef struct zk_vk zk_vk;
@@ -524,6 +525,27 @@ typedef struct {
 } zk_eddsa_layout;
 int zk_eddsa_fill_witnesses(zk_eddsa *v, const uint64_t *A /* n x 8 */, const uint64_t *R /* n x 8 */, const uint64_t *s /* n x 4 */, const uint64_t *msgs /* n x msg_len x 4 */,
                             uint32_t n, void *d_w, uint64_t row_elems, const zk_eddsa_layout *layout, uint8_t *verdicts /* n */);
+/* The PureEdDSA circuit (ZK_EDDSA_PURE only) -- eddsa_pure_circuit of ethsnarks_amd/jubjub_gadgets.py, the reference's PureEdDSA gadget: PointValidator(R),
+ * fixed_base_mul(B, the 254 bits of s), field2bits_strict of R.x and of A.x, the windowed Pedersen hash "EdDSA_Verify.RAM" of those bits and the
+ * message bits IN THE CIRCUIT (fixed_base_mul_zcash: lookup_signed_3bit, MontgomeryAdder, MontgomeryToEdwards, PointAdder), field2bits_strict of its
+ * x, a range check behind each of the three decompositions, ScalarMult(A, bits of t), PointAdder(R, t A), lhs == rhs.  With W = ceil((508 + 8 msg_len) / 3)
+ * windows and S = ceil(W / 62) segments, first variable of each segment of a row: A.x, A.y | 8 msg_len message bits (a byte's most significant first) |
+ * R.x, R.y | 254 bits of s | 3 W - 508 - 8 msg_len zero padding bits | validator (22) | 127 x (x, y) | 126 x 7 | R.x: 254 bits, 253 results, 254
+ * comparisons | 99 range products | A.x likewise | W x (b0b1, Montgomery y) | (W - S) x (lambda, X3, Y3) | S x (x, y) of the converters, the lone last
+ * window's first | (S - 1) x 7 Edwards adder variables | t likewise | conditionals[0] (2) | per step doubler (6), conditional (2), adder (7), step_stride
+ * apart | the last adder (7).
+ * zk_eddsa_fill_pure_witnesses is zk_eddsa_fill_witnesses for this circuit, with the same contract: the front end defines every offset; ZK_ERR_ARG and
+ * nothing written for a handle that is not ZK_EDDSA_PURE, row_elems < n_vars + 1, a layout whose msg_len is not the verifier's, a segment outside
+ * variables 1 .. n_vars or overlapping another, a coordinate >= r; a well-formed wrong signature gets its full row and verdict 0; a malformed item
+ * (A or R off the curve, s >= 2^254) gets verdict 0 and an untouched row; verdicts[i] is zk_eddsa_verify_batch's.  One kernel launch, one lane per
+ * signature, TWO field inversions per witness whatever the number of windows (csrc/jubjub.hpp k_eddsa_fill_pure). */
+typedef struct {
+    uint32_t msg_len, n_vars, ax_var, msg_bit0, rx_var, s_bit0, pad_bit0, validator_var0, window_var0, fixed_adder_var0, rx_bit0, rx_range_var0,
+             ax_bit0, ax_range_var0, hash_window_var0, mont_adder_var0, converter_var0, edwards_adder_var0, t_bit0, t_range_var0, cond0_var,
+             doubler_var0, cond_var0, adder_var0, step_stride, last_adder_var0;
+} zk_eddsa_pure_layout;
+int zk_eddsa_fill_pure_witnesses(zk_eddsa *v, const uint64_t *A /* n x 8 */, const uint64_t *R /* n x 8 */, const uint64_t *s /* n x 4 */, const uint8_t *msgs /* n x msg_len bytes */,
+                                 uint32_t n, void *d_w, uint64_t row_elems, const zk_eddsa_pure_layout *layout, uint8_t *verdicts /* n */);
 
 /* ---- measurement aids (bench.py): kernel launches issued by this library so far; between zk_profile_begin() and
  * zk_profile_end() every launch is bracketed by a HIP event pair on its own stream -- the sum of the kernel durations

@@ -2,8 +2,11 @@
 event pairs after a warm-up call at n = 1, 32, 1 024 and 2^14, the field products per witness from the formulas, the fraction of a product-chain
 rate (tools/mulbench, "mul chain 8 waves/SIMD", passed as --chain in G/s) that the kernel reaches, the time of submit_batch + collect for the
 same k on the same circuit, and the front end's generate_r1cs_witness per signature on the CPU.  Prints the table and, with --out, also writes it to that file: profiles/eddsa_circuit.txt is such a run.
+--scheme pure measures the PureEdDSA circuit instead (zk_eddsa_fill_pure_witnesses, k_eddsa_fill_pure; msg_len in bytes); profiles/eddsa_pure_circuit.txt
+holds both schemes from one session.
 
     python tools/eddsa_circuit_bench.py --chain 142.4 --out profiles/eddsa_circuit.txt
+    python tools/eddsa_circuit_bench.py --scheme pure --chain 142.4
 """
 import argparse
 import os
@@ -35,12 +38,38 @@ def products(msg_len):
     }
 
 
+def products_pure(msg_len):
+    """field products of one lane of k_eddsa_fill_pure, part by part.  A segment of m windows: forward 1 (x y) + 9 (m - 1) mixed additions + m
+    (the running product) + 3 (m - 2) + 2 (the denominators E); back 2 m + 1 (lambda of the first adder) + 10 (m - 2) + 9 (the last, with the
+    converter)"""
+    steps, fixed = 253, 126
+    W = (508 + 8 * msg_len + 2) // 3
+    lone = 1 if W % 62 == 1 else 0
+    seg = [min(62, W - lone - j) for j in range(0, W - lone, 62)]
+    n_ed = len(seg) + lone - 1
+    return {
+        "inputs: conversions, two curve equations": 4 + 2 * CURVE,
+        "validator: three doublings, x of 8 R": 1 + 3 * (DBL + 1) + 1,
+        "fixed base: 126 mixed additions": 1 + fixed * (MIXED + 1),
+        "hash, forward: %d windows in %d segments, 13 m - 12 each; %d Edwards additions" % (W, len(seg), n_ed): sum(13 * m - 12 for m in seg) + lone + n_ed * (1 + ADD + 1),
+        "the first inversion": INV,
+        "hash, back: 12 m - 10 a segment, 4 an Edwards addition": sum(12 * m - 10 for m in seg) + 4 * n_ed,
+        "the way back of validator and fixed base": 4 * (3 + fixed) + 3,
+        "Edwards adders of the hash (5 each), t": 5 * n_ed + 1,
+        "variable base: 253 x (doubling, d T, addition), R + t A": 2 + steps * (DBL_T + 1 + 1 + ADD + 1) + 2 + MIXED + 1,
+        "the second inversion": INV,
+        "its way back: 4 per parked point": 4 * (2 * steps + 1),
+        "gadget products: 5 per doubler, 5 per adder, xx, yy": 5 * (3 + steps) + 5 * (fixed + steps + 1) + 2,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--chain", type=float, required=True, help="product-chain rate of the same session in G products/s")
     ap.add_argument("--sizes", type=int, nargs="*", default=[1, 32, 1024, 1 << 14])
     ap.add_argument("--prove-up-to", type=int, default=32, help="largest k that is also proven (submit_batch + collect)")
     ap.add_argument("--msg-len", type=int, default=1)
+    ap.add_argument("--scheme", choices=["mimc", "pure"], default="mimc")
     ap.add_argument("--out", help="also write every printed line to this file")
     a = ap.parse_args()
     out = open(a.out, "w") if a.out else None
@@ -51,18 +80,21 @@ def main():
             out.write(line + "\n")
             out.flush()
     L = J._lib()
-    parts = products(a.msg_len)
+    pure = a.scheme == "pure"
+    parts = products_pure(a.msg_len) if pure else products(a.msg_len)
     total = sum(parts.values())
-    emit("%s, chain rate %.2f G products/s, msg_len %d" % (L.zk_version().decode(), a.chain, a.msg_len))
+    emit("%s, scheme %s, chain rate %.2f G products/s, msg_len %d" % (L.zk_version().decode(), a.scheme, a.chain, a.msg_len))
     for label, v in parts.items():
         emit("    %6d  %s" % (v, label))
-    emit("    %6d  products per witness, %d inversion" % (total, 1))
+    emit("    %6d  products per witness, %d inversion%s" % (total, 2 if pure else 1, "s" if pure else ""))
     prng = random.Random(8)
-    signed = [JC.sign("mimc", JC.make_msg("mimc", a.msg_len, prng), prng.randrange(1, JC.L)) for _ in range(32)]
+    signed = [JC.sign(a.scheme, JC.make_msg(a.scheme, a.msg_len, prng), prng.randrange(1, JC.L)) for _ in range(32)]
     signed = [(A, (R, s % (1 << 254)), m) for A, (R, s), m in signed]
-    with J.EdDSAVerifier("mimc", msg_len=a.msg_len) as v:
-        r, lay = v.circuit()
-        c = v._circuit
+    with J.EdDSAVerifier(a.scheme, msg_len=a.msg_len) as v:
+        r, lay = v.pedersen_circuit() if pure else v.circuit()
+        c = v._pedersen_circuit if pure else v._circuit
+        fill = v.fill_pedersen_witnesses if pure else v.fill_witnesses
+        want = [JC.verify(a.scheme, x[0], x[1], x[2]) for x in signed]
         t0 = time.perf_counter()
         for A, (R, s), m in signed[:8]:
             c.assign(A, R, s, m)
@@ -74,17 +106,16 @@ def main():
             items = [signed[i % 32] for i in range(n)]
             A, sigs, msgs = [x[0] for x in items], [x[1] for x in items], [x[2] for x in items]
             buf = P.DeviceBuffer(32 * (r.V + 1) * n)
-            verdicts, _ = v.fill_witnesses(A, sigs, msgs, buf)           # warm-up: code object, scratch
+            verdicts, _ = fill(A, sigs, msgs, buf)                       # warm-up: code object, scratch
             P.profile_begin()
             t0 = time.perf_counter()
-            verdicts, _ = v.fill_witnesses(A, sigs, msgs, buf)
+            verdicts, _ = fill(A, sigs, msgs, buf)
             wall = 1e3 * (time.perf_counter() - t0)
             ms, launches, _ = P.profile_end()
             rate = n * total / (ms * 1e-3) / 1e9
             line = "fill n = %6d: kernel %9.3f ms (%d launch), call %9.3f ms, %9.0f witnesses/s, %6.2f G products/s = %.3f of the chain rate" % (
                 n, ms, launches, wall, n / (ms * 1e-3), rate, rate / a.chain)
-            assert sum(verdicts) == sum(JC.verify("mimc", x[0], x[1], x[2]) for x in items[:32]) * (n // 32) + sum(
-                JC.verify("mimc", x[0], x[1], x[2]) for x in items[:n % 32])
+            assert sum(verdicts) == sum(want) * (n // 32) + sum(want[:n % 32])
             if n <= a.prove_up_to:
                 ctx = P.ProverContext(pk, r, max_batch=n)
                 ctx.submit_batch(None, device_ptr=buf.ptr, k=n)
