@@ -283,6 +283,125 @@ struct Field {
     static __device__ __forceinline__ fe lmul4(const fe &a, const fe &b, const fe &c, const fe &d, const fe &e, const fe &f, const fe &g, const fe &h) {
         const fe *const op[8] = {&a, &b, &c, &d, &e, &f, &g, &h}; return mul_fips_n<4, false>(op);
     }
+    // ---- lazy Karatsuba pieces of the Fq2 product (Fq2::lmul / lmul2 call lmul_k / lmul2_k).  With v0 = a0 b0, v1 = a1 b1 and
+    // v2 = (a0 + a1)(b0 + b1) as UNREDUCED 16-limb integers,  c0 = REDC(v0 - v1)  and  c1 = REDC(v2 - v0 - v1):  three integer
+    // products and two reductions, 3 x 64 + 2 x 72 multiplies against the schoolbook form's 4 x 64 + 2 x 72, and no negated operand.
+    //   * v0 and v1 come out of a product scanning without the m * p terms (mul_wide).
+    //   * fips::karat_comb8_* turns them, in one pass and in place, into d = v0 - v1 mod 2^512 (with the borrow as a mask) and
+    //     w = ~(v0 + v1) = 2^512 - 1 - (v0 + v1).
+    //   * redc_inj<0> reduces d.  Where the difference wrapped, the eight result limbs hold t mod 2^256 for t = (v0 - v1 + m p)/R in
+    //     (-4p^2/R, p) = (-0.76p, p), so adding p under the mask gives (0.24p, 2p); without a borrow t is in [0, (4p^2 + Rp)/R) =
+    //     [0, 1.76p).  Either way the value is loose with NO fold.  (Two-term form: t in (-1.51p, p) gets 2p, (0.49p, 3p); else
+    //     [0, 2.51p): one fold by 2p.)
+    //   * redc_inj<NP> scans the columns of the sum product(s) with w's limb added to every column's addend and 1 to column 0:
+    //     v2 + w + 1 = v2 - v0 - v1 + 2^512, and the 2^512 leaves as the carry out of column 15, which nothing keeps.  v2 - v0 - v1 =
+    //     a0 b1 + a1 b0 is below 8p^2 (16p^2 for two terms): the bounds, and the folds, of lmul2 (lmul4).
+    // Operands may be anything up to 2p INCLUSIVE (lneg_op values): the sums reach 4p < 2^256 and every bound above holds with <=.
+    template <int NP>
+    static __device__ __forceinline__ void mul_wide(uint32_t (&v)[16], const fe *const (&op)[2 * NP]) {
+        uint64_t lo, ad; uint32_t hi;
+        fips::mul1_vv(lo, op[0]->l[0], op[1]->l[0]);
+        if constexpr (NP == 2) { fips::mac1_vv_sethi(lo, hi, op[2]->l[0], op[3]->l[0]); ad = next_addend(lo, hi); } else ad = lo >> 32;
+        v[0] = (uint32_t)lo;
+#define ZK_COL(N, J0, I) \
+        col_ab_set<N, J0, I>(lo, hi, ad, *op[0], *op[1]); \
+        if constexpr (NP == 2) col_ab<N, J0, I>(lo, hi, *op[2], *op[3]); \
+        v[I] = (uint32_t)lo; \
+        ad = next_addend(lo, hi);
+        ZK_COL(2, 0, 1) ZK_COL(3, 0, 2) ZK_COL(4, 0, 3) ZK_COL(5, 0, 4) ZK_COL(6, 0, 5) ZK_COL(7, 0, 6) ZK_COL(8, 0, 7)
+        ZK_COL(7, 1, 8) ZK_COL(6, 2, 9) ZK_COL(5, 3, 10) ZK_COL(4, 4, 11) ZK_COL(3, 5, 12) ZK_COL(2, 6, 13) ZK_COL(1, 7, 14)
+#undef ZK_COL
+        v[15] = (uint32_t)ad;
+    }
+    template <int N, int J0, int I>
+    static __device__ __forceinline__ void col_mp_set(uint64_t &lo, uint32_t &hi, uint64_t ad, const uint32_t (&m)[8]) {
+#define ZK_MP(k) m[J0 + k], P::p(I - J0 - k)
+        if constexpr (N == 1) fips::mac1_vs_set(lo, hi, ad, ZK_MP(0));
+        if constexpr (N == 2) fips::mac2_vs_set(lo, hi, ad, ZK_MP(0), ZK_MP(1));
+        if constexpr (N == 3) fips::mac3_vs_set(lo, hi, ad, ZK_MP(0), ZK_MP(1), ZK_MP(2));
+        if constexpr (N == 4) fips::mac4_vs_set(lo, hi, ad, ZK_MP(0), ZK_MP(1), ZK_MP(2), ZK_MP(3));
+        if constexpr (N == 5) fips::mac5_vs_set(lo, hi, ad, ZK_MP(0), ZK_MP(1), ZK_MP(2), ZK_MP(3), ZK_MP(4));
+        if constexpr (N == 6) fips::mac6_vs_set(lo, hi, ad, ZK_MP(0), ZK_MP(1), ZK_MP(2), ZK_MP(3), ZK_MP(4), ZK_MP(5));
+        if constexpr (N == 7) fips::mac7_vs_set(lo, hi, ad, ZK_MP(0), ZK_MP(1), ZK_MP(2), ZK_MP(3), ZK_MP(4), ZK_MP(5), ZK_MP(6));
+#undef ZK_MP
+    }
+    // eight limbs of (T + [NP > 0: sum of NP products + 1] + m p) / R mod 2^256, T a 16-limb integer taken modulo 2^512; no fold
+    template <int NP>
+    static __device__ __forceinline__ fe redc_inj(const fe *const *op, const uint32_t (&T)[16]) {
+        uint64_t lo, ad; uint32_t hi;
+        uint32_t m[8], t[8];
+        if constexpr (NP == 0) lo = T[0];
+        else {
+            lo = (uint64_t)T[0] + 1;
+            fips::mac1_vv_sethi(lo, hi, op[0]->l[0], op[1]->l[0]);
+            if constexpr (NP == 2) fips::mac1_vv(lo, hi, op[2]->l[0], op[3]->l[0]);
+        }
+        m[0] = mont_m((uint32_t)lo);
+        if constexpr (NP == 0) fips::mac1_vs_sethi(lo, hi, m[0], P::p(0)); else fips::mac1_vs(lo, hi, m[0], P::p(0));
+        ad = next_addend(lo, hi) + T[1];
+#define ZK_LOW(I) \
+        if constexpr (NP == 0) col_mp_set<I, 0, I>(lo, hi, ad, m); \
+        else { col_ab_set<I + 1, 0, I>(lo, hi, ad, *op[0], *op[1]); \
+               if constexpr (NP == 2) col_ab<I + 1, 0, I>(lo, hi, *op[2], *op[3]); \
+               col_mp<I, 0, I>(lo, hi, m); } \
+        m[I] = mont_m((uint32_t)lo); \
+        fips::mac1_vs(lo, hi, m[I], P::p(0)); \
+        ad = next_addend(lo, hi) + T[I + 1];
+#define ZK_HIGH(I) \
+        if constexpr (NP == 0) col_mp_set<15 - I, I - 7, I>(lo, hi, ad, m); \
+        else { col_ab_set<15 - I, I - 7, I>(lo, hi, ad, *op[0], *op[1]); \
+               if constexpr (NP == 2) col_ab<15 - I, I - 7, I>(lo, hi, *op[2], *op[3]); \
+               col_mp<15 - I, I - 7, I>(lo, hi, m); } \
+        t[I - 8] = (uint32_t)lo; \
+        ad = next_addend(lo, hi) + T[I + 1];
+        ZK_LOW(1) ZK_LOW(2) ZK_LOW(3) ZK_LOW(4) ZK_LOW(5) ZK_LOW(6) ZK_LOW(7)
+        ZK_HIGH(8) ZK_HIGH(9) ZK_HIGH(10) ZK_HIGH(11) ZK_HIGH(12) ZK_HIGH(13) ZK_HIGH(14)
+#undef ZK_LOW
+#undef ZK_HIGH
+        t[7] = (uint32_t)ad;                               // column 15: the carry of column 14 plus T's top limb, whatever passes 2^32 drops
+        fe r;
+#pragma unroll
+        for (int i = 0; i < 8; i++) r.l[i] = t[i];
+        return r;
+    }
+    // (r0, r1) = (a0 b0 - a1 b1, a0 b1 + a1 b0) [NP = 1], plus the same of (c, d) [NP = 2]: op = {a0, b0, a1, b1} or
+    // {a0, b0, c0, d0, a1, b1, c1, d1}
+    template <int NP>
+    static __device__ __forceinline__ void karatsuba(const fe *const (&op)[4 * NP], fe &r0, fe &r1) {
+        uint32_t w[16], d[16];
+        {
+            uint32_t v1[16];
+            if constexpr (NP == 1) {
+                const fe *const A[2] = {op[0], op[1]}, *const B[2] = {op[2], op[3]};
+                mul_wide<1>(w, A); mul_wide<1>(v1, B);
+            } else {
+                const fe *const A[4] = {op[0], op[1], op[2], op[3]}, *const B[4] = {op[4], op[5], op[6], op[7]};
+                mul_wide<2>(w, A); mul_wide<2>(v1, B);
+            }
+            uint64_t cw, bd;
+            fips::karat_comb8_lo(*(uint32_t (*)[8])&w[0], *(uint32_t (*)[8])&d[0], *(const uint32_t (*)[8])&v1[0], cw, bd);
+            const uint32_t mask = fips::karat_comb8_hi(*(uint32_t (*)[8])&w[8], *(uint32_t (*)[8])&d[8], *(const uint32_t (*)[8])&v1[8], cw, bd);
+            r0 = redc_inj<0>(nullptr, d);
+            if constexpr (NP == 1) { if constexpr (P::is_fq) fips::addp_masked8_fq(r0.l, mask); else fips::addp_masked8_fr(r0.l, mask); }
+            else if constexpr (P::is_fq) { fips::addp_masked8_fq2(r0.l, mask); fips::reduce8_fq2(r0.l); }
+            else { fips::addp_masked8_fr2(r0.l, mask); fips::reduce8_fr2(r0.l); }
+        }
+        fe s[2 * NP];
+#pragma unroll
+        for (int i = 0; i < 2 * NP; i++) fips::add8(s[i].l, op[i]->l, op[2 * NP + i]->l);     // a0 + a1, b0 + b1 (, c0 + c1, d0 + d1): at most 4p
+        const fe *S[2 * NP];
+#pragma unroll
+        for (int i = 0; i < 2 * NP; i++) S[i] = &s[i];
+        r1 = redc_inj<NP>(S, w);
+        if constexpr (P::is_fq) fips::reduce8_fq2(r1.l); else fips::reduce8_fr2(r1.l);
+        if constexpr (NP == 2) { if constexpr (P::is_fq) fips::reduce8_fq2(r1.l); else fips::reduce8_fr2(r1.l); }
+    }
+    static __device__ __forceinline__ void lmul_k(const fe &a0, const fe &a1, const fe &b0, const fe &b1, fe &r0, fe &r1) {
+        const fe *const op[4] = {&a0, &b0, &a1, &b1}; karatsuba<1>(op, r0, r1);
+    }
+    static __device__ __forceinline__ void lmul2_k(const fe &a0, const fe &a1, const fe &b0, const fe &b1, const fe &c0, const fe &c1, const fe &d0, const fe &d1, fe &r0, fe &r1) {
+        const fe *const op[8] = {&a0, &b0, &c0, &d0, &a1, &b1, &c1, &d1}; karatsuba<2>(op, r0, r1);
+    }
     // ---- six-term dot product with a CONSTANT row: x_0 m_0 + ... + x_5 m_5 with one Montgomery reduction (the MIX layer of Poseidon,
     // poseidon.hpp: every output element is such a sum).  The row limbs are wave-uniform and ride in SGPRs (the macN_vs forms the m*p
     // products use), so the 48 limbs of a row cost no VGPR.  6 x 64 + 72 multiplies against 6 x 136 for six products, and no modular additions.
@@ -477,6 +596,69 @@ struct Field {
     static ZK_HD fe ladd(const fe &a, const fe &b) { return add(a, b); }
     static ZK_HD fe lsub(const fe &a, const fe &b) { return sub(a, b); }
     static ZK_HD bool lis_zero(const fe &a) { return is_zero(a); }
+    // the lazy Karatsuba Fq2 product of the device form above, step for step in plain C++ (host code, the CPU emulation, ZK_NO_ASM
+    // builds): unreduced 16-limb products, d = v0 - v1 mod 2^512 with its borrow, w = ~(v0 + v1), REDC of d plus p (2p) under the
+    // borrow, REDC of v2 + w + 1 modulo 2^512.  Operands up to 2p inclusive; the results leave CANONICAL, as every host value is.
+    static ZK_HD void mac_wide_c(uint32_t (&v)[16], const fe &a, const fe &b) {          // v += a b (mod 2^512)
+        for (int i = 0; i < 8; i++) {
+            uint64_t c = 0;
+            for (int j = 0; j < 8; j++) { c += (uint64_t)a.l[i] * b.l[j] + v[i + j]; v[i + j] = (uint32_t)c; c >>= 32; }
+            for (int k = i + 8; k < 16; k++) { c += v[k]; v[k] = (uint32_t)c; c >>= 32; }
+        }
+    }
+    static ZK_HD fe redc_wide_c(uint32_t (&T)[16]) {                                     // limbs 8 .. 15 of T + m p (mod 2^512)
+        for (int i = 0; i < 8; i++) {
+            const uint32_t m = T[i] * P::inv;
+            uint64_t c = 0;
+            for (int j = 0; j < 8; j++) { c += (uint64_t)m * P::p(j) + T[i + j]; T[i + j] = (uint32_t)c; c >>= 32; }
+            for (int k = i + 8; k < 16; k++) { c += T[k]; T[k] = (uint32_t)c; c >>= 32; }
+        }
+        fe r;
+        for (int i = 0; i < 8; i++) r.l[i] = T[8 + i];
+        return r;
+    }
+    static ZK_HD fe add_raw_c(const fe &a, const fe &b) {                                // a + b mod 2^256, no fold
+        fe s; uint64_t c = 0;
+        for (int i = 0; i < 8; i++) { c += (uint64_t)a.l[i] + b.l[i]; s.l[i] = (uint32_t)c; c >>= 32; }
+        return s;
+    }
+    static ZK_HD fe pmul_c(uint32_t k) {                                                 // k p for k = 1, 2
+        fe r;
+        for (int i = 0; i < 8; i++) r.l[i] = k == 1 ? P::p(i) : (P::p(i) << 1) | (i ? P::p(i - 1) >> 31 : 0u);
+        return r;
+    }
+    static ZK_HD fe fold2p_c(const fe &a) {                                              // a - 2p if a >= 2p
+        const fe pp = pmul_c(2);
+        fe d; uint64_t br = 0;
+        for (int i = 0; i < 8; i++) { uint64_t t = (uint64_t)a.l[i] - pp.l[i] - br; d.l[i] = (uint32_t)t; br = (t >> 32) & 1; }
+        return br ? a : d;
+    }
+    template <int NP>
+    static ZK_HD void karatsuba_c(const fe *const (&op)[4 * NP], fe &r0, fe &r1) {       // operand order as the device form's
+        uint32_t v0[16], v1[16], v2[16], d[16], w[16];
+        for (int i = 0; i < 16; i++) v0[i] = v1[i] = v2[i] = 0;
+        for (int k = 0; k < NP; k++) { mac_wide_c(v0, *op[2 * k], *op[2 * k + 1]); mac_wide_c(v1, *op[2 * NP + 2 * k], *op[2 * NP + 2 * k + 1]); }
+        uint64_t br = 0, c = 0;
+        for (int i = 0; i < 16; i++) {
+            uint64_t t = (uint64_t)v0[i] - v1[i] - br; d[i] = (uint32_t)t; br = (t >> 32) & 1;
+            c += (uint64_t)v0[i] + v1[i]; w[i] = ~(uint32_t)c; c >>= 32;
+        }
+        r0 = redc_wide_c(d);
+        if (br) r0 = add_raw_c(r0, pmul_c(NP));
+        if (NP == 2) r0 = fold2p_c(r0);
+        for (int k = 0; k < NP; k++) mac_wide_c(v2, add_raw_c(*op[2 * k], *op[2 * NP + 2 * k]), add_raw_c(*op[2 * k + 1], *op[2 * NP + 2 * k + 1]));
+        c = 1;
+        for (int i = 0; i < 16; i++) { c += (uint64_t)v2[i] + w[i]; v2[i] = (uint32_t)c; c >>= 32; }
+        r1 = fold2p_c(redc_wide_c(v2));
+        if (NP == 2) r1 = fold2p_c(r1);
+        r0 = reduce_once_c(r0); r1 = reduce_once_c(r1);
+    }
+    static ZK_HD void lmul_k(const fe &a0, const fe &a1, const fe &b0, const fe &b1, fe &r0, fe &r1) {
+        const fe *const op[4] = {&a0, &b0, &a1, &b1}; karatsuba_c<1>(op, r0, r1);
+    }
+    static ZK_HD void lmul2_k(const fe &a0, const fe &a1, const fe &b0, const fe &b1, const fe &c0, const fe &c1, const fe &d0, const fe &d1, fe &r0, fe &r1) {
+        const fe *const op[8] = {&a0, &b0, &c0, &d0, &a1, &b1, &c1, &d1}; karatsuba_c<2>(op, r0, r1);
+    }
 #endif
 #if !(defined(__HIP_DEVICE_COMPILE__) && !defined(ZK_NO_ASM))
     static ZK_HD void lmul_x2(const fe &a, const fe &b, const fe &c, const fe &d, fe &r0, fe &r1) { r0 = lmul(a, b); r1 = lmul(c, d); }
@@ -588,14 +770,24 @@ struct Fq2 {
     static ZK_HD fe2 lneg_op(const fe2 &a) { fe2 r; r.c0 = Fq::lneg_op(a.c0); r.c1 = Fq::lneg_op(a.c1); return r; }   // product operand only (Field::lneg_op)
     static ZK_HD fe2 lneg_yop(const fe2 &a) { return lneg_op(a); }
     static ZK_HD fe2 ldbl(const fe2 &a) { return ladd(a, a); }
-    // schoolbook with one reduction per component (Field::lmul2): 4 x 64 + 2 x 72 multiplies and two folds, against
-    // Karatsuba's 3 x 136 multiplies plus five modular additions -- fewer VALU issue slots on gfx950
+    // Lazy Karatsuba (Field::lmul_k): v0 = a0 b0, v1 = a1 b1 and v2 = (a0 + a1)(b0 + b1) stay unreduced 16-limb integers,
+    // c0 = REDC(v0 - v1), c1 = REDC(v2 - v0 - v1): 3 x 64 + 2 x 72 = 336 multiplies and no negated operand, against the schoolbook form's
+    // (one Field::lmul2 per component) 4 x 64 + 2 x 72 = 400.  A Karatsuba of three separately REDUCED products (3 x 136 multiplies and
+    // five modular additions) costs more VALU issue slots than either.  ZK_FQ2_KARATSUBA: 2 (default) lmul and lmul2, 1 lmul only,
+    // 0 the schoolbook forms (kept for same-box A/B builds; measured: profiles/fq2_karatsuba_ab.txt).
+#ifndef ZK_FQ2_KARATSUBA
+#define ZK_FQ2_KARATSUBA 2
+#endif
     static ZK_HD fe2 lmul(const fe2 &a, const fe2 &b) {
         fe2 r;
+#if ZK_FQ2_KARATSUBA >= 1
+        Fq::lmul_k(a.c0, a.c1, b.c0, b.c1, r.c0, r.c1);
+#else
         // (c0 and c1 as a dual-issue pair, Field::lmul2_x2, was measured: no gain -- a two-term dot product at 2 waves/SIMD already
         // runs at 91 % of its issue bound, profiles/r03_dual_issue.txt -- for 10 more VGPRs)
         r.c0 = Fq::lmul2(a.c0, b.c0, a.c1, Fq::lneg_op(b.c1));
         r.c1 = Fq::lmul2(a.c0, b.c1, a.c1, b.c0);
+#endif
         return r;
     }
     static constexpr bool PAIRS = false;                              // the G2 formulas keep their order (see lmul)
@@ -604,8 +796,12 @@ struct Fq2 {
     // a*b + c*d in Fq2, one reduction per component
     static ZK_HD fe2 lmul2(const fe2 &a, const fe2 &b, const fe2 &c, const fe2 &d) {
         fe2 r;
+#if ZK_FQ2_KARATSUBA >= 2
+        Fq::lmul2_k(a.c0, a.c1, b.c0, b.c1, c.c0, c.c1, d.c0, d.c1, r.c0, r.c1);      // six integer products, two reductions
+#else
         r.c0 = Fq::lmul4(a.c0, b.c0, a.c1, Fq::lneg_op(b.c1), c.c0, d.c0, c.c1, Fq::lneg_op(d.c1));
         r.c1 = Fq::lmul4(a.c0, b.c1, a.c1, b.c0, c.c0, d.c1, c.c1, d.c0);
+#endif
         return r;
     }
     static ZK_HD fe2 lsqr(const fe2 &a) {

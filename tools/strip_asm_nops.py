@@ -6,7 +6,7 @@ hipcc cannot see into an asm statement, assumes it may end in an SDWA / op_sel w
 one wait state), and counts the statement itself as zero wait states -- so a chain of dependent asm statements, which is
 what the field arithmetic is (fips_asm.hpp), gets one s_nop per statement: 2-4 % of the accumulation kernels' time
 (DESIGN section 4).  The statements of fips_asm.hpp hold only plain VOP2 / VOP3 integer instructions (v_mad_u64_u32,
-v_addc_co_u32, v_add/sub/and/cndmask/mov): no SDWA, no op_sel, no transcendental, no DPP -- nothing that needs the wait
+v_addc_co_u32, v_add/sub/subb/and/not/cndmask/mov): no SDWA, no op_sel, no transcendental, no DPP -- nothing that needs the wait
 state -- and every statement is at least one VALU instruction long, so a one-wait-state hazard between an instruction
 BEFORE the statement and one after it is satisfied by the statement itself.
 Rules: only `s_nop 0` lines that directly follow `;;#ASMEND` go; not in functions that contain a DPP, SDWA, permlane or
@@ -23,7 +23,8 @@ LANE = re.compile(r"^\s*(v_readlane|v_readfirstlane|v_writelane)")
 # The premise is CHECKED, not assumed: every ;;#ASMSTART .. ;;#ASMEND body must consist of these mnemonics only (plain
 # VOP2 / VOP3 integer instructions, no modifiers); a function whose asm holds anything else keeps all its pads.
 ALLOWED = {"v_mad_u64_u32", "v_addc_co_u32_e64", "v_addc_co_u32_e32", "v_add_co_u32_e32", "v_sub_co_u32_e32", "v_subb_co_u32_e32",
-           "v_cndmask_b32_e32", "v_cndmask_b32_e64", "v_and_b32_e32", "v_mov_b32_e32"}
+           "v_cndmask_b32_e32", "v_cndmask_b32_e64", "v_and_b32_e32", "v_mov_b32_e32",
+           "v_add_co_u32_e64", "v_sub_co_u32_e64", "v_subb_co_u32_e64", "v_not_b32_e32"}      # the 16-limb Karatsuba combination
 MODIFIER = re.compile(r"\b(op_sel|dst_sel|src0_sel|src1_sel|clamp|omod|mul:|div:|neg_lo|neg_hi|byte_sel)")
 # A pad also stays when the instruction after it is a memory store (VMEM / FLAT / DS / scratch write of a just-written VGPR:
 # the > 64-bit store-data hazard counts wait states too), a v_accvgpr_* move or an MFMA: none of them follows a pad in today's
