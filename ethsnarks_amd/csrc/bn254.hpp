@@ -554,6 +554,104 @@ struct Field {
     static __device__ __forceinline__ void lmul2_x2(const fe &a, const fe &b, const fe &c, const fe &d, const fe &e, const fe &f, const fe &g, const fe &h, fe &r0, fe &r1) {
         const fe *const A[4] = {&a, &b, &c, &d}; const fe *const B[4] = {&e, &f, &g, &h}; mul_fips_n_x2<2>(A, B, r0, r1);   // (tools/mulbench.cpp measures it)
     }
+    // ---- dedicated squaring in column form: 36 + 72 multiply-adds instead of 64 + 72.  a^2 = sum_i a_i^2 B^2i + sum_i a_i B^i (2 T_i),
+    // T_i = sum_{j > i} a_j B^j (B = 2^32).  The doubling is done on the OPERAND, never on a column accumulator: with a <= 2p < 2^255 the
+    // integer 2a fits eight limbs d_j = (a_j << 1) | (a_{j-1} >> 31), and the limbs of 2 T_i are d_{i+2} .. d_7 above a_{i+1} << 1 (d_{i+1}
+    // without the bit that a_i, which T_i does not hold, shifted in; T_i <= a < 2^255, so 2 T_i < 2^256 and nothing leaves at the top).  Column I is
+    // therefore  sum_{i < j, i + j = I} a_i y_j  (+ a_{I/2}^2 when I is even),  y_j = a_j << 1 for j = i + 1, else d_j: plain products of
+    // 32-bit words, at most four per column, through the same macN_vv_set / _x2 statements the product uses, followed by the product's own
+    // m * p steps -- the integer summed is a^2 exactly, so m and the result are those of lmul(a, a) bit for bit and the loose contract is
+    // lmul's: a <= 2p gives (4p^2 + Rp)/R < 2p.  Worst column (I = 6 .. 8): 4 + 8 products below 2^64 plus the carried 64 bits, under 13 * 2^64:
+    // the carry word stays below 13 (the product's worst column holds 16 products).  Cost of the doubling: one shift per odd column (the
+    // adjacent pair) and d_2 .. d_7, each made at the column that first reads it (d_j is read in columns j .. 2j - 2: four limbs live at most).
+    template <int I>
+    static __device__ __forceinline__ void col_sq_set(uint64_t &lo, uint32_t &hi, uint64_t ad, const fe &a, const uint32_t (&d)[8]) {
+        constexpr int i0 = I > 7 ? I - 7 : 0, np = (I + 1) / 2 - i0, N = np + 1 - (I & 1);   // np cross terms, then the square in even columns
+        uint32_t x[4], y[4];
+#pragma unroll
+        for (int k = 0; k < np; k++) { const int i = i0 + k, j = I - i; x[k] = a.l[i]; y[k] = j == i + 1 ? a.l[j] << 1 : d[j]; }
+        if constexpr ((I & 1) == 0) x[np] = y[np] = a.l[I / 2];
+        if constexpr (N == 1) fips::mac1_vv_set(lo, hi, ad, x[0], y[0]);
+        if constexpr (N == 2) fips::mac2_vv_set(lo, hi, ad, x[0], y[0], x[1], y[1]);
+        if constexpr (N == 3) fips::mac3_vv_set(lo, hi, ad, x[0], y[0], x[1], y[1], x[2], y[2]);
+        if constexpr (N == 4) fips::mac4_vv_set(lo, hi, ad, x[0], y[0], x[1], y[1], x[2], y[2], x[3], y[3]);
+    }
+    template <int I>
+    static __device__ __forceinline__ void col_sq_set_x2(uint64_t &l0, uint32_t &h0, uint64_t &l1, uint32_t &h1, uint64_t ad0, uint64_t ad1,
+                                                         const fe &a, const uint32_t (&da)[8], const fe &b, const uint32_t (&db)[8]) {
+        constexpr int i0 = I > 7 ? I - 7 : 0, np = (I + 1) / 2 - i0, N = np + 1 - (I & 1);
+        uint32_t x[4], y[4], u[4], v[4];
+#pragma unroll
+        for (int k = 0; k < np; k++) {
+            const int i = i0 + k, j = I - i;
+            x[k] = a.l[i]; y[k] = j == i + 1 ? a.l[j] << 1 : da[j];
+            u[k] = b.l[i]; v[k] = j == i + 1 ? b.l[j] << 1 : db[j];
+        }
+        if constexpr ((I & 1) == 0) { x[np] = y[np] = a.l[I / 2]; u[np] = v[np] = b.l[I / 2]; }
+        if constexpr (N == 1) fips::mac1_vv_set_x2(l0, h0, l1, h1, ad0, ad1, x[0], y[0], u[0], v[0]);
+        if constexpr (N == 2) fips::mac2_vv_set_x2(l0, h0, l1, h1, ad0, ad1, x[0], y[0], x[1], y[1], u[0], v[0], u[1], v[1]);
+        if constexpr (N == 3) fips::mac3_vv_set_x2(l0, h0, l1, h1, ad0, ad1, x[0], y[0], x[1], y[1], x[2], y[2], u[0], v[0], u[1], v[1], u[2], v[2]);
+        if constexpr (N == 4) fips::mac4_vv_set_x2(l0, h0, l1, h1, ad0, ad1, x[0], y[0], x[1], y[1], x[2], y[2], x[3], y[3], u[0], v[0], u[1], v[1], u[2], v[2], u[3], v[3]);
+    }
+    static __device__ __forceinline__ uint32_t dbl_limb(const fe &a, int j) { return (a.l[j] << 1) | (a.l[j - 1] >> 31); }
+    template <bool REDUCE>
+    static __device__ __forceinline__ fe sqr_fips(const fe &a) {
+        uint64_t lo, ad; uint32_t hi;
+        uint32_t m[8], t[8], d[8];                             // d[0], d[1] are never read
+        fips::mul1_vv(lo, a.l[0], a.l[0]);                     // column 0: a_0^2
+        m[0] = mont_m((uint32_t)lo);
+        fips::mac1_vs_sethi(lo, hi, m[0], P::p(0));
+        ad = next_addend(lo, hi);
+#define ZK_LOW(I) \
+        if constexpr (I >= 2) d[I] = dbl_limb(a, I); \
+        col_sq_set<I>(lo, hi, ad, a, d); \
+        col_mp<I, 0, I>(lo, hi, m); \
+        m[I] = mont_m((uint32_t)lo); \
+        fips::mac1_vs(lo, hi, m[I], P::p(0)); \
+        ad = next_addend(lo, hi);
+#define ZK_HIGH(I) \
+        col_sq_set<I>(lo, hi, ad, a, d); \
+        col_mp<15 - I, I - 7, I>(lo, hi, m); \
+        t[I - 8] = (uint32_t)lo; \
+        ad = next_addend(lo, hi);
+        ZK_LOW(1) ZK_LOW(2) ZK_LOW(3) ZK_LOW(4) ZK_LOW(5) ZK_LOW(6) ZK_LOW(7)
+        ZK_HIGH(8) ZK_HIGH(9) ZK_HIGH(10) ZK_HIGH(11) ZK_HIGH(12) ZK_HIGH(13) ZK_HIGH(14)
+#undef ZK_LOW
+#undef ZK_HIGH
+        t[7] = (uint32_t)ad;
+        fe r;
+#pragma unroll
+        for (int i = 0; i < 8; i++) r.l[i] = t[i];
+        if constexpr (REDUCE) return reduce_once(r); else return r;
+    }
+    // two squarings advancing together, as mul_fips_n_x2 does for two products (the PP and R^2 of a G1 mixed addition)
+    static __device__ __forceinline__ void sqr_fips_x2(const fe &a, const fe &b, fe &r0, fe &r1) {
+        uint64_t l0, l1, ad0, ad1; uint32_t h0, h1;
+        uint32_t m0[8], m1[8], t0[8], t1[8], da[8], db[8];
+        fips::mul1_vv_x2(l0, l1, a.l[0], a.l[0], b.l[0], b.l[0]);
+        fips::mullo_vs_x2(m0[0], m1[0], (uint32_t)l0, (uint32_t)l1, P::inv);
+        fips::mac1_vs_sethi_x2(l0, h0, l1, h1, m0[0], m1[0], P::p(0));
+        ad0 = next_addend(l0, h0); ad1 = next_addend(l1, h1);
+#define ZK_LOW(I) \
+        if constexpr (I >= 2) { da[I] = dbl_limb(a, I); db[I] = dbl_limb(b, I); } \
+        col_sq_set_x2<I>(l0, h0, l1, h1, ad0, ad1, a, da, b, db); \
+        col_mp_x2<I, 0, I>(l0, h0, l1, h1, m0, m1); \
+        fips::mullo_vs_x2(m0[I], m1[I], (uint32_t)l0, (uint32_t)l1, P::inv); \
+        fips::mac1_vs_x2(l0, h0, l1, h1, m0[I], m1[I], P::p(0)); \
+        ad0 = next_addend(l0, h0); ad1 = next_addend(l1, h1);
+#define ZK_HIGH(I) \
+        col_sq_set_x2<I>(l0, h0, l1, h1, ad0, ad1, a, da, b, db); \
+        col_mp_x2<15 - I, I - 7, I>(l0, h0, l1, h1, m0, m1); \
+        t0[I - 8] = (uint32_t)l0; t1[I - 8] = (uint32_t)l1; \
+        ad0 = next_addend(l0, h0); ad1 = next_addend(l1, h1);
+        ZK_LOW(1) ZK_LOW(2) ZK_LOW(3) ZK_LOW(4) ZK_LOW(5) ZK_LOW(6) ZK_LOW(7)
+        ZK_HIGH(8) ZK_HIGH(9) ZK_HIGH(10) ZK_HIGH(11) ZK_HIGH(12) ZK_HIGH(13) ZK_HIGH(14)
+#undef ZK_LOW
+#undef ZK_HIGH
+        t0[7] = (uint32_t)ad0; t1[7] = (uint32_t)ad1;
+#pragma unroll
+        for (int i = 0; i < 8; i++) { r0.l[i] = t0[i]; r1.l[i] = t1[i]; }
+    }
 #else
     static ZK_HD fe mul(const fe &a, const fe &b) { return mul_cios(a, b); }
 #endif
@@ -659,6 +757,31 @@ struct Field {
     static ZK_HD void lmul2_k(const fe &a0, const fe &a1, const fe &b0, const fe &b1, const fe &c0, const fe &c1, const fe &d0, const fe &d1, fe &r0, fe &r1) {
         const fe *const op[8] = {&a0, &b0, &c0, &d0, &a1, &b1, &c1, &d1}; karatsuba_c<2>(op, r0, r1);
     }
+    // the column-form squaring of the device form above (sqr_fips), step for step in plain C++: the doubled limbs d_j, per column the cross
+    // terms a_i y_j (y_j = a_j << 1 for the adjacent pair, else d_j) and the square of even columns in a 96-bit accumulator, then the m * p
+    // steps.  Operands up to 2p inclusive; the raw value returned is below 2p (lsqr reduces it: host values are canonical).
+    static ZK_HD void mac96_c(uint64_t &lo, uint32_t &hi, uint32_t x, uint32_t y) {
+        const uint64_t pr = (uint64_t)x * y;
+        lo += pr; hi += lo < pr;
+    }
+    static ZK_HD fe sqr_cols_c(const fe &a) {
+        uint32_t d[8], m[8];
+        fe r;
+        d[0] = a.l[0] << 1;
+        for (int j = 1; j < 8; j++) d[j] = (a.l[j] << 1) | (a.l[j - 1] >> 31);
+        uint64_t lo = 0; uint32_t hi = 0;
+        for (int I = 0; I < 15; I++) {
+            const int i0 = I > 7 ? I - 7 : 0;
+            for (int i = i0; 2 * i < I; i++) mac96_c(lo, hi, a.l[i], I - i == i + 1 ? a.l[I - i] << 1 : d[I - i]);
+            if ((I & 1) == 0) mac96_c(lo, hi, a.l[I / 2], a.l[I / 2]);
+            for (int j = i0; j < (I < 8 ? I : 8); j++) mac96_c(lo, hi, m[j], P::p(I - j));
+            if (I < 8) { m[I] = (uint32_t)lo * P::inv; mac96_c(lo, hi, m[I], P::p(0)); }   // the low word of the column is now 0
+            else r.l[I - 8] = (uint32_t)lo;
+            lo = (lo >> 32) | ((uint64_t)hi << 32); hi = 0;
+        }
+        r.l[7] = (uint32_t)lo;
+        return r;
+    }
 #endif
 #if !(defined(__HIP_DEVICE_COMPILE__) && !defined(ZK_NO_ASM))
     static ZK_HD void lmul_x2(const fe &a, const fe &b, const fe &c, const fe &d, fe &r0, fe &r1) { r0 = lmul(a, b); r1 = lmul(c, d); }
@@ -673,8 +796,17 @@ struct Field {
     static constexpr bool PAIRS = false;
 #endif
     static ZK_HD void lmul_pair(const fe &a, const fe &b, const fe &c, const fe &d, fe &r0, fe &r1) { lmul_x2(a, b, c, d, r0, r1); }
+    // squarings: the dedicated column form (sqr_fips / sqr_fips_x2; sqr_cols_c on the host).  -DZK_FQ_SQR=0 keeps general products (A/B builds)
+#if defined(ZK_FQ_SQR) && !ZK_FQ_SQR
     static ZK_HD void lsqr_pair(const fe &a, const fe &b, fe &r0, fe &r1) { lmul_pair(a, a, b, b, r0, r1); }
     static ZK_HD fe lsqr(const fe &a) { return lmul(a, a); }
+#elif defined(__HIP_DEVICE_COMPILE__) && !defined(ZK_NO_ASM)
+    static __device__ __forceinline__ void lsqr_pair(const fe &a, const fe &b, fe &r0, fe &r1) { sqr_fips_x2(a, b, r0, r1); }
+    static __device__ __forceinline__ fe lsqr(const fe &a) { return sqr_fips<false>(a); }
+#else
+    static ZK_HD void lsqr_pair(const fe &a, const fe &b, fe &r0, fe &r1) { r0 = lsqr(a); r1 = lsqr(b); }
+    static ZK_HD fe lsqr(const fe &a) { return reduce_once_c(sqr_cols_c(a)); }
+#endif
     static ZK_HD fe ldbl(const fe &a) { return ladd(a, a); }
     static ZK_HD fe lneg(const fe &a) { return lsub(zero(), a); }
     // -a as an OPERAND OF A PRODUCT: 2p - a in (0, 2p], eight subtractions and no fold.  2p itself is outside the loose domain but

@@ -2507,6 +2507,7 @@ ZK_PROBE_OP(PrLmul2X2, 8, 2, F::lmul2_x2(a[0], a[1], a[2], a[3], a[4], a[5], a[6
 ZK_PROBE_OP(PrToMont, 1, 1, o[0] = F::to_mont(a[0]))
 ZK_PROBE_OP(PrFromMont, 1, 1, o[0] = F::from_mont(a[0]))
 ZK_PROBE_OP(PrInv, 1, 1, o[0] = F::inv(a[0]))
+ZK_PROBE_OP(PrLsqrPair, 2, 2, F::lsqr_pair(a[0], a[1], o[0], o[1]))
 // Fq2 (F = Fq2): elements are two words
 ZK_PROBE_OP(Pr2Lmul, 4, 2, probe_st2(o, F::lmul(probe_ld2(a), probe_ld2(a + 2))))
 ZK_PROBE_OP(Pr2Lsqr, 2, 2, probe_st2(o, F::lsqr(probe_ld2(a))))
@@ -2580,6 +2581,7 @@ template <class F> int probe_field(int idx, const fe *d_in, uint32_t n, fe *d_ou
     case 21: return probe_launch<PrToMont<F>>(d_in, n, d_out);
     case 22: return probe_launch<PrFromMont<F>>(d_in, n, d_out);
     case 23: return probe_launch<PrInv<F>>(d_in, n, d_out);
+    case 26: return probe_launch<PrLsqrPair<F>>(d_in, n, d_out);
     }
     return fail(ZK_ERR_ARG, "unknown probe op");
 }
@@ -2601,14 +2603,14 @@ int probe_fq2(int idx, const fe *d_in, uint32_t n, fe *d_out) {
 }
 // words per case in and out; false for an op that does not exist
 bool probe_shape(int op, uint32_t &in_words, uint32_t &out_words) {
-    static const uint8_t field_in[26] = {2, 2, 1, 2, 1, 1, 2, 1, 2, 2, 1, 1, 1, 1, 2, 4, 4, 8, 8, 4, 8, 1, 1, 1, 0, 12};   // (24 is not assigned)
+    static const uint8_t field_in[27] = {2, 2, 1, 2, 1, 1, 2, 1, 2, 2, 1, 1, 1, 1, 2, 4, 4, 8, 8, 4, 8, 1, 1, 1, 0, 12, 2};   // (24 is not assigned)
     static const uint8_t fq2_in[11] = {4, 2, 8, 4, 4, 2, 2, 2, 2, 2, 4};
     static const uint8_t curve_in[10] = {2, 4, 6, 6, 8, 4, 8, 6, 4, 4}, curve_out[10] = {4, 4, 4, 4, 4, 16, 16, 16, 4, 2};   // in field elements
     if (op < 0) return false;
     const int dom = op & ~0xff, idx = op & 0xff;
     if (dom == ZK_PROBE_FR || dom == ZK_PROBE_FQ) {
-        if (idx >= 26 || idx == 24) return false;
-        in_words = field_in[idx]; out_words = idx == 19 || idx == 20 ? 2 : 1;
+        if (idx >= 27 || idx == 24) return false;
+        in_words = field_in[idx]; out_words = idx == 19 || idx == 20 || idx == 26 ? 2 : 1;
     } else if (dom == ZK_PROBE_FQ2) {
         if (idx >= 11) return false;
         in_words = fq2_in[idx]; out_words = 2;

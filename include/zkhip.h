@@ -589,6 +589,7 @@ int zk_pairing_tower_op(int op, const uint64_t *a, const uint64_t *b, uint64_t *
  *     25 ldot6(a0 .. a5, b0 .. b5) = a0 b0 + .. + a5 b5 with one reduction: 12 operand words, a0 .. a5 then b0 .. b5 (the a loose, the b
  *        CANONICAL: the precondition of Field::ldot6), one result word.  (24 is not assigned and stays an unknown op: the probe's own
  *        argument test uses it as the first index past the table.)
+ *     26 lsqr_pair(a, b) -> (a^2, b^2): 2 words (the dual squaring of the G1 mixed addition)
  *   ZK_PROBE_FQ2 (operands and result are Fq2 elements):
  *      0 lmul(a, b)  1 lsqr(a)  2 lmul2(a, b, c, d)  3 ladd(a, b)  4 lsub(a, b)  5 lis_zero(a) (0 or 1 in the low limb of c0)
  *      6 ldbl(a)  7 lneg(a)  8 canon(a)  9 inv(canon(a)) (strict result; 0 -> 0: the form pairing.hpp's f2inv uses)
