@@ -2,7 +2,7 @@
 //
 // Host-only work, done once per context with the strict field operations: hash-to-point (sha256, the from_y rule, a Tonelli-Shanks root, times the
 // cofactor), the Pedersen tables (1 .. 4) 16^j B_s as affine points, the 16 multiples of the EdDSA base point, the MiMC constants of the seed
-// "EdDSA_Verify.RAM".  Per item the host only compares limbs with r; every field operation of a batch runs in ONE kernel launch.
+// "EdDSA_Verify.RAM", and -- on a handle's first zk_eddsa_sign_batch -- the signer's fixed-base table (0 .. 15) 16^j B (eddsa_sign.hpp).  Per item the host only compares limbs with r; every field operation of a batch runs in ONE kernel launch.
 #include <algorithm>
 #include <memory>
 #include <string>
@@ -11,6 +11,7 @@
 #include <string.h>
 #include "bn254.hpp"
 #include "jubjub.hpp"
+#include "eddsa_sign.hpp"
 #include "../../include/ethsnarks_hip/gadgets.hpp"              // the streaming sha256 and keccak256 (host code), as merkle.cpp uses them
 #include "../../include/zkhip.h"
 
@@ -226,6 +227,8 @@ struct zk_eddsa {
     const fe *fbtab = nullptr;                                  // (0 .. 3) 4^i B, i = 0 .. 126: the tables of the circuit's fixed_base_mul
     const fe *mtab = nullptr;                                   // the Montgomery form of every ram table point: the lookups of the in-circuit Pedersen hash
     EddsaView view;
+    jpoint base;                                                // B, for the signer's table
+    DevBuf sign_tab;                                            // (0 .. 15) 16^j B, j = 0 .. 63 as (x, y, d x y): built by the first zk_eddsa_sign_batch
     hipStream_t st = nullptr;
     ~zk_eddsa() { if (st) (void)hipStreamDestroy(st); }
 };
@@ -362,6 +365,7 @@ extern "C" int zk_eddsa_create(int scheme, const uint64_t *B, uint32_t msg_len, 
     set_identity(mult[0]);
     from_affine(mult[1], Fr::to_mont(limbs_to_fe(B)), Fr::to_mont(limbs_to_fe(B + 4)));
     for (uint32_t i = 2; i < TABLE; i++) { mult[i] = mult[i - 1]; host_add(mult[i], mult[1]); }
+    v->base = mult[1];
     std::vector<fe> btab, ram, mt, rc(merkle::MIMC_ROUNDS);
     to_entries(mult, btab);
     if (scheme == SCHEME_MIMC) mimc_constants("EdDSA_Verify.RAM", rc.data());
@@ -537,5 +541,86 @@ extern "C" int zk_eddsa_fill_pure_witnesses(zk_eddsa *v, const uint64_t *A, cons
     ZK_HIP(hipGetLastError());
     ZK_HIP(hipMemcpyAsync(verdicts, dV, n, hipMemcpyDeviceToHost, v->st));
     ZK_HIP(hipStreamSynchronize(v->st));
+    return ZK_OK;
+} ZK_GUARD
+
+// ---- the signer (eddsa_sign.hpp)
+namespace {
+bool key_in_range(const uint64_t *k) {                          // 0 < k < L
+    static const uint64_t ORDER[4] = {0x677297dc392126f1ull, 0xab3eedb83920ee0aull, 0x370a08b6d0302b0bull, 0x060c89ce5c263405ull};
+    if (!(k[0] | k[1] | k[2] | k[3])) return false;
+    for (int i = 3; i >= 0; i--) if (k[i] != ORDER[i]) return k[i] < ORDER[i];
+    return false;
+}
+// entry (j 16 + m) = m 16^j B, with the strict field operations like the Pedersen tables
+int build_sign_table(zk_eddsa *v) {
+    if (v->sign_tab.p) return ZK_OK;
+    std::vector<jpoint> pts;
+    pts.reserve(SIGN_TABLE_ENTRIES);
+    jpoint cur = v->base, zero;
+    set_identity(zero);
+    for (uint32_t j = 0; j < N_WIN; j++) {
+        pts.push_back(zero);
+        pts.push_back(cur);
+        for (uint32_t m = 2; m < TABLE; m++) { jpoint nx = pts.back(); host_add(nx, cur); pts.push_back(nx); }
+        for (uint32_t b = 0; b < WIN; b++) jj_dbl(cur, true);
+    }
+    std::vector<fe> entries;
+    to_entries(pts, entries);
+    return v->sign_tab.upload(entries.data(), sizeof(fe) * entries.size());
+}
+// the device copies of the keys and of the nonces do not outlive the call, whichever way the call ends
+struct WipeOnExit {
+    void *p; size_t bytes; hipStream_t st;
+    ~WipeOnExit() { if (p && bytes) { (void)hipMemsetAsync(p, 0, bytes, st); (void)hipStreamSynchronize(st); } }
+};
+}  // namespace
+
+extern "C" int zk_eddsa_sign_batch(zk_eddsa *v, const uint64_t *keys, const void *msgs, uint32_t n, uint64_t *A, uint64_t *R, uint64_t *s) try {
+    if (!v || !keys || !msgs || !A || !R || !s) return jfail(ZK_ERR_ARG, "null argument");
+    if (n == 0) return ZK_OK;
+    for (uint32_t i = 0; i < n; i++) if (!key_in_range(keys + 4 * (size_t)i)) return jfail(ZK_ERR_ARG, "a key is not in 1 .. L - 1");
+    const bool mimc = v->scheme == SCHEME_MIMC;
+    if (mimc && !all_below_modulus((const uint64_t *)msgs, (uint64_t)n * v->msg_len)) return jfail(ZK_ERR_ARG, "a message element is not below the Fr modulus");
+    ZK_TRY(jj_use_device(v->device));
+    ZK_TRY(build_sign_table(v));
+    const size_t pb = 2 * sizeof(fe) * (size_t)n, sb = sizeof(fe) * (size_t)n;
+    const size_t mb = (size_t)n * v->msg_len * (mimc ? sizeof(fe) : 1), mb_al = align32(mb);
+    ZK_TRY(v->scratch.ensure(2 * sb + mb_al + 2 * pb + sb + (v->scheme == SCHEME_HASH ? pb : 0)));
+    char *d = (char *)v->scratch.p;
+    char *dK = d, *dN = dK + sb, *dM = dN + sb, *dA = dM + mb_al, *dR = dA + pb, *dS = dR + pb, *dP = dS + sb;
+    WipeOnExit wipe{dK, 2 * sb, v->st};                         // keys | nonces: the kernel reads both from here at every use (eddsa_sign.hpp)
+    ZK_HIP(hipMemcpyAsync(dK, keys, sb, hipMemcpyHostToDevice, v->st));
+    ZK_HIP(hipMemcpyAsync(dM, msgs, mb, hipMemcpyHostToDevice, v->st));
+    ZK_LAUNCH(k_eddsa_sign, zk_div_up(n, BLOCK), BLOCK, v->st, v->view, (const fe *)v->sign_tab.p, (const fe *)dK, (fe *)dN, (const void *)dM, n, (fe *)dA, (fe *)dR, (fe *)dS,
+              v->scheme == SCHEME_HASH ? (fe *)dP : (fe *)nullptr);
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipStreamSynchronize(v->st));
+    ZK_HIP(hipMemcpyAsync(A, dA, pb, hipMemcpyDeviceToHost, v->st));
+    ZK_HIP(hipMemcpyAsync(R, dR, pb, hipMemcpyDeviceToHost, v->st));
+    ZK_HIP(hipMemcpyAsync(s, dS, sb, hipMemcpyDeviceToHost, v->st));
+    ZK_HIP(hipStreamSynchronize(v->st));
+    return ZK_OK;
+} ZK_GUARD
+
+extern "C" int zk_eddsa_sign_probe(int op, const void *a, const void *b, const void *c, uint32_t n, uint32_t len, int device, void *out) try {
+    if (op != SIGN_PROBE_SHA512 && op != SIGN_PROBE_MOD_L && op != SIGN_PROBE_MULADD_MOD_E) return jfail(ZK_ERR_ARG, "unknown signer probe op");
+    if (n == 0) return ZK_OK;
+    const size_t ab = op == SIGN_PROBE_SHA512 ? (size_t)n * len : op == SIGN_PROBE_MOD_L ? sizeof(wide) * (size_t)n : sizeof(fe) * (size_t)n;
+    const size_t bb = op == SIGN_PROBE_MULADD_MOD_E ? sizeof(fe) * (size_t)n : 0, ob = (op == SIGN_PROBE_SHA512 ? sizeof(wide) : sizeof(fe)) * (size_t)n;
+    if (!out || (ab && !a) || (bb && (!b || !c))) return jfail(ZK_ERR_ARG, "null argument");
+    if (n > (1u << 20) || ab > ((size_t)1 << 30)) return jfail(ZK_ERR_ARG, "the probe takes at most 2^20 items and 2^30 bytes per call");
+    ZK_TRY(jj_use_device(device));
+    const size_t ab_al = align32(ab);
+    DevBuf buf;
+    ZK_TRY(buf.ensure(ab_al + 2 * bb + ob + 32));
+    char *d = (char *)buf.p;
+    char *dA = d, *dB = dA + ab_al, *dC = dB + bb, *dO = dC + bb;
+    if (ab) ZK_HIP(hipMemcpy(dA, a, ab, hipMemcpyHostToDevice));
+    if (bb) { ZK_HIP(hipMemcpy(dB, b, bb, hipMemcpyHostToDevice)); ZK_HIP(hipMemcpy(dC, c, bb, hipMemcpyHostToDevice)); }
+    ZK_LAUNCH(k_eddsa_sign_probe, zk_div_up(n, BLOCK), BLOCK, nullptr, op, (const void *)dA, (const fe *)dB, (const fe *)dC, n, len, (uint32_t *)dO);
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipDeviceSynchronize());
+    ZK_HIP(hipMemcpy(out, dO, ob, hipMemcpyDeviceToHost));
     return ZK_OK;
 } ZK_GUARD

@@ -1,15 +1,19 @@
-"""Baby JubJub on the device: the curve, the windowed Pedersen hash and batch EdDSA verification (zk_jj_*, zk_pedersen_*, zk_eddsa_* of
-include/zkhip.h; kernels in csrc/jubjub.hpp).
+"""Baby JubJub on the device: the curve, the windowed Pedersen hash, batch EdDSA verification and batch EdDSA signing (zk_jj_*, zk_pedersen_*,
+zk_eddsa_* of include/zkhip.h; kernels in csrc/jubjub.hpp and csrc/eddsa_sign.hpp).
 
 The native surface of the reference's ethsnarks/jubjub.py, pedersen.py and eddsa.py, in bulk form: a point is a pair (x, y) of ints in [0, r),
-the identity is (0, 1).  All curve arithmetic of a call runs in one HIP kernel launch; there is no CPU path and no signer.  A point that is not on
+the identity is (0, 1).  All curve arithmetic of a call runs in one HIP kernel launch; there is no CPU path.  A point that is not on
 the curve raises ZkError (ZK_ERR_ARG) in scalar_mul / point_add / point_double / point_neg and as a base point, and gives the verdict False as
 the A or R of a signature -- the reference never checks and divides by zero there; everything on the curve behaves as the reference does.
 
 EdDSAVerifier("mimc").circuit() is the R1CS that proves such a signature (jubjub_gadgets.eddsa_mimc_circuit) and fill_witnesses writes the
 complete witness rows of a batch into the device buffer that ProverContext.submit_batch(device_ptr=...) proves from.
 EdDSAVerifier("pure").pedersen_circuit() and fill_pedersen_witnesses are the same pair for the reference's PureEdDSA gadget, whose hash is the
-windowed Pedersen hash in the circuit (jubjub_gadgets.eddsa_pure_circuit, k_eddsa_fill_pure).  There is no signer.
+windowed Pedersen hash in the circuit (jubjub_gadgets.eddsa_pure_circuit, k_eddsa_fill_pure).
+
+EdDSASigner is the reference's _SignatureScheme.sign in bulk: sign(keys, msgs) gives (A, sigs) in the shape verify() and the two fills take, so
+sign -> verify -> fill witnesses -> prove runs on the device from end to end.  The kernel is not constant-time (include/zkhip.h): it is for bulk
+generation of signatures, not for keys that must withstand a co-tenant of the device.
 """
 import ctypes as C
 
@@ -32,6 +36,7 @@ _OPS = {"add": 0, "double": 1, "negate": 2}                     # ZK_JJ_OP_*
 _SYMBOLS = ("zk_jj_hash_to_point", "zk_jj_pedersen_basepoint", "zk_jj_point_op", "zk_jj_scalar_mul", "zk_pedersen_create", "zk_pedersen_free",
             "zk_pedersen_hash", "zk_pedersen_table", "zk_eddsa_create", "zk_eddsa_free", "zk_eddsa_verify_batch", "zk_eddsa_fill_witnesses",
             "zk_eddsa_fill_pure_witnesses")
+_SIGN_SYMBOLS = ("zk_eddsa_sign_batch", "zk_eddsa_sign_probe")   # checked by the signer alone: a library without them still serves the rest
 
 
 class EddsaLayout(C.Structure):
@@ -364,3 +369,72 @@ class EdDSAVerifier:
         out = np.full(n, 255, dtype=np.uint8)
         P._check(self._lib.zk_eddsa_verify_batch(self._h, _ptr(a), _ptr(r), _ptr(s), _ptr(m), n, _ptr(out)))
         return [bool(v) for v in out]
+
+
+def _sign_lib():
+    lib = _lib()
+    missing = [n for n in _SIGN_SYMBOLS if not hasattr(lib, n)]
+    if missing:
+        raise ImportError("%s has no EdDSA signer (%s): it was built before csrc/eddsa_sign.hpp" % (P._lib_path_loaded or P.LIB_PATH, missing[0]))
+    lib.zk_eddsa_sign_batch.argtypes = [C.c_void_p] * 3 + [C.c_uint32] + [C.c_void_p] * 3
+    lib.zk_eddsa_sign_probe.argtypes = [C.c_int] + [C.c_void_p] * 3 + [C.c_uint32, C.c_uint32, C.c_int, C.c_void_p]
+    return lib
+
+
+class EdDSASigner:
+    """Batch signing of one scheme -- _SignatureScheme.sign of the reference for "mimc" (a message is msg_len field elements), "pure" or "hash"
+    (msg_len bytes).  B=None: the generator.  Owns a zk_eddsa handle like EdDSAVerifier; the first sign() builds the fixed-base table of B on it.
+    Deterministic: r = SHA-512(key || M) mod L.  Not constant-time (include/zkhip.h)"""
+
+    def __init__(self, scheme, B=None, msg_len=1, device=0):
+        self._h = C.c_void_p()                                  # (first: close() runs from __del__ even when the line below raises)
+        self._lib = _sign_lib()
+        self.scheme = scheme
+        self.msg_len = int(msg_len)
+        self.B = (int(B[0]), int(B[1])) if B is not None else None
+        b = _point_limbs([B]) if B is not None else None
+        P._check(self._lib.zk_eddsa_create(SCHEMES[scheme], _ptr(b) if b is not None else None, self.msg_len, int(device), C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            self._lib.zk_eddsa_free(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def sign(self, keys, msgs):
+        """keys: ints in (0, L); msgs: bytes objects (lists of ints for "mimc"), one per key.  Returns (A, sigs): the public keys key B as points
+        and [(R, s), ..], what EdDSAVerifier.verify(A, sigs, msgs), fill_witnesses and fill_pedersen_witnesses take.  s is the integer mod 8 L.
+        ZkError (ZK_ERR_ARG) for a key that is 0 or >= L or a "mimc" message element >= r; nothing is signed then"""
+        keys = [int(k) for k in keys]
+        msgs = list(msgs)
+        n = len(keys)
+        if len(msgs) != n:
+            raise ValueError("keys and msgs differ in length")
+        if n == 0:
+            return [], []
+        if any(not 0 <= k < 1 << 256 for k in keys):
+            raise ValueError("a key is not in [0, 2^256)")
+        if self.scheme == "mimc":
+            if any(len(m) != self.msg_len for m in msgs):
+                raise ValueError("a message does not have msg_len elements")
+            m = F.ints_to_limbs([int(x) for msg in msgs for x in msg])
+        else:
+            if any(len(bytes(m)) != self.msg_len for m in msgs):
+                raise ValueError("a message does not have msg_len bytes")
+            m = np.frombuffer(b"".join(bytes(x) for x in msgs), dtype=np.uint8).copy()
+        k = F.ints_to_limbs(keys)
+        a = np.zeros((n, 8), dtype=np.uint64)
+        r = np.zeros((n, 8), dtype=np.uint64)
+        s = np.zeros((n, 4), dtype=np.uint64)
+        try:
+            P._check(self._lib.zk_eddsa_sign_batch(self._h, _ptr(k), _ptr(m), n, _ptr(a), _ptr(r), _ptr(s)))
+        finally:
+            k.fill(0)                                           # the staging copy of the keys
+        return _points(a), list(zip(_points(r), F.limbs_to_ints(s)))

@@ -65,6 +65,8 @@ extern "C" {
  * 7: zk_wplan_probe_program.
  * 8: zk_eddsa_fill_witnesses and zk_eddsa_layout.
  * 9: zk_eddsa_fill_pure_witnesses and zk_eddsa_pure_layout.
+ *    (zk_eddsa_sign_batch and zk_eddsa_sign_probe came later WITHOUT a bump: no struct changed layout and no function changed signature.  A
+ *    client that needs the signer detects it by its symbol.)
  * A client checks zk_abi_version() == ZK_ABI_VERSION once after loading the library, or passes the size of the zk_config
  * it was compiled with to zk_ctx_create_sized (members it does not know read as 0 = their defaults). */
 #define ZK_ABI_VERSION 9
@@ -546,6 +548,30 @@ typedef struct {
 } zk_eddsa_pure_layout;
 int zk_eddsa_fill_pure_witnesses(zk_eddsa *v, const uint64_t *A /* n x 8 */, const uint64_t *R /* n x 8 */, const uint64_t *s /* n x 4 */, const uint8_t *msgs /* n x msg_len bytes */,
                                  uint32_t n, void *d_w, uint64_t row_elems, const zk_eddsa_pure_layout *layout, uint8_t *verdicts /* n */);
+/* The signer (csrc/eddsa_sign.hpp): _SignatureScheme.sign of ethsnarks/eddsa.py for n keys and messages in ONE kernel launch, one lane per
+ * signature.  Scheme, B and msg_len are the handle's; msgs as zk_eddsa_verify_batch takes them.  Per item: r = int_le(SHA-512(key as 32 little-endian
+ * bytes || the bytes of M)) mod L, R = r B, A = key B, t = H(R, A, M) as the verifier computes it, s = (r + key t) mod 8 L.  The bytes of M: the message
+ * elements as 32 little-endian bytes each (ZK_EDDSA_MIMC), the message bytes (ZK_EDDSA_PURE), the point pedersen_hash_bytes("EdDSA_Verify.M", msg) as x
+ * then y, 32 little-endian bytes each (ZK_EDDSA_HASH).  The handle's first call builds a fixed-base table of B (98 304 bytes of device memory, freed
+ * with the handle).  ZK_ERR_ARG for the WHOLE call, and nothing written: a null argument, a key that is 0 or >= L (the reference raises "Strict parsing
+ * of k failed"), a ZK_EDDSA_MIMC message element >= r.  n = 0 succeeds and writes nothing.
+ * WHERE THE SECRETS GO.  The keys are copied to a device buffer and each lane writes its nonce to a buffer beside it; both are zeroed before the call
+ * returns, on every path.  The kernel reads every digit of key and nonce from those buffers at the point of use and keeps neither scalar in a private
+ * array nor in a register across a call, so that no copy of them is left in the lanes' scratch memory, which nobody clears (checked in the gfx950
+ * assembly; what a call may still save there is the table address chosen by ONE digit).  The library itself makes no host copy of the keys, but it
+ * uploads them from the caller's pageable memory, which the HIP runtime stages through a pinned buffer of its own that is not wiped; a caller who
+ * minds passes page-locked memory (zk_host_alloc) and zeroes it.  The first call on a handle builds the table: like every call on a zk_eddsa it must
+ * not run beside another call on the same handle (the single-thread rule above).
+ *   1. NOT CONSTANT TIME.  The table entries a lane reads are chosen by the digits of the key and of the nonce, and the reductions end in
+ *      data-dependent subtractions.  The signer is for bulk generation of signatures, not for keys that must withstand a co-tenant of the device.
+ *   2. s IS THE INTEGER mod 8 L, and 8 L lies slightly above the field modulus r.  A value in [r, 8 L) has a probability below 2^-160; the reference's
+ *      Signature would reduce such a value mod r and break the signature; zk_eddsa_verify_batch answers ZK_ERR_ARG for it.
+ * zk_eddsa_sign_probe is for tests only: the SAME device functions the signer uses, one lane per item.  op 0: SHA-512 of n messages of len bytes
+ * each (a: n x len bytes) -> n x 64 bytes; op 1: n 512-bit little-endian integers (a: n x 8 limbs) mod L -> n x 4 limbs; op 2: (a + b c) mod 8 L
+ * for any 256-bit a, b, c (n x 4 limbs each) -> n x 4 limbs.  ZK_ERR_ARG: an unknown op, a null argument, n above 2^20 or more than 2^30 input bytes. */
+int zk_eddsa_sign_batch(zk_eddsa *v, const uint64_t *keys /* n x 4 */, const void *msgs /* as zk_eddsa_verify_batch */, uint32_t n,
+                        uint64_t *A /* n x 8 */, uint64_t *R /* n x 8 */, uint64_t *s /* n x 4 */);
+int zk_eddsa_sign_probe(int op, const void *a, const void *b, const void *c, uint32_t n, uint32_t len, int device, void *out);
 
 /* ---- measurement aids (bench.py): kernel launches issued by this library so far; between zk_profile_begin() and
  * zk_profile_end() every launch is bracketed by a HIP event pair on its own stream -- the sum of the kernel durations
