@@ -2,7 +2,8 @@
 //
 // Host-only work, done once per context with the strict field operations: hash-to-point (sha256, the from_y rule, a Tonelli-Shanks root, times the
 // cofactor), the Pedersen tables (1 .. 4) 16^j B_s as affine points, the 16 multiples of the EdDSA base point, the MiMC constants of the seed
-// "EdDSA_Verify.RAM", and -- on a handle's first zk_eddsa_sign_batch -- the signer's fixed-base table (0 .. 15) 16^j B (eddsa_sign.hpp).  Per item the host only compares limbs with r; every field operation of a batch runs in ONE kernel launch.
+// "EdDSA_Verify.RAM", and -- on a handle's first zk_eddsa_sign_batch -- the signer's fixed-base table (0 .. 15) 16^j B (eddsa_sign.hpp), on a
+// ZK_EDDSA_HASH handle's first zk_eddsa_fill_hash_witnesses the tables of its circuit (build_hash_fill_tables).  Per item the host only compares limbs with r; every field operation of a batch runs in ONE kernel launch.
 #include <algorithm>
 #include <memory>
 #include <string>
@@ -21,6 +22,7 @@ using namespace zk::jubjub;
 static_assert(ZK_JJ_OP_ADD == OP_ADD && ZK_JJ_OP_DOUBLE == OP_DOUBLE && ZK_JJ_OP_NEGATE == OP_NEGATE, "zkhip.h and jubjub.hpp number the point operations alike");
 static_assert(sizeof(zk_eddsa_layout) == sizeof(FillLayout) && sizeof(FillLayout) == 19 * sizeof(uint32_t), "zkhip.h and jubjub.hpp lay the witness row out alike");
 static_assert(sizeof(zk_eddsa_pure_layout) == sizeof(PureLayout) && sizeof(PureLayout) == 26 * sizeof(uint32_t), "zkhip.h and jubjub.hpp lay the PureEdDSA witness row out alike");
+static_assert(sizeof(zk_eddsa_hash_layout) == sizeof(HashLayout) && sizeof(HashLayout) == 32 * sizeof(uint32_t), "zkhip.h and jubjub.hpp lay the EdDSA (hash scheme) witness row out alike");
 static_assert(ZK_EDDSA_MIMC == SCHEME_MIMC && ZK_EDDSA_PURE == SCHEME_PURE && ZK_EDDSA_HASH == SCHEME_HASH, "zkhip.h and jubjub.hpp number the schemes alike");
 
 namespace {
@@ -159,12 +161,14 @@ void pedersen_table(const std::string &name, uint32_t windows, std::vector<fe> &
     to_entries(pts, out);
 }
 // table entries (x, y, d x y) -> the Montgomery form (u, v) = ((1 + y) / (1 - y), u / x) of each point (EdwardsPoint::as_montgomery, scale 1), one
-// inversion for all of them.  No table point has x = 0 or y = 1: each is a multiple below L of a point of prime order
-void montgomery_entries(const std::vector<fe> &entries, std::vector<fe> &out) {
+// inversion for all of them.  No table point has x = 0 or y = 1: each is a multiple below L of a point of prime order; false (and garbage in out)
+// if one had
+bool montgomery_entries(const std::vector<fe> &entries, std::vector<fe> &out) {
     const size_t n = entries.size() / 3;
     std::vector<fe> pre(n);
     fe run = Fr::one();
     for (size_t i = 0; i < n; i++) { pre[i] = run; run = Fr::mul(run, Fr::mul(Fr::sub(Fr::one(), entries[3 * i + 1]), entries[3 * i])); }
+    const bool ok = !Fr::is_zero(run);
     fe inv = Fr::inv(run);
     out.resize(2 * n);
     for (size_t i = n; i-- > 0;) {
@@ -174,6 +178,21 @@ void montgomery_entries(const std::vector<fe> &entries, std::vector<fe> &out) {
         const fe u = Fr::mul(Fr::add(Fr::one(), y), Fr::mul(di, x));
         out[2 * i] = u; out[2 * i + 1] = Fr::mul(u, Fr::mul(di, omy));
     }
+    return ok;
+}
+// window i of the circuit's fixed-base multiplication: identity, P, 2 P, 3 P with P = 4^i B, as table entries
+void fixed_base_windows(const jpoint &B, std::vector<fe> &out) {
+    std::vector<jpoint> w;
+    w.reserve(4 * FB_WINDOWS);
+    jpoint cur = B, zero;
+    set_identity(zero);
+    for (uint32_t i = 0; i < FB_WINDOWS; i++) {
+        jpoint m2 = cur; jj_dbl(m2, true);
+        jpoint m3 = m2; host_add(m3, cur);
+        w.push_back(zero); w.push_back(cur); w.push_back(m2); w.push_back(m3);
+        cur = m2; jj_dbl(cur, true);
+    }
+    to_entries(w, out);
 }
 // C_0 = keccak256(keccak256(seed)), C_{i+1} = keccak256(C_i) (mimc_constants of ethsnarks/mimc/permutation.py), Montgomery
 void mimc_constants(const char *seed, fe *rc) {
@@ -229,6 +248,8 @@ struct zk_eddsa {
     EddsaView view;
     jpoint base;                                                // B, for the signer's table
     DevBuf sign_tab;                                            // (0 .. 15) 16^j B, j = 0 .. 63 as (x, y, d x y): built by the first zk_eddsa_sign_batch
+    DevBuf hash_fill_tab;                                       // (hash) fbtab | (u, v) of the ram table | (u, v) of the m table: built by the first zk_eddsa_fill_hash_witnesses
+    const fe *m_mtab = nullptr;                                 // (hash) the Montgomery form of every m table point
     hipStream_t st = nullptr;
     ~zk_eddsa() { if (st) (void)hipStreamDestroy(st); }
 };
@@ -375,19 +396,8 @@ extern "C" int zk_eddsa_create(int scheme, const uint64_t *B, uint32_t msg_len, 
         if (scheme == SCHEME_HASH) { v->m_windows = (8 * msg_len + 2) / 3; pedersen_table("EdDSA_Verify.M", v->m_windows, mt); }
     }
     std::vector<fe> all(btab), fb, mont;
-    if (scheme != SCHEME_HASH) {                                // window i of the circuit's fixed-base multiplication: identity, P, 2 P, 3 P, P = 4^i B
-        std::vector<jpoint> w;
-        w.reserve(4 * FB_WINDOWS);
-        jpoint cur = mult[1];
-        for (uint32_t i = 0; i < FB_WINDOWS; i++) {
-            jpoint m2 = cur; jj_dbl(m2, true);
-            jpoint m3 = m2; host_add(m3, cur);
-            w.push_back(mult[0]); w.push_back(cur); w.push_back(m2); w.push_back(m3);
-            cur = m2; jj_dbl(cur, true);
-        }
-        to_entries(w, fb);
-    }
-    if (scheme == SCHEME_PURE) montgomery_entries(ram, mont);
+    if (scheme != SCHEME_HASH) fixed_base_windows(mult[1], fb); // (a ZK_EDDSA_HASH handle builds its circuit's tables on its first fill: build_hash_fill_tables)
+    if (scheme == SCHEME_PURE) (void)montgomery_entries(ram, mont);
     const size_t o_rc = all.size(); all.insert(all.end(), rc.begin(), rc.end());
     const size_t o_ram = all.size(); all.insert(all.end(), ram.begin(), ram.end());
     const size_t o_m = all.size(); all.insert(all.end(), mt.begin(), mt.end());
@@ -538,6 +548,85 @@ extern "C" int zk_eddsa_fill_pure_witnesses(zk_eddsa *v, const uint64_t *A, cons
     ZK_HIP(hipMemcpyAsync(dM, msgs, mb, hipMemcpyHostToDevice, v->st));
     ZK_LAUNCH(k_eddsa_fill_pure, zk_div_up(n, BLOCK), BLOCK, v->st, v->view, v->fbtab, v->mtab, L, (const fe *)dA, (const fe *)dR, (const fe *)dS, (const uint8_t *)dM, n,
               (fe *)d_w, row_elems, (uint8_t *)dV);
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipMemcpyAsync(verdicts, dV, n, hipMemcpyDeviceToHost, v->st));
+    ZK_HIP(hipStreamSynchronize(v->st));
+    return ZK_OK;
+} ZK_GUARD
+
+namespace {
+// the EdDSA (hash scheme) row: as pure_layout_fits, the RAM hash over 3 x 254 bits and the message hash sized by the verifier's msg_len.  A segment
+// without elements (no padding bits, no Edwards adder of the message hash) is not there: its offset is not looked at
+bool hash_layout_fits(const HashLayout &L, uint32_t msg_len, uint64_t row_elems) {
+    if (L.msg_len != msg_len || (uint64_t)L.n_vars + 1 > row_elems) return false;
+    const uint64_t W = HASH_RAM_WINDOWS, S = (W + SEG_WINDOWS - 1) / SEG_WINDOWS, Wm = hash_msg_windows(msg_len), Sm = (Wm + SEG_WINDOWS - 1) / SEG_WINDOWS;
+    const uint64_t step0 = std::min(L.doubler_var0, std::min(L.cond_var0, L.adder_var0));
+    struct Seg { uint64_t at, len; };
+    const Seg step[3] = {{L.doubler_var0, DBL_VARS}, {L.cond_var0, 2}, {L.adder_var0, ADD_VARS}};
+    for (int i = 0; i < 3; i++) {
+        if (step[i].at + step[i].len > step0 + L.step_stride) return false;
+        for (int j = 0; j < i; j++) if (step[i].at < step[j].at + step[j].len && step[j].at < step[i].at + step[i].len) return false;
+    }
+    std::vector<Seg> segs = {{L.ax_var, 2}, {L.msg_bit0, 8 * (uint64_t)msg_len}, {L.rx_var, 2}, {L.s_bit0, FIELD_BITS},
+                             {L.m_pad_bit0, 3 * Wm - 8 * (uint64_t)msg_len}, {L.m_window_var0, 2 * Wm}, {L.m_mont_adder_var0, MADD_VARS * (Wm - Sm)},
+                             {L.m_converter_var0, 2 * Sm}, {L.m_edwards_adder_var0, ADD_VARS * (Sm - 1)}, {L.m_bit0, T_BITS_VARS}, {L.m_range_var0, T_RANGE_VARS},
+                             {L.validator_var0, VALIDATOR_VARS}, {L.window_var0, 2 * FB_WINDOWS}, {L.fixed_adder_var0, ADD_VARS * (FB_WINDOWS - 1)},
+                             {L.rx_bit0, T_BITS_VARS}, {L.rx_range_var0, T_RANGE_VARS}, {L.ax_bit0, T_BITS_VARS}, {L.ax_range_var0, T_RANGE_VARS},
+                             {L.hash_window_var0, 2 * W}, {L.mont_adder_var0, MADD_VARS * (W - S)}, {L.converter_var0, 2 * S}, {L.edwards_adder_var0, ADD_VARS * (S - 1)},
+                             {L.t_bit0, T_BITS_VARS}, {L.t_range_var0, T_RANGE_VARS}, {L.cond0_var, 2}, {step0, (uint64_t)N_STEPS * L.step_stride}, {L.last_adder_var0, ADD_VARS}};
+    std::sort(segs.begin(), segs.end(), [](const Seg &a, const Seg &b) { return a.at < b.at; });
+    uint64_t end = 1;                                           // variable 0 is ONE
+    for (const Seg &g : segs) {
+        if (g.len == 0) continue;
+        if (g.at < end) return false;
+        end = g.at + g.len;
+    }
+    return end <= (uint64_t)L.n_vars + 1;
+}
+// what the fill of a ZK_EDDSA_HASH handle reads beyond the verifier's tables: the circuit's fixed-base windows and the Montgomery form of the two
+// Pedersen tables (read back from the device: the handle keeps no host copy).  Built once, freed with the handle
+int build_hash_fill_tables(zk_eddsa *v) {
+    if (v->hash_fill_tab.p) return ZK_OK;
+    const size_t n_ram = (size_t)v->ram_windows * 4 * 3, n_m = (size_t)v->m_windows * 4 * 3;
+    std::vector<fe> ram(n_ram), mt(n_m), all, mont_ram, mont_m;
+    ZK_HIP(hipMemcpy(ram.data(), v->view.ram_tab, sizeof(fe) * n_ram, hipMemcpyDeviceToHost));
+    ZK_HIP(hipMemcpy(mt.data(), v->view.m_tab, sizeof(fe) * n_m, hipMemcpyDeviceToHost));
+    fixed_base_windows(v->base, all);
+    if (!montgomery_entries(ram, mont_ram) || !montgomery_entries(mt, mont_m))
+        return jfail(ZK_ERR_INTERNAL, "a Pedersen table point has x = 0 or y = 1: it has no Montgomery form");
+    const size_t o_ram = all.size(); all.insert(all.end(), mont_ram.begin(), mont_ram.end());
+    const size_t o_m = all.size(); all.insert(all.end(), mont_m.begin(), mont_m.end());
+    DevBuf b;
+    ZK_TRY(b.upload(all.data(), sizeof(fe) * all.size()));
+    std::swap(v->hash_fill_tab.p, b.p); std::swap(v->hash_fill_tab.cap, b.cap);
+    const fe *d = (const fe *)v->hash_fill_tab.p;
+    v->fbtab = d; v->mtab = d + o_ram; v->m_mtab = d + o_m;
+    return ZK_OK;
+}
+}  // namespace
+
+extern "C" int zk_eddsa_fill_hash_witnesses(zk_eddsa *v, const uint64_t *A, const uint64_t *R, const uint64_t *s, const uint8_t *msgs, uint32_t n, void *d_w,
+                                            uint64_t row_elems, const zk_eddsa_hash_layout *layout, uint8_t *verdicts) try {
+    if (!v || !layout) return jfail(ZK_ERR_ARG, "null argument");
+    if (v->scheme != SCHEME_HASH) return jfail(ZK_ERR_ARG, "only a ZK_EDDSA_HASH verifier has an EdDSA circuit with the message hash in it to fill witnesses of");
+    HashLayout L;
+    memcpy(&L, layout, sizeof(L));
+    if (!hash_layout_fits(L, v->msg_len, row_elems)) return jfail(ZK_ERR_ARG, "the layout does not fit the verifier's msg_len, overlaps itself or leaves the row");
+    if (n == 0) return ZK_OK;
+    if (!A || !R || !s || !msgs || !d_w || !verdicts) return jfail(ZK_ERR_ARG, "null argument");
+    if (!all_below_modulus(A, 2 * (uint64_t)n) || !all_below_modulus(R, 2 * (uint64_t)n)) return jfail(ZK_ERR_ARG, "a coordinate is not below the Fr modulus");
+    ZK_TRY(jj_use_device(v->device));
+    ZK_TRY(build_hash_fill_tables(v));
+    const size_t pb = 2 * sizeof(fe) * (size_t)n, sb = sizeof(fe) * (size_t)n, mb = (size_t)n * v->msg_len, mb_al = align32(mb);
+    ZK_TRY(v->scratch.ensure(2 * pb + sb + mb_al + align32(n)));
+    char *d = (char *)v->scratch.p;
+    char *dA = d, *dR = d + pb, *dS = d + 2 * pb, *dM = dS + sb, *dV = dM + mb_al;
+    ZK_HIP(hipMemcpyAsync(dA, A, pb, hipMemcpyHostToDevice, v->st));
+    ZK_HIP(hipMemcpyAsync(dR, R, pb, hipMemcpyHostToDevice, v->st));
+    ZK_HIP(hipMemcpyAsync(dS, s, sb, hipMemcpyHostToDevice, v->st));
+    ZK_HIP(hipMemcpyAsync(dM, msgs, mb, hipMemcpyHostToDevice, v->st));
+    ZK_LAUNCH(k_eddsa_fill_hash, zk_div_up(n, BLOCK), BLOCK, v->st, v->view, v->fbtab, v->mtab, v->m_mtab, L, (const fe *)dA, (const fe *)dR, (const fe *)dS,
+              (const uint8_t *)dM, n, (fe *)d_w, row_elems, (uint8_t *)dV);
     ZK_HIP(hipGetLastError());
     ZK_HIP(hipMemcpyAsync(verdicts, dV, n, hipMemcpyDeviceToHost, v->st));
     ZK_HIP(hipStreamSynchronize(v->st));

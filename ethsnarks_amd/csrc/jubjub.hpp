@@ -26,7 +26,8 @@
 //   k_jj_pedersen     n windowed Pedersen hashes over a table of affine multiples in device memory, the window count per lane
 //   k_eddsa_verify    n verdicts S B == R + t A, t = H(R, A, M) computed here for the three schemes of eddsa.py
 //   k_eddsa_fill      n complete witness rows of the MiMC-EdDSA circuit, one field inversion per row
-//   k_eddsa_fill_pure n complete witness rows of the PureEdDSA circuit (in-circuit Pedersen hash), two field inversions per row (at the end of this file)
+//   k_eddsa_fill_pure n complete witness rows of the PureEdDSA circuit (in-circuit Pedersen hash), two field inversions per row
+//   k_eddsa_fill_hash n complete witness rows of the EdDSA circuit (the message hashed in the circuit first), three field inversions per row (at the end of this file)
 #pragma once
 #include "bn254.hpp"
 #include "mimc.hpp"
@@ -729,6 +730,300 @@ k_eddsa_fill_pure(EddsaView v, const fe *__restrict__ fbtab, const fe *__restric
     fill_strict_bits(row + L.t_bit0, row + L.t_range_var0, t.l);
 
     // ---- the second set: variable base and R + t A
+    run = Fr::one();
+    {
+        jpoint d;
+        from_affine(d, ax, ay);
+        const uint32_t b0 = int_bit(t.l, 0);
+        row[L.cond0_var] = b0 ? ax : Fr::zero(); row[L.cond0_var + 1] = b0 ? ay : Fr::one();
+        from_affine(p, row[L.cond0_var], row[L.cond0_var + 1]);
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 1; i <= N_STEPS; i++) {
+            const size_t off = (size_t)(i - 1) * L.step_stride;
+            jj_dbl(d, true);
+            park_point(row + L.doubler_var0 + off, DBL_VARS, d, run);
+            const bool b = int_bit(t.l, i);
+            fe q[4];
+            q[0] = b ? d.c[0] : Fr::zero(); q[1] = b ? d.c[1] : Fr::one(); q[2] = b ? jj_mul(coef_d(), d.c[2]) : Fr::zero(); q[3] = b ? d.c[3] : Fr::one();
+            jj_add(p, q, false);
+            park_point(row + L.adder_var0 + off, ADD_VARS, p, run);
+        }
+        fe q[3];
+        q[0] = rx; q[1] = ry; q[2] = jj_mul(coef_d(), jj_mul(rx, ry));
+        jj_add(p, q, true);
+        park_point(row + L.last_adder_var0, ADD_VARS, p, run);
+    }
+    inv = jj_inv(run);
+    unpark_point(row + L.last_adder_var0, ADD_VARS, inv);
+#pragma clang loop unroll(disable)
+    for (uint32_t i = N_STEPS; i >= 1; i--) {
+        const size_t off = (size_t)(i - 1) * L.step_stride;
+        unpark_point(row + L.adder_var0 + off, ADD_VARS, inv);
+        unpark_point(row + L.doubler_var0 + off, DBL_VARS, inv);
+    }
+
+    // ---- the products of affine inputs
+    fill_doubler(val, rx, ry);
+    fill_doubler(val + DBL_VARS, val[4], val[5]);
+    fill_doubler(val + 2 * DBL_VARS, val[DBL_VARS + 4], val[DBL_VARS + 5]);
+    val[3 * DBL_VARS + 2] = Fr::canon(jj_mul(rx, rx)); val[3 * DBL_VARS + 3] = Fr::canon(jj_mul(ry, ry));
+    {
+        const fe *prev = row + L.window_var0;
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 0; i + 1 < FB_WINDOWS; i++) {
+            fe *blk = row + L.fixed_adder_var0 + ADD_VARS * (size_t)i;
+            const fe *w = row + L.window_var0 + 2 * (size_t)(i + 1);
+            fill_adder(blk, prev[0], prev[1], w[0], w[1]);
+            prev = blk + ADD_VARS - 2;
+        }
+    }
+    {
+        const fe *dprev = row + L.ax_var, *sprev = row + L.cond0_var;
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 1; i <= N_STEPS; i++) {
+            const size_t off = (size_t)(i - 1) * L.step_stride;
+            fe *dbl = row + L.doubler_var0 + off, *cond = row + L.cond_var0 + off, *add = row + L.adder_var0 + off;
+            fill_doubler(dbl, dprev[0], dprev[1]);
+            const bool b = int_bit(t.l, i);
+            cond[0] = b ? dbl[4] : Fr::zero(); cond[1] = b ? dbl[5] : Fr::one();
+            fill_adder(add, sprev[0], sprev[1], cond[0], cond[1]);
+            dprev = dbl + DBL_VARS - 2; sprev = add + ADD_VARS - 2;
+        }
+        fill_adder(row + L.last_adder_var0, rx, ry, sprev[0], sprev[1]);
+    }
+    const fe *lhs = row + L.fixed_adder_var0 + ADD_VARS * (size_t)(FB_WINDOWS - 2) + ADD_VARS - 2, *rhs = row + L.last_adder_var0 + ADD_VARS - 2;
+    verdicts[g] = Fr::eq(lhs[0], rhs[0]) && Fr::eq(lhs[1], rhs[1]) ? 1 : 0;
+}
+
+// ---- the complete witness of the EdDSA circuit of the "hash" scheme (jubjub_gadgets.py, EddsaHashCircuit): the row of k_eddsa_fill_pure with a
+// SECOND in-circuit Pedersen hash in front, M = the hash "EdDSA_Verify.M" of the message bits, whose 254 strict bits are the third part of the
+// input of the hash "EdDSA_Verify.RAM".  HashLayout is zk_eddsa_hash_layout of zkhip.h; the host has checked it as it checks PureLayout.
+//
+// THREE inversions per witness, whatever msg_len.  The walk of one hash is that of k_eddsa_fill_pure, here as two device functions over a HashWalk
+// (the table, its Montgomery form, the four segments of the row, the window count, the first bit of the stream): hash_walk_forward parks every
+// denominator on the caller's running product, hash_walk_back takes the quotients on the way back.  The message hash joins the product of the
+// validator and of the fixed-base chain, which need nothing from it: the first inversion closes all three and yields M.x.  The RAM hash needs
+// the bits of M.x and yields t (the second inversion); the variable-base chain needs the bits of t (the third).  The message hash may have a
+// single segment (msg_len <= 23: no Edwards adder, M is the converter's point) and, unlike the RAM hash of this circuit, a lone last window
+// (W_m % 62 == 1).  No step has a special case: DESIGN 5m restates the argument of 5k for the table of "EdDSA_Verify.M".
+struct HashLayout {
+    uint32_t msg_len, n_vars, ax_var, msg_bit0, rx_var, s_bit0, validator_var0, window_var0, fixed_adder_var0, rx_bit0, rx_range_var0,
+             ax_bit0, ax_range_var0, hash_window_var0, mont_adder_var0, converter_var0, edwards_adder_var0, t_bit0, t_range_var0, cond0_var,
+             doubler_var0, cond_var0, adder_var0, step_stride, last_adder_var0, m_pad_bit0, m_window_var0, m_mont_adder_var0, m_converter_var0,
+             m_edwards_adder_var0, m_bit0, m_range_var0;
+};
+constexpr uint32_t HASH_RAM_WINDOWS = FIELD_BITS;                // 3 x 254 bits: 254 windows, segments of 62, 62, 62, 62 and 6
+ZK_HD uint32_t hash_msg_windows(uint32_t msg_len) { return (8 * msg_len + 2) / 3; }
+
+// one in-circuit hash: tab / mtab = its table and the (u, v) of every entry; hw, madd, conv, ed = its windows, Montgomery adders, converters and
+// Edwards adders in the row; W windows over the bits of the stream from bit0 on
+struct HashWalk {
+    const fe *tab, *mtab;
+    fe *hw, *madd, *conv, *ed;
+    uint32_t W, bit0;
+    ZK_HD uint32_t lone() const { return W % SEG_WINDOWS == 1 ? 1u : 0u; }
+    ZK_HD uint32_t n_seg() const { return (W - lone() + SEG_WINDOWS - 1) / SEG_WINDOWS; }
+    ZK_HD uint32_t seg_windows(uint32_t sg) const { const uint32_t left = W - lone() - sg * SEG_WINDOWS; return left < SEG_WINDOWS ? left : SEG_WINDOWS; }   // >= 2
+    ZK_HD uint32_t window(const BitStream &bs, uint32_t j) const { const uint32_t i = bit0 + 3 * j; return bs.bit(i) | (bs.bit(i + 1) << 1) | (bs.bit(i + 2) << 2); }
+};
+
+// the forward walk of k_eddsa_fill_pure's hash: per window the prefix product and the denominator E wait in the window's two slots, (X, Y, Z) in
+// the adder's three; the Edwards sums of the segments are parked like every other point
+ZK_JFN void hash_walk_forward(const HashWalk &h, const BitStream &bs, fe &run) {
+    const uint32_t W = h.W, lone = h.lone(), n_seg = h.n_seg();
+    jpoint hacc, p;
+    if (lone) {                                                 // the last base point's single window: its converter is the table point itself
+        const uint32_t j = W - 1, w = h.window(bs, j);
+        const fe *e = h.tab + ((size_t)j * 4 + (w & 3)) * 3;
+        const fe x = Fr::canon(neg_if(e[0], w > 3));
+        h.conv[0] = x; h.conv[1] = e[1];
+        from_affine(hacc, x, e[1]);
+    }
+#pragma clang loop unroll(disable)
+    for (uint32_t sg = 0; sg < n_seg; sg++) {
+        const uint32_t j0 = sg * SEG_WINDOWS, m = h.seg_windows(sg);
+        uint32_t w = h.window(bs, j0);
+        {
+            const fe *e = h.tab + ((size_t)j0 * 4 + (w & 3)) * 3;
+            from_affine(p, neg_if(e[0], w > 3), e[1]);
+        }
+#pragma clang loop unroll(disable)
+        for (uint32_t k = 0; k < m; k++) {
+            const uint32_t j = j0 + k;
+            const bool last = k + 1 == m;
+            const uint32_t w2 = last ? 0u : h.window(bs, j + 1);
+            const fe u2 = h.mtab[((size_t)(last ? j : j + 1) * 4 + (w2 & 3)) * 2];
+            fe E;
+            if (k == 0) E = Fr::lsub(u2, h.mtab[((size_t)j * 4 + (w & 3)) * 2]);
+            else {
+                fe *blk = h.madd + MADD_VARS * (size_t)(sg * SEG_ADDERS + k - 1);
+                blk[0] = p.c[0]; blk[1] = p.c[1]; blk[2] = p.c[3];
+                const fe d1 = Fr::lsub(p.c[3], p.c[1]);
+                const fe d3 = last ? p.c[3] : Fr::lsub(Fr::lmul(u2, d1), Fr::ladd(p.c[3], p.c[1]));
+                E = Fr::lmul(Fr::lmul(d1, p.c[0]), d3);
+            }
+            h.hw[2 * (size_t)j] = run; h.hw[2 * (size_t)j + 1] = E;
+            run = Fr::lmul(run, E);
+            if (!last) { pedersen_step(p, h.tab, j + 1, w2); w = w2; }
+        }
+        if (!lone && sg == 0) hacc = p;
+        else {
+            fe q[4];
+            q[0] = p.c[0]; q[1] = p.c[1]; q[2] = jj_mul(coef_d(), p.c[2]); q[3] = p.c[3];
+            jj_add(hacc, q, false);
+            park_point(h.ed + ADD_VARS * (size_t)(sg - 1 + lone), ADD_VARS, hacc, run);
+        }
+    }
+}
+
+// the way back: inv = 1 / (the product up to and including the hash's last denominator) on entry, 1 / (the product before its first) on return.
+// Leaves every window, Montgomery adder and converter of the hash as the front end has it, and x3, y3 of every Edwards adder
+ZK_JFN void hash_walk_back(const HashWalk &h, const BitStream &bs, fe &inv) {
+    const uint32_t W = h.W, lone = h.lone(), n_seg = h.n_seg();
+#pragma clang loop unroll(disable)
+    for (int sg = (int)n_seg - 1; sg >= 0; sg--) {
+        const uint32_t j0 = sg * SEG_WINDOWS, m = h.seg_windows(sg);
+        if (lone || sg > 0) unpark_point(h.ed + ADD_VARS * (size_t)(sg - 1 + lone), ADD_VARS, inv);
+#pragma clang loop unroll(disable)
+        for (int k = (int)m - 1; k >= 0; k--) {
+            const uint32_t j = j0 + k;
+            const bool last = k + 1 == (int)m;
+            fe *win = h.hw + 2 * (size_t)j;
+            const fe einv = Fr::lmul(inv, win[0]);              // 1 / E of this step
+            inv = Fr::lmul(inv, win[1]);
+            const uint32_t w = h.window(bs, j), w2 = last ? 0u : h.window(bs, j + 1);
+            const fe vown = Fr::canon(neg_if(h.mtab[((size_t)j * 4 + (w & 3)) * 2 + 1], w > 3));
+            const fe *m2 = h.mtab + ((size_t)(last ? j : j + 1) * 4 + (w2 & 3)) * 2;
+            const fe u2 = m2[0], v2 = neg_if(m2[1], w2 > 3);
+            if (k == 0) h.madd[MADD_VARS * (size_t)(sg * SEG_ADDERS)] = Fr::canon(Fr::lmul(Fr::lsub(v2, vown), einv));
+            else {
+                fe *blk = h.madd + MADD_VARS * (size_t)(sg * SEG_ADDERS + k - 1);
+                const fe X = blk[0], Y = blk[1], Z = blk[2];
+                const fe d1 = Fr::lsub(Z, Y), zpy = Fr::ladd(Z, Y);
+                const fe d3 = last ? Z : Fr::lsub(Fr::lmul(u2, d1), zpy);
+                const fe i2 = Fr::lmul(einv, d3), i1 = Fr::lmul(i2, X);                  // 1 / ((Z - Y) X), 1 / (Z - Y)
+                const fe i3 = Fr::lmul(einv, Fr::lmul(d1, X));                            // 1 / D3
+                const fe vv = Fr::lmul(Fr::lmul(zpy, Z), i2);
+                blk[1] = Fr::canon(Fr::lmul(zpy, i1)); blk[2] = Fr::canon(vv);
+                if (last) {
+                    fe *c = h.conv + 2 * (size_t)(sg + lone);
+                    c[0] = Fr::canon(Fr::lmul(X, i3)); c[1] = Fr::canon(Fr::lmul(Y, i3));
+                } else blk[MADD_VARS] = Fr::canon(Fr::lmul(Fr::lsub(v2, vv), Fr::lmul(i3, d1)));   // the next adder's lambda
+            }
+            win[0] = bit_fe((w & 3) == 3); win[1] = vown;
+        }
+    }
+    if (lone) {
+        const uint32_t j = W - 1, w = h.window(bs, j);
+        h.hw[2 * (size_t)j] = bit_fe((w & 3) == 3);
+        h.hw[2 * (size_t)j + 1] = Fr::canon(neg_if(h.mtab[((size_t)j * 4 + (w & 3)) * 2 + 1], w > 3));
+    }
+}
+
+// the products of the Edwards adders over the converted segments; returns the x of the hash (canonical Montgomery): the last adder's, or the
+// only converter's when the hash has one segment
+ZK_JFN fe hash_walk_close(const HashWalk &h) {
+    const uint32_t n_conv = h.n_seg() + h.lone();
+    const fe *prev = h.conv;
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0; i + 1 < n_conv; i++) {
+        fe *blk = h.ed + ADD_VARS * (size_t)i;
+        fill_adder(blk, prev[0], prev[1], h.conv[2 * (size_t)(i + 1)], h.conv[2 * (size_t)(i + 1) + 1]);
+        prev = blk + ADD_VARS - 2;
+    }
+    return prev[0];
+}
+
+// mtab / m_mtab: the Montgomery forms of ram_tab / m_tab as k_eddsa_fill_pure takes its mtab.  msgs: msg_len bytes an item.  Malformed items,
+// verdicts and the row's form as k_eddsa_fill
+__global__ void __launch_bounds__(BLOCK)
+k_eddsa_fill_hash(EddsaView v, const fe *__restrict__ fbtab, const fe *__restrict__ mtab, const fe *__restrict__ m_mtab, HashLayout L, const fe *__restrict__ A,
+                  const fe *__restrict__ R, const fe *__restrict__ s, const uint8_t *__restrict__ msgs, uint32_t n, fe *d_w, uint64_t row_elems,
+                  uint8_t *__restrict__ verdicts) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    fe ax, ay, rx, ry;
+    load_point(A, g, ax, ay);
+    load_point(R, g, rx, ry);
+    const uint32_t *__restrict__ sw = s[g].l;
+    if (!on_curve(ax, ay) || !on_curve(rx, ry) || (sw[7] >> 30)) { verdicts[g] = 0; return; }
+    ax = Fr::canon(ax); ay = Fr::canon(ay); rx = Fr::canon(rx); ry = Fr::canon(ry);
+    fe *row = d_w + (size_t)g * row_elems;
+    BitStream bs;
+    bs.rx = R[2 * (size_t)g].l; bs.ax = A[2 * (size_t)g].l; bs.mx = nullptr; bs.msg = msgs + (size_t)g * L.msg_len; bs.msg_bits = 8 * L.msg_len;
+    HashWalk hm, hr;                                            // the message hash reads the stream from the message on (past its end: the zero padding)
+    hm.tab = v.m_tab; hm.mtab = m_mtab; hm.W = v.m_windows; hm.bit0 = 2 * FIELD_BITS;
+    hm.hw = row + L.m_window_var0; hm.madd = row + L.m_mont_adder_var0; hm.conv = row + L.m_converter_var0; hm.ed = row + L.m_edwards_adder_var0;
+    hr.tab = v.ram_tab; hr.mtab = mtab; hr.W = v.ram_windows; hr.bit0 = 0;
+    hr.hw = row + L.hash_window_var0; hr.madd = row + L.mont_adder_var0; hr.conv = row + L.converter_var0; hr.ed = row + L.edwards_adder_var0;
+
+    // ---- the inputs and the two decompositions that need nothing else
+    row[0] = Fr::one();
+    row[L.ax_var] = ax; row[L.ax_var + 1] = ay; row[L.rx_var] = rx; row[L.rx_var + 1] = ry;
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0; i < FIELD_BITS; i++) row[L.s_bit0 + i] = bit_fe(int_bit(sw, i));
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0; i < bs.msg_bits; i++) row[L.msg_bit0 + i] = bit_fe(bs.bit(2 * FIELD_BITS + i));
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0; i < 3 * hm.W - bs.msg_bits; i++) row[L.m_pad_bit0 + i] = Fr::zero();
+    fill_strict_bits(row + L.rx_bit0, row + L.rx_range_var0, bs.rx);
+    fill_strict_bits(row + L.ax_bit0, row + L.ax_range_var0, bs.ax);
+
+    // ---- the first set of chains, projective: validator, fixed base, the message hash
+    fe run = Fr::one();
+    jpoint p;
+    fe *val = row + L.validator_var0;
+    from_affine(p, rx, ry);
+#pragma clang loop unroll(disable)
+    for (uint32_t j = 0; j < 3; j++) { jj_dbl(p, false); park_point(val + DBL_VARS * j, DBL_VARS, p, run); }
+    {
+        const bool nz = !Fr::is_zero(Fr::canon(p.c[0]));
+        const fe x8 = nz ? p.c[0] : Fr::one();
+        val[3 * DBL_VARS] = run; val[3 * DBL_VARS + 1] = x8;
+        run = Fr::lmul(run, x8);
+    }
+    {
+        const fe *e = fbtab + 3 * (size_t)(int_bit(sw, 0) | (int_bit(sw, 1) << 1));
+        row[L.window_var0] = e[0]; row[L.window_var0 + 1] = e[1];
+        from_affine(p, e[0], e[1]);
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 1; i < FB_WINDOWS; i++) {
+            e = fbtab + 3 * ((size_t)4 * i + (int_bit(sw, 2 * i) | (int_bit(sw, 2 * i + 1) << 1)));
+            row[L.window_var0 + 2 * i] = e[0]; row[L.window_var0 + 2 * i + 1] = e[1];
+            jj_add(p, e, true);
+            park_point(row + L.fixed_adder_var0 + ADD_VARS * (size_t)(i - 1), ADD_VARS, p, run);
+        }
+    }
+    hash_walk_forward(hm, bs, run);
+
+    // ---- the first inversion and its way back; M = the message hash, the strict bits of its x
+    fe inv = jj_inv(run);
+    hash_walk_back(hm, bs, inv);
+#pragma clang loop unroll(disable)
+    for (uint32_t i = FB_WINDOWS - 1; i >= 1; i--) unpark_point(row + L.fixed_adder_var0 + ADD_VARS * (size_t)(i - 1), ADD_VARS, inv);
+    {
+        fe *blk8 = val + 2 * DBL_VARS;
+        const bool nz = !Fr::is_zero(Fr::canon(blk8[4]));
+        const fe xi = Fr::lmul(inv, val[3 * DBL_VARS]);
+        inv = Fr::lmul(inv, val[3 * DBL_VARS + 1]);
+        val[3 * DBL_VARS] = bit_fe(nz);
+        val[3 * DBL_VARS + 1] = nz ? Fr::canon(Fr::lmul(blk8[0], xi)) : Fr::zero();
+    }
+#pragma clang loop unroll(disable)
+    for (int j = 2; j >= 0; j--) unpark_point(val + DBL_VARS * j, DBL_VARS, inv);
+    const fe mx = jj_from_mont(hash_walk_close(hm));            // the canonical integer: the third part of the RAM hash's input
+    fill_strict_bits(row + L.m_bit0, row + L.m_range_var0, mx.l);
+
+    // ---- the RAM hash over bits(R.x) || bits(A.x) || bits(M.x): the second inversion; t = its x, the strict bits of t
+    bs.mx = mx.l;
+    run = Fr::one();
+    hash_walk_forward(hr, bs, run);
+    inv = jj_inv(run);
+    hash_walk_back(hr, bs, inv);
+    const fe t = jj_from_mont(hash_walk_close(hr));
+    fill_strict_bits(row + L.t_bit0, row + L.t_range_var0, t.l);
+
+    // ---- the third set: variable base and R + t A
     run = Fr::one();
     {
         jpoint d;

@@ -10,8 +10,10 @@ EdDSAVerifier("mimc").circuit() is the R1CS that proves such a signature (jubjub
 complete witness rows of a batch into the device buffer that ProverContext.submit_batch(device_ptr=...) proves from.
 EdDSAVerifier("pure").pedersen_circuit() and fill_pedersen_witnesses are the same pair for the reference's PureEdDSA gadget, whose hash is the
 windowed Pedersen hash in the circuit (jubjub_gadgets.eddsa_pure_circuit, k_eddsa_fill_pure).
+EdDSAVerifier("hash").hash_circuit() and fill_hash_witnesses are the pair for the reference's EdDSA gadget, which hashes the message in the
+circuit first (jubjub_gadgets.EddsaHashCircuit, k_eddsa_fill_hash).
 
-EdDSASigner is the reference's _SignatureScheme.sign in bulk: sign(keys, msgs) gives (A, sigs) in the shape verify() and the two fills take, so
+EdDSASigner is the reference's _SignatureScheme.sign in bulk: sign(keys, msgs) gives (A, sigs) in the shape verify() and the three fills take, so
 sign -> verify -> fill witnesses -> prove runs on the device from end to end.  The kernel is not constant-time (include/zkhip.h): it is for bulk
 generation of signatures, not for keys that must withstand a co-tenant of the device.
 """
@@ -36,6 +38,7 @@ _OPS = {"add": 0, "double": 1, "negate": 2}                     # ZK_JJ_OP_*
 _SYMBOLS = ("zk_jj_hash_to_point", "zk_jj_pedersen_basepoint", "zk_jj_point_op", "zk_jj_scalar_mul", "zk_pedersen_create", "zk_pedersen_free",
             "zk_pedersen_hash", "zk_pedersen_table", "zk_eddsa_create", "zk_eddsa_free", "zk_eddsa_verify_batch", "zk_eddsa_fill_witnesses",
             "zk_eddsa_fill_pure_witnesses")
+_HASH_FILL_SYMBOLS = ("zk_eddsa_fill_hash_witnesses",)           # checked by the first fill_hash_witnesses alone, likewise
 _SIGN_SYMBOLS = ("zk_eddsa_sign_batch", "zk_eddsa_sign_probe")   # checked by the signer alone: a library without them still serves the rest
 
 
@@ -47,6 +50,11 @@ class EddsaLayout(C.Structure):
 class EddsaPureLayout(C.Structure):
     """zk_eddsa_pure_layout: the segments of a witness row of the PureEdDSA circuit (jubjub_gadgets.EddsaPureLayout, field for field)"""
     _fields_ = [(n, C.c_uint32) for n in JG.PURE_LAYOUT_FIELDS]
+
+
+class EddsaHashLayout(C.Structure):
+    """zk_eddsa_hash_layout: the segments of a witness row of the EdDSA ("hash") circuit (jubjub_gadgets.EddsaHashLayout, field for field)"""
+    _fields_ = [(n, C.c_uint32) for n in JG.HASH_LAYOUT_FIELDS]
 
 
 def generator():
@@ -73,6 +81,15 @@ def _lib():
     lib.zk_eddsa_verify_batch.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p]
     lib.zk_eddsa_fill_witnesses.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     lib.zk_eddsa_fill_pure_witnesses.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    return lib
+
+
+def _hash_fill_lib():
+    lib = _lib()
+    missing = [n for n in _HASH_FILL_SYMBOLS if not hasattr(lib, n)]
+    if missing:
+        raise ImportError("%s has no witness fill for the EdDSA (\"hash\") circuit (%s): it was built before k_eddsa_fill_hash" % (P._lib_path_loaded or P.LIB_PATH, missing[0]))
+    lib.zk_eddsa_fill_hash_witnesses.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     return lib
 
 
@@ -240,6 +257,7 @@ class EdDSAVerifier:
         self.B = (int(B[0]), int(B[1])) if B is not None else None
         self._circuit = None
         self._pedersen_circuit = None
+        self._hash_circuit = None
         self._h = C.c_void_p()
         b = _point_limbs([B]) if B is not None else None
         P._check(self._lib.zk_eddsa_create(SCHEMES[scheme], _ptr(b) if b is not None else None, self.msg_len, int(device), C.byref(self._h)))
@@ -270,7 +288,8 @@ class EdDSAVerifier:
 
     def _circuit_object(self):
         if self.scheme != "mimc":
-            raise NotImplementedError('only the "mimc" scheme has a circuit; the Pedersen hash of "%s" has no gadget here' % self.scheme)
+            raise NotImplementedError('only the "mimc" scheme has the MiMC circuit; "%s" has %s' % (
+                self.scheme, "pedersen_circuit() and fill_pedersen_witnesses" if self.scheme == "pure" else "hash_circuit() and fill_hash_witnesses"))
         if self._circuit is None:
             self._circuit = JG.EddsaMimcCircuit(self.msg_len, self.B)
         return self._circuit
@@ -309,8 +328,8 @@ class EdDSAVerifier:
 
     def _pedersen_circuit_object(self):
         if self.scheme != "pure":
-            raise NotImplementedError('only the "pure" scheme has a circuit with the Pedersen hash in it; "mimc" has circuit(), "hash" has '
-                                      'jubjub_gadgets.EddsaHashCircuit and no device fill')
+            raise NotImplementedError('only the "pure" scheme has the PureEdDSA circuit; "mimc" has circuit() and fill_witnesses, "hash" has '
+                                      'hash_circuit() and fill_hash_witnesses')
         if self._pedersen_circuit is None:
             self._pedersen_circuit = JG.EddsaPureCircuit(self.msg_len, self.B)
         return self._pedersen_circuit
@@ -347,6 +366,49 @@ class EdDSAVerifier:
         verdicts = np.full(max(n, 1), 255, dtype=np.uint8)
         P._check(self._lib.zk_eddsa_fill_pure_witnesses(self._h, _ptr(a), _ptr(r), _ptr(s), _ptr(m), n, C.c_void_p(ptr), C.c_uint64(int(row_elems)),
                                                         C.byref(EddsaPureLayout(*lay)), _ptr(verdicts)))
+        return [bool(v) for v in verdicts[:n]], out
+
+    def _hash_circuit_object(self):
+        if self.scheme != "hash":
+            raise NotImplementedError('only the "hash" scheme has the EdDSA circuit that hashes the message first; "mimc" has circuit() and '
+                                      'fill_witnesses, "pure" has pedersen_circuit() and fill_pedersen_witnesses')
+        if self._hash_circuit is None:
+            self._hash_circuit = JG.EddsaHashCircuit(self.msg_len, self.B)
+        return self._hash_circuit
+
+    def hash_circuit(self):
+        """(R1CS, layout) of the EdDSA circuit that accepts this verifier's signatures: jubjub_gadgets.EddsaHashCircuit for its msg_len and B, the
+        message hashed in the circuit ("EdDSA_Verify.M") before PureEdDSA over the bits of that hash.  Public inputs: A.x, A.y, the 8 msg_len
+        message bits.  layout: a jubjub_gadgets.EddsaHashLayout; a row has layout.n_vars + 1 elements"""
+        c = self._hash_circuit_object()
+        return c.r1cs(), c.layout
+
+    def fill_hash_witnesses(self, A, sigs, msgs, out=None, row_elems=None, layout=None):
+        """fill_pedersen_witnesses for the circuit of hash_circuit(): the complete rows of a batch written on the device, Montgomery, ready for
+        submit_batch(device_ptr=...).  Returns (verdicts, out).  A wrong signature still gets its row; an item with A or R off the curve or
+        s >= 2^254 gets the verdict False and its row is left as it was.  A, sigs, msgs as verify(); the circuit, unlike verify(), refuses an R of
+        low order and takes any s below 2^254.  ImportError from a library that was built before this entry point"""
+        c = self._hash_circuit_object()
+        lib = _hash_fill_lib()
+        A, sigs, msgs, n = self._items(A, sigs, msgs)
+        lay = c.layout if layout is None else layout
+        if row_elems is None:
+            row_elems = lay.n_vars + 1
+        msgs = [bytes(m) for m in msgs]
+        if any(len(m) != self.msg_len for m in msgs):
+            raise ValueError("a message does not have msg_len bytes")
+        if out is None:
+            out = P.DeviceBuffer(32 * int(row_elems) * max(n, 1))
+        if isinstance(out, P.DeviceBuffer) and n * int(row_elems) * 32 > out.nbytes:
+            raise ValueError("the device buffer is smaller than n rows")
+        ptr = out.ptr if isinstance(out, P.DeviceBuffer) else int(out)
+        a = _point_limbs(A)
+        r = _point_limbs([R for R, _ in sigs])
+        s = F.ints_to_limbs([int(v) for _, v in sigs]) if n else np.zeros((0, 4), dtype=np.uint64)
+        m = np.frombuffer(b"".join(msgs), dtype=np.uint8).copy() if n else np.zeros(1, dtype=np.uint8)
+        verdicts = np.full(max(n, 1), 255, dtype=np.uint8)
+        P._check(lib.zk_eddsa_fill_hash_witnesses(self._h, _ptr(a), _ptr(r), _ptr(s), _ptr(m), n, C.c_void_p(ptr), C.c_uint64(int(row_elems)),
+                                                  C.byref(EddsaHashLayout(*lay)), _ptr(verdicts)))
         return [bool(v) for v in verdicts[:n]], out
 
     def verify(self, A, sigs, msgs):
@@ -410,7 +472,7 @@ class EdDSASigner:
 
     def sign(self, keys, msgs):
         """keys: ints in (0, L); msgs: bytes objects (lists of ints for "mimc"), one per key.  Returns (A, sigs): the public keys key B as points
-        and [(R, s), ..], what EdDSAVerifier.verify(A, sigs, msgs), fill_witnesses and fill_pedersen_witnesses take.  s is the integer mod 8 L.
+        and [(R, s), ..], what EdDSAVerifier.verify(A, sigs, msgs) and the three fills take.  s is the integer mod 8 L.
         ZkError (ZK_ERR_ARG) for a key that is 0 or >= L or a "mimc" message element >= r; nothing is signed then"""
         keys = [int(k) for k in keys]
         msgs = list(msgs)

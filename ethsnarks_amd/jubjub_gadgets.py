@@ -976,10 +976,32 @@ def eddsa_pure_circuit(msg_len=1, B=None, A=None, R=None, s=None, msg=None):
     return c.pb, c.layout
 
 
+HASH_LAYOUT_FIELDS = tuple(f for f in PURE_LAYOUT_FIELDS if f != "pad_bit0") + (
+    "m_pad_bit0", "m_window_var0", "m_mont_adder_var0", "m_converter_var0", "m_edwards_adder_var0", "m_bit0", "m_range_var0")
+EddsaHashLayout = namedtuple("EddsaHashLayout", HASH_LAYOUT_FIELDS)
+EddsaHashLayout.__doc__ = """Where the segments of a witness row of EddsaHashCircuit start (variable indices; variable 0 is ONE; a row has n_vars + 1 elements).
+Every field of EddsaPureLayout but pad_bit0, with the same meaning: the hash "EdDSA_Verify.RAM" covers bits(R.x) || bits(A.x) || bits(M.x), 762
+bits, so W = 254 windows in S = 5 segments of 62, 62, 62, 62 and 6, no padding bit and no lone window.  For the message hash "EdDSA_Verify.M", with
+W_m = ceil(8 msg_len / 3) windows and S_m = ceil(W_m / 62) segments (a lone last window when W_m % 62 == 1):
+    m_pad_bit0            (-8 msg_len) mod 3 padding bits, zero                  (none when msg_len is a multiple of 3)
+    m_window_var0         W_m x (b0b1, the looked-up Montgomery y)               stride 2
+    m_mont_adder_var0     (W_m - S_m) x (lambda, X3, Y3)                         stride 3
+    m_converter_var0      S_m x (x, y) in the order of point_converters: the lone window's first
+    m_edwards_adder_var0  (S_m - 1) x 7                                          (none when W_m <= 62, msg_len <= 23)
+    m_bit0                254 bits, 253 results, 254 comparisons of field2bits_strict(M.x): the bits are the third part of the RAM hash's input
+    m_range_var0          the 99 running products of BitsNotAbove(those bits, r - 1)
+An empty segment's field holds the variable the segment would start at."""
+
+
+def hash_msg_windows(msg_len):
+    """windows of the message hash of EddsaHashCircuit: 8 msg_len bits, the last window zero-padded"""
+    return (8 * msg_len + 2) // 3
+
+
 class EddsaHashCircuit:
     """The reference's EdDSA: M = PedersenHashToBits("EdDSA_Verify.M", the message bits) and PureEdDSA over the 254 bits of M.  Public inputs and
     additions as eddsa_pure_circuit, a BitsNotAbove behind the fourth decomposition too, zero padding bits for the message hash when 8 msg_len
-    is no multiple of 3.  Host Python only: the device fills no witness of this circuit"""
+    is no multiple of 3.  .layout (an EddsaHashLayout) is the row that k_eddsa_fill_hash fills on the device"""
 
     def __init__(self, msg_len=1, B=None):
         if int(msg_len) < 1:
@@ -991,10 +1013,20 @@ class EddsaHashCircuit:
         pb.set_input_sizes(2 + 8 * self.msg_len)
         self.rx, self.ry = pb.allocate(), pb.allocate()
         self.s_bits = pb.allocate_array(N_S_BITS)
+        mark = lambda: len(pb.values)
+        at = {"m_pad_bit0": mark()}
         self.pad_bits = pb.allocate_array((-8 * self.msg_len) % 3)
+        at["m_window_var0"] = mark()
         self.msg_hashed = PedersenHashToBits(pb, PEDERSEN_MSG_SEED, self.msg_bits + self.pad_bits)
+        fb = self.msg_hashed.hash.commitment
+        at["m_bit0"] = self.msg_hashed.tobits.bits[0]
+        at["m_mont_adder_var0"], at["m_converter_var0"] = fb.montgomery_adders[0].lam, fb.point_converters[0].x2
+        at["m_edwards_adder_var0"] = fb.edward_adders[0].beta if fb.edward_adders else at["m_bit0"]
+        at["m_range_var0"] = mark()
         self.msg_range = BitsNotAbove(pb, self.msg_hashed.result(), FR - 1)
         self.core = _PureCore(pb, self.B, self.ax, self.ay, self.rx, self.ry, self.s_bits, self.msg_hashed.result())
+        self.layout = EddsaHashLayout(msg_len=self.msg_len, n_vars=len(pb.values) - 1, ax_var=self.ax, msg_bit0=self.msg_bits[0], rx_var=self.rx,
+                                      s_bit0=self.s_bits[0], **at, **self.core.at_var)
         for b in self.s_bits + self.msg_bits:
             pb.add_r1cs_constraint(V(b), lc_add(1, lc_scale(V(b), -1)), 0)
         for b in self.pad_bits:
@@ -1028,6 +1060,6 @@ class EddsaHashCircuit:
 
 
 def eddsa_hash_circuit(msg_len=1, B=None):
-    """(protoboard, None) of EddsaHashCircuit: the reference's EdDSA, M hashed with the Pedersen hash before PureEdDSA"""
+    """(protoboard, EddsaHashLayout) of EddsaHashCircuit: the reference's EdDSA, M hashed with the Pedersen hash before PureEdDSA"""
     c = EddsaHashCircuit(msg_len, B)
-    return c.pb, None
+    return c.pb, c.layout

@@ -66,7 +66,8 @@ extern "C" {
  * 8: zk_eddsa_fill_witnesses and zk_eddsa_layout.
  * 9: zk_eddsa_fill_pure_witnesses and zk_eddsa_pure_layout.
  *    (zk_eddsa_sign_batch and zk_eddsa_sign_probe came later WITHOUT a bump: no struct changed layout and no function changed signature.  A
- *    client that needs the signer detects it by its symbol.)
+ *    client that needs the signer detects it by its symbol.  zk_eddsa_fill_hash_witnesses and zk_eddsa_hash_layout came the same way: a new
+ *    function and a new struct beside the old ones, detected by the symbol.)
  * A client checks zk_abi_version() == ZK_ABI_VERSION once after loading the library, or passes the size of the zk_config
  * it was compiled with to zk_ctx_create_sized (members it does not know read as 0 = their defaults). */
 #define ZK_ABI_VERSION 9
@@ -548,6 +549,31 @@ typedef struct {
 } zk_eddsa_pure_layout;
 int zk_eddsa_fill_pure_witnesses(zk_eddsa *v, const uint64_t *A /* n x 8 */, const uint64_t *R /* n x 8 */, const uint64_t *s /* n x 4 */, const uint8_t *msgs /* n x msg_len bytes */,
                                  uint32_t n, void *d_w, uint64_t row_elems, const zk_eddsa_pure_layout *layout, uint8_t *verdicts /* n */);
+/* The EdDSA circuit of the "hash" scheme (ZK_EDDSA_HASH only) -- EddsaHashCircuit of ethsnarks_amd/jubjub_gadgets.py, the reference's EdDSA gadget: the
+ * PureEdDSA circuit above over the 254 strict bits of M.x, M = the windowed Pedersen hash "EdDSA_Verify.M" of the message bits, hashed IN THE CIRCUIT too,
+ * with a range check behind that fourth decomposition.  The hash "EdDSA_Verify.RAM" covers 3 x 254 bits: W = 254 windows, S = 5 segments (62, 62, 62,
+ * 62, 6), no padding bit, no lone window.  The message hash has W_m = ceil(8 msg_len / 3) windows in S_m = ceil(W_m / 62) segments, a lone last window
+ * when W_m % 62 == 1.  zk_eddsa_hash_layout: every member of zk_eddsa_pure_layout but pad_bit0, with the same meaning, then the message hash's:
+ * m_pad_bit0 ((-8 msg_len) mod 3 zero padding bits) | m_window_var0 (W_m x (b0b1, Montgomery y)) | m_mont_adder_var0 ((W_m - S_m) x 3) |
+ * m_converter_var0 (S_m x (x, y), the lone window's first) | m_edwards_adder_var0 ((S_m - 1) x 7) | m_bit0 (254 bits, 253 results, 254 comparisons of
+ * M.x) | m_range_var0 (99 range products).  A segment WITHOUT elements (no padding bit when msg_len is a multiple of 3; no Edwards adder when
+ * msg_len <= 23) is not there: its member is not looked at.
+ * zk_eddsa_fill_hash_witnesses has the contract of zk_eddsa_fill_pure_witnesses: ZK_ERR_ARG and nothing written for a handle that is not ZK_EDDSA_HASH,
+ * row_elems < n_vars + 1, a layout whose msg_len is not the verifier's, a segment outside variables 1 .. n_vars or overlapping another, a coordinate
+ * >= r, a null argument with n > 0; n = 0 succeeds; a well-formed wrong signature gets its full row and verdict 0; a malformed item (A or R off the
+ * curve, s >= 2^254) gets verdict 0 and an untouched row; verdicts[i] is zk_eddsa_verify_batch's.  One kernel launch, one lane per signature, THREE
+ * field inversions per witness whatever msg_len (csrc/jubjub.hpp k_eddsa_fill_hash).  The handle's first call builds the tables that only the
+ * fill reads -- the circuit's fixed-base windows of B and the Montgomery form of both Pedersen tables, 32 x (1 524 + 8 (254 + W_m)) bytes of device
+ * memory, freed with the handle -- so zk_eddsa_create costs a verify-only user what it did; like every call on a zk_eddsa it must not run beside
+ * another call on the same handle. */
+typedef struct {
+    uint32_t msg_len, n_vars, ax_var, msg_bit0, rx_var, s_bit0, validator_var0, window_var0, fixed_adder_var0, rx_bit0, rx_range_var0,
+             ax_bit0, ax_range_var0, hash_window_var0, mont_adder_var0, converter_var0, edwards_adder_var0, t_bit0, t_range_var0, cond0_var,
+             doubler_var0, cond_var0, adder_var0, step_stride, last_adder_var0, m_pad_bit0, m_window_var0, m_mont_adder_var0, m_converter_var0,
+             m_edwards_adder_var0, m_bit0, m_range_var0;
+} zk_eddsa_hash_layout;
+int zk_eddsa_fill_hash_witnesses(zk_eddsa *v, const uint64_t *A /* n x 8 */, const uint64_t *R /* n x 8 */, const uint64_t *s /* n x 4 */, const uint8_t *msgs /* n x msg_len bytes */,
+                                 uint32_t n, void *d_w, uint64_t row_elems, const zk_eddsa_hash_layout *layout, uint8_t *verdicts /* n */);
 /* The signer (csrc/eddsa_sign.hpp): _SignatureScheme.sign of ethsnarks/eddsa.py for n keys and messages in ONE kernel launch, one lane per
  * signature.  Scheme, B and msg_len are the handle's; msgs as zk_eddsa_verify_batch takes them.  Per item: r = int_le(SHA-512(key as 32 little-endian
  * bytes || the bytes of M)) mod L, R = r B, A = key B, t = H(R, A, M) as the verifier computes it, s = (r + key t) mod 8 L.  The bytes of M: the message

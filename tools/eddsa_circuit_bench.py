@@ -3,10 +3,12 @@ event pairs after a warm-up call at n = 1, 32, 1 024 and 2^14, the field product
 rate (tools/mulbench, "mul chain 8 waves/SIMD", passed as --chain in G/s) that the kernel reaches, the time of submit_batch + collect for the
 same k on the same circuit, and the front end's generate_r1cs_witness per signature on the CPU.  Prints the table and, with --out, also writes it to that file: profiles/eddsa_circuit.txt is such a run.
 --scheme pure measures the PureEdDSA circuit instead (zk_eddsa_fill_pure_witnesses, k_eddsa_fill_pure; msg_len in bytes); profiles/eddsa_pure_circuit.txt
-holds both schemes from one session.
+holds both schemes from one session.  --scheme hash measures the EdDSA circuit that hashes the message first (zk_eddsa_fill_hash_witnesses,
+k_eddsa_fill_hash); profiles/eddsa_hash_circuit.txt holds it beside the pure scheme, one session.
 
     python tools/eddsa_circuit_bench.py --chain 142.4 --out profiles/eddsa_circuit.txt
     python tools/eddsa_circuit_bench.py --scheme pure --chain 142.4
+    python tools/eddsa_circuit_bench.py --scheme hash --chain 142.4
 """
 import argparse
 import os
@@ -63,13 +65,48 @@ def products_pure(msg_len):
     }
 
 
+def hash_walk(W):
+    """one in-circuit Pedersen hash of W windows as products_pure counts it: (segments, Edwards additions, forward, back, closing products)"""
+    lone = 1 if W % 62 == 1 else 0
+    seg = [min(62, W - lone - j) for j in range(0, W - lone, 62)]
+    n_ed = len(seg) + lone - 1
+    return seg, n_ed, sum(13 * m - 12 for m in seg) + lone + n_ed * (1 + ADD + 1), sum(12 * m - 10 for m in seg) + 4 * n_ed, 5 * n_ed + 1
+
+
+def products_hash(msg_len):
+    """field products of one lane of k_eddsa_fill_hash, part by part: k_eddsa_fill_pure with the message hash in front of the first inversion and
+    the RAM hash, 254 windows whatever msg_len, behind an inversion of its own"""
+    steps, fixed = 253, 126
+    Wm = (8 * msg_len + 2) // 3
+    mseg, m_ed, m_fwd, m_back, m_close = hash_walk(Wm)
+    rseg, r_ed, r_fwd, r_back, r_close = hash_walk(254)
+    return {
+        "inputs: conversions, two curve equations": 4 + 2 * CURVE,
+        "validator: three doublings, x of 8 R": 1 + 3 * (DBL + 1) + 1,
+        "fixed base: 126 mixed additions": 1 + fixed * (MIXED + 1),
+        "message hash, forward: %d windows in %d segments, 13 m - 12 each; %d Edwards additions" % (Wm, len(mseg), m_ed): m_fwd,
+        "the first inversion": INV,
+        "message hash, back: 12 m - 10 a segment, 4 an Edwards addition": m_back,
+        "the way back of validator and fixed base": 4 * (3 + fixed) + 3,
+        "Edwards adders of the message hash (5 each), M.x": m_close,
+        "RAM hash, forward: 254 windows in %d segments; %d Edwards additions" % (len(rseg), r_ed): r_fwd,
+        "the second inversion": INV,
+        "RAM hash, back": r_back,
+        "Edwards adders of the RAM hash (5 each), t": r_close,
+        "variable base: 253 x (doubling, d T, addition), R + t A": 2 + steps * (DBL_T + 1 + 1 + ADD + 1) + 2 + MIXED + 1,
+        "the third inversion": INV,
+        "its way back: 4 per parked point": 4 * (2 * steps + 1),
+        "gadget products: 5 per doubler, 5 per adder, xx, yy": 5 * (3 + steps) + 5 * (fixed + steps + 1) + 2,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--chain", type=float, required=True, help="product-chain rate of the same session in G products/s")
     ap.add_argument("--sizes", type=int, nargs="*", default=[1, 32, 1024, 1 << 14])
     ap.add_argument("--prove-up-to", type=int, default=32, help="largest k that is also proven (submit_batch + collect)")
     ap.add_argument("--msg-len", type=int, default=1)
-    ap.add_argument("--scheme", choices=["mimc", "pure"], default="mimc")
+    ap.add_argument("--scheme", choices=["mimc", "pure", "hash"], default="mimc")
     ap.add_argument("--out", help="also write every printed line to this file")
     a = ap.parse_args()
     out = open(a.out, "w") if a.out else None
@@ -80,20 +117,20 @@ def main():
             out.write(line + "\n")
             out.flush()
     L = J._lib()
-    pure = a.scheme == "pure"
-    parts = products_pure(a.msg_len) if pure else products(a.msg_len)
+    parts = {"mimc": products, "pure": products_pure, "hash": products_hash}[a.scheme](a.msg_len)
+    n_inv = {"mimc": 1, "pure": 2, "hash": 3}[a.scheme]
     total = sum(parts.values())
     emit("%s, scheme %s, chain rate %.2f G products/s, msg_len %d" % (L.zk_version().decode(), a.scheme, a.chain, a.msg_len))
     for label, v in parts.items():
         emit("    %6d  %s" % (v, label))
-    emit("    %6d  products per witness, %d inversion%s" % (total, 2 if pure else 1, "s" if pure else ""))
+    emit("    %6d  products per witness, %d inversion%s" % (total, n_inv, "s" if n_inv > 1 else ""))
     prng = random.Random(8)
     signed = [JC.sign(a.scheme, JC.make_msg(a.scheme, a.msg_len, prng), prng.randrange(1, JC.L)) for _ in range(32)]
     signed = [(A, (R, s % (1 << 254)), m) for A, (R, s), m in signed]
     with J.EdDSAVerifier(a.scheme, msg_len=a.msg_len) as v:
-        r, lay = v.pedersen_circuit() if pure else v.circuit()
-        c = v._pedersen_circuit if pure else v._circuit
-        fill = v.fill_pedersen_witnesses if pure else v.fill_witnesses
+        r, lay = {"mimc": v.circuit, "pure": v.pedersen_circuit, "hash": v.hash_circuit}[a.scheme]()
+        c = {"mimc": v._circuit, "pure": v._pedersen_circuit, "hash": v._hash_circuit}[a.scheme]
+        fill = {"mimc": v.fill_witnesses, "pure": v.fill_pedersen_witnesses, "hash": v.fill_hash_witnesses}[a.scheme]
         want = [JC.verify(a.scheme, x[0], x[1], x[2]) for x in signed]
         t0 = time.perf_counter()
         for A, (R, s), m in signed[:8]:
