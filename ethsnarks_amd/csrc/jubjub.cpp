@@ -500,6 +500,39 @@ extern "C" int zk_eddsa_fill_witnesses(zk_eddsa *v, const uint64_t *A, const uin
     return ZK_OK;
 } ZK_GUARD
 
+// zk_eddsa_fill_witnesses with `lanes` lanes per witness: 1 is that call itself (k_eddsa_fill), 2 and 4 launch k_eddsa_fill_wide over workgroups of
+// 64 x lanes threads.  lanes is checked first, then that call's checks in its order; the same rows byte for byte
+extern "C" int zk_eddsa_fill_witnesses_wide(zk_eddsa *v, const uint64_t *A, const uint64_t *R, const uint64_t *s, const uint64_t *msgs, uint32_t n, void *d_w,
+                                            uint64_t row_elems, const zk_eddsa_layout *layout, uint8_t *verdicts, uint32_t lanes) try {
+    if (lanes != 1 && lanes != 2 && lanes != 4) return jfail(ZK_ERR_ARG, "lanes per witness: 1, 2 or 4");
+    if (lanes == 1) return zk_eddsa_fill_witnesses(v, A, R, s, msgs, n, d_w, row_elems, layout, verdicts);
+    if (!v || !A || !R || !s || !msgs || !d_w || !layout || !verdicts) return jfail(ZK_ERR_ARG, "null argument");
+    if (v->scheme != SCHEME_MIMC) return jfail(ZK_ERR_ARG, "only a ZK_EDDSA_MIMC verifier has a circuit to fill witnesses of");
+    FillLayout L;
+    memcpy(&L, layout, sizeof(L));
+    if (!layout_fits(L, v->msg_len, row_elems)) return jfail(ZK_ERR_ARG, "the layout does not fit the verifier's msg_len, overlaps itself or leaves the row");
+    if (n == 0) return ZK_OK;
+    if (!all_below_modulus(A, 2 * (uint64_t)n) || !all_below_modulus(R, 2 * (uint64_t)n)) return jfail(ZK_ERR_ARG, "a coordinate is not below the Fr modulus");
+    if (!all_below_modulus(msgs, (uint64_t)n * v->msg_len)) return jfail(ZK_ERR_ARG, "a message element is not below the Fr modulus");
+    ZK_TRY(jj_use_device(v->device));
+    const size_t pb = 2 * sizeof(fe) * (size_t)n, sb = sizeof(fe) * (size_t)n, mb = sb * v->msg_len;
+    ZK_TRY(v->scratch.ensure(2 * pb + sb + mb + align32(n)));
+    char *d = (char *)v->scratch.p;
+    char *dA = d, *dR = d + pb, *dS = d + 2 * pb, *dM = dS + sb, *dV = dM + mb;
+    ZK_HIP(hipMemcpyAsync(dA, A, pb, hipMemcpyHostToDevice, v->st));
+    ZK_HIP(hipMemcpyAsync(dR, R, pb, hipMemcpyHostToDevice, v->st));
+    ZK_HIP(hipMemcpyAsync(dS, s, sb, hipMemcpyHostToDevice, v->st));
+    ZK_HIP(hipMemcpyAsync(dM, msgs, mb, hipMemcpyHostToDevice, v->st));
+    if (lanes == 2) ZK_LAUNCH_SYNC((k_eddsa_fill_wide<2>), zk_div_up(n, BLOCK), BLOCK * 2, v->st, v->view, v->fbtab, L, (const fe *)dA, (const fe *)dR, (const fe *)dS,
+                                   (const fe *)dM, n, (fe *)d_w, row_elems, (uint8_t *)dV);
+    else ZK_LAUNCH_SYNC((k_eddsa_fill_wide<4>), zk_div_up(n, BLOCK), BLOCK * 4, v->st, v->view, v->fbtab, L, (const fe *)dA, (const fe *)dR, (const fe *)dS,
+                        (const fe *)dM, n, (fe *)d_w, row_elems, (uint8_t *)dV);
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipMemcpyAsync(verdicts, dV, n, hipMemcpyDeviceToHost, v->st));
+    ZK_HIP(hipStreamSynchronize(v->st));
+    return ZK_OK;
+} ZK_GUARD
+
 namespace {
 // the PureEdDSA row: as layout_fits, with the hash's segments sized by the window count of the verifier's msg_len
 bool pure_layout_fits(const PureLayout &L, uint32_t msg_len, uint64_t row_elems) {

@@ -26,6 +26,7 @@
 //   k_jj_pedersen     n windowed Pedersen hashes over a table of affine multiples in device memory, the window count per lane
 //   k_eddsa_verify    n verdicts S B == R + t A, t = H(R, A, M) computed here for the three schemes of eddsa.py
 //   k_eddsa_fill      n complete witness rows of the MiMC-EdDSA circuit, one field inversion per row
+//   k_eddsa_fill_wide the same rows with 2 or 4 lanes per witness, one per wave of a workgroup of 2 or 4 waves: a shorter dependent chain
 //   k_eddsa_fill_pure n complete witness rows of the PureEdDSA circuit (in-circuit Pedersen hash), two field inversions per row
 //   k_eddsa_fill_hash n complete witness rows of the EdDSA circuit (the message hashed in the circuit first), three field inversions per row (at the end of this file)
 #pragma once
@@ -522,6 +523,232 @@ k_eddsa_fill(EddsaView v, const fe *__restrict__ fbtab, FillLayout L, const fe *
     }
     const fe *lhs = row + L.fixed_adder_var0 + ADD_VARS * (size_t)(FB_WINDOWS - 2) + ADD_VARS - 2, *rhs = row + L.last_adder_var0 + ADD_VARS - 2;
     verdicts[g] = Fr::eq(lhs[0], rhs[0]) && Fr::eq(lhs[1], rhs[1]) ? 1 : 0;
+}
+
+// ---- k_eddsa_fill with ROLES = 2 or 4 lanes per witness: the same row, byte for byte, off a shorter dependent chain.
+//
+// Roles are WAVE-UNIFORM.  A workgroup is ROLES waves; witness blockIdx.x * 64 + (threadIdx.x & 63) is served by lane (threadIdx.x & 63) of every
+// wave, and the wave number threadIdx.x >> 6 is the role, so a branch on the role never splits a wave.  Three phases, two barriers:
+//   forward   role 0: the message elements, MiMC, t with its bits and range products, then both variable-base chains and R + t A, parked as
+//             k_eddsa_fill parks them; role 1: the other inputs, the bits of s, the validator, the x of 8 R and the fixed-base chain.  The 637
+//             parked items form NSEG segments (WideCut) with a running product each: role 1's 130 items are segment 0, role 0 restarts its
+//             running product after the steps var_end(k).  Every segment's total, and t, go to LDS.  Further roles idle here.
+//   way back  every role multiplies the totals and inverts the product itself (381 products on all waves at once instead of a third barrier and
+//             a broadcast), takes inverse x the OTHER totals as the inverse of a segment it owns, and unparks that segment.
+//   gadgets   the products of affine inputs, split evenly by adder and step index; role ROLES - 1 adds the validator's, role 0 the closing
+//             adder's and the verdict.
+// LDS: (NSEG + 1) slots of 64 x 32 B, each written once before the first barrier and read after it; nothing in LDS is written twice.
+//
+// Why __syncthreads() alone orders the ROWS, which are global memory written by one wave and read by another on either side of a barrier: a
+// workgroup runs on ONE compute unit, whose waves share that unit's one vector L1 (write-through); only workgroups on different units need
+// agent-scope release and acquire (workgroup scope does not reach another unit, and need not here).  __syncthreads() is a workgroup-scope
+// release fence, s_barrier, and a workgroup-scope acquire fence: the compiler moves no load or store of the rows across it.  For gfx950 it emits
+// s_waitcnt lgkmcnt(0) (LDS) and s_barrier with NO vmcnt wait, which is the AMDGPU memory model for this family outside threadgroup-split mode:
+// the vector memory requests of all waves of a unit enter its one L1 in issue order, so a store issued before the barrier is ahead of any load
+// another wave issues behind it, and needs no completion wait to be seen.  k_mimc_merkle_tail (merkle.hpp) hands tree levels from wave to wave
+// the same way.  Every access to a row is a per-lane vector load or store through the non-restrict d_w: nothing of a row goes through the
+// scalar cache, which that argument does not cover.
+//
+// No lane returns before the last barrier: `live` (in range, A and R on the curve, s < 2^254 -- computed by every role for itself) guards every
+// load and store of a witness, the barriers stand outside it.  A malformed item: verdict 0 from role 0, the row untouched by every role.
+template <uint32_t ROLES> struct WideCut {
+    static constexpr uint32_t NV = ROLES == 4 ? 3 : 2, NSEG = NV + 1;   // segment 0: validator, x of 8 R, fixed base; 1 + k: the steps up to var_end(k)
+    // the last step of variable segment k (the last segment also holds the closing adder).  4 roles: 129 + 1 | 168 | 170 | 169 items, one segment
+    // a role; 2 roles: role 1 owns 129 + 1 and 188, role 0 owns 319
+    ZK_HD static constexpr uint32_t var_end(uint32_t k) { return ROLES == 4 ? (k == 0 ? 84 : k == 1 ? 169 : N_STEPS) : (k == 0 ? 94 : N_STEPS); }
+    ZK_HD static constexpr uint32_t owner(uint32_t sg) { return ROLES == 4 ? (sg == 0 ? 1 : sg == 1 ? 0 : sg) : (sg == 2 ? 0 : 1); }
+};
+
+// the way back over the steps first .. last (first >= 1) of the variable-base chains, behind the closing adder where the segment holds it
+ZK_HD void wide_unpark_var(fe *row, const FillLayout &L, uint32_t first, uint32_t last, bool closing, fe &inv) {
+    if (closing) unpark_point(row + L.last_adder_var0, ADD_VARS, inv);
+#pragma clang loop unroll(disable)
+    for (uint32_t i = last; i >= first; i--) {
+        const size_t off = (size_t)(i - 1) * L.step_stride;
+        unpark_point(row + L.adder_var0 + off, ADD_VARS, inv);
+        unpark_point(row + L.doubler_var0 + off, DBL_VARS, inv);
+    }
+}
+// the way back over segment 0: the fixed-base adders, 1 / x of 8 R, the validator's doublings
+ZK_HD void wide_unpark_fixed(fe *row, const FillLayout &L, fe &inv) {
+    fe *val = row + L.validator_var0;
+#pragma clang loop unroll(disable)
+    for (uint32_t i = FB_WINDOWS - 1; i >= 1; i--) unpark_point(row + L.fixed_adder_var0 + ADD_VARS * (size_t)(i - 1), ADD_VARS, inv);
+    {
+        fe *blk8 = val + 2 * DBL_VARS;                          // still projective: X, Y at [4], [5], Z at [0]
+        const bool nz = !Fr::is_zero(Fr::canon(blk8[4]));
+        const fe xi = Fr::lmul(inv, val[3 * DBL_VARS]);         // 1 / X (or 1 / 1)
+        inv = Fr::lmul(inv, val[3 * DBL_VARS + 1]);
+        val[3 * DBL_VARS] = bit_fe(nz);
+        val[3 * DBL_VARS + 1] = nz ? Fr::canon(Fr::lmul(blk8[0], xi)) : Fr::zero();   // 1 / x = Z / X
+    }
+#pragma clang loop unroll(disable)
+    for (int j = 2; j >= 0; j--) unpark_point(val + DBL_VARS * j, DBL_VARS, inv);
+}
+
+// arguments, malformed items, verdicts and the row as k_eddsa_fill; launched with zk_div_up(n, 64) workgroups of 64 ROLES threads
+template <uint32_t ROLES>
+__global__ void __launch_bounds__(BLOCK * ROLES)
+k_eddsa_fill_wide(EddsaView v, const fe *__restrict__ fbtab, FillLayout L, const fe *__restrict__ A, const fe *__restrict__ R, const fe *__restrict__ s,
+                  const fe *__restrict__ msgs, uint32_t n, fe *d_w, uint64_t row_elems, uint8_t *__restrict__ verdicts) {
+    using Cut = WideCut<ROLES>;
+    constexpr uint32_t NSEG = Cut::NSEG, T_SLOT = NSEG;
+    __shared__ fe xch[NSEG + 1][BLOCK];                         // the segments' totals and t, per witness of the workgroup
+    const uint32_t j = threadIdx.x & (BLOCK - 1), role = threadIdx.x / BLOCK;
+    const uint32_t g = blockIdx.x * BLOCK + j;
+    const bool in_range = g < n;
+    const size_t gi = in_range ? g : 0;                         // a lane out of range forms no address past the arrays
+    const uint32_t *__restrict__ sw = s[gi].l;
+    fe ax = Fr::zero(), ay = ax, rx = ax, ry = ax;
+    bool live = in_range;
+    if (live) {
+        load_point(A, g, ax, ay);
+        load_point(R, g, rx, ry);
+        live = on_curve(ax, ay) && on_curve(rx, ry) && !(sw[7] >> 30);
+        ax = Fr::canon(ax); ay = Fr::canon(ay); rx = Fr::canon(rx); ry = Fr::canon(ry);
+    }
+    fe *row = d_w + gi * row_elems;
+    fe *val = row + L.validator_var0;
+
+    // ---- forward
+    if (live && role == 0) {
+        const uint32_t n_hash = 4 + L.msg_len;
+        fe k = Fr::zero();
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 0; i < n_hash; i++) {                 // t = the hash, its rounds stored
+            fe xi;
+            if (i < 4) xi = i == 0 ? rx : i == 1 ? ry : i == 2 ? ax : ay;
+            else { xi = Fr::canon(jj_to_mont(msgs[(size_t)g * L.msg_len + (i - 4)])); row[L.msg_var0 + (i - 4)] = xi; }
+            const fe e = mimc_cipher_rounds(v.rc, xi, k, row + L.mimc_var0 + n_hash + (size_t)i * MIMC_ROUND_VARS);
+            k = Fr::ladd(Fr::ladd(k, xi), e);
+            row[L.mimc_var0 + i] = Fr::canon(k);
+        }
+        const fe t = jj_from_mont(k);
+        xch[T_SLOT][j] = t;
+        {
+            fe *tb = row + L.t_bit0, *res = tb + FIELD_BITS, *cmp = res + (FIELD_BITS - 1);
+            uint32_t run = 1, eq = int_bit(t.l, FIELD_BITS - 1), slot = 0;
+#pragma clang loop unroll(disable)
+            for (int i = FIELD_BITS - 1; i >= 0; i--) {         // from the top bit down, as k_eddsa_fill
+                const uint32_t b = int_bit(t.l, i), c = modulus_m1_bit(i) ? 1u : b;
+                tb[i] = bit_fe(b); cmp[i] = bit_fe(c);
+                run &= c;
+                if (i < (int)FIELD_BITS - 1) res[i] = bit_fe(run);
+                if (i < (int)FIELD_BITS - 1 && i > 0 && modulus_m1_bit(i)) { eq &= b; row[L.t_range_var0 + slot++] = bit_fe(eq); }
+            }
+        }
+        fe run = Fr::one();                                     // variable base: D = 2^i A, S += bit_i ? D : identity
+        jpoint d, p;
+        from_affine(d, ax, ay);
+        const uint32_t b0 = int_bit(t.l, 0);
+        row[L.cond0_var] = b0 ? ax : Fr::zero(); row[L.cond0_var + 1] = b0 ? ay : Fr::one();
+        from_affine(p, row[L.cond0_var], row[L.cond0_var + 1]);
+        uint32_t sg = 0;
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 1; i <= N_STEPS; i++) {
+            const size_t off = (size_t)(i - 1) * L.step_stride;
+            jj_dbl(d, true);
+            park_point(row + L.doubler_var0 + off, DBL_VARS, d, run);
+            const bool b = int_bit(t.l, i);
+            fe q[4];
+            q[0] = b ? d.c[0] : Fr::zero(); q[1] = b ? d.c[1] : Fr::one(); q[2] = b ? jj_mul(coef_d(), d.c[2]) : Fr::zero(); q[3] = b ? d.c[3] : Fr::one();
+            jj_add(p, q, false);
+            park_point(row + L.adder_var0 + off, ADD_VARS, p, run);
+            if (sg + 1 < Cut::NV && i == Cut::var_end(sg)) { xch[1 + sg][j] = run; run = Fr::one(); sg++; }   // a segment ends: its total, a new product
+        }
+        fe q[3];                                                // rhs = R + t A
+        q[0] = rx; q[1] = ry; q[2] = jj_mul(coef_d(), jj_mul(rx, ry));
+        jj_add(p, q, true);
+        park_point(row + L.last_adder_var0, ADD_VARS, p, run);
+        xch[Cut::NV][j] = run;
+    } else if (live && role == 1) {
+        row[0] = Fr::one();
+        row[L.ax_var] = ax; row[L.ax_var + 1] = ay; row[L.rx_var] = rx; row[L.rx_var + 1] = ry;
+        row[L.iv_var] = Fr::zero();
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 0; i < FIELD_BITS; i++) row[L.s_bit0 + i] = bit_fe(int_bit(sw, i));
+        fe run = Fr::one();
+        jpoint p;
+        from_affine(p, rx, ry);
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 0; i < 3; i++) { jj_dbl(p, false); park_point(val + DBL_VARS * i, DBL_VARS, p, run); }
+        {                                                       // IsNonZero(x of 8 R): Y holds the prefix, M the value (1 in the place of 0)
+            const bool nz = !Fr::is_zero(Fr::canon(p.c[0]));
+            const fe x8 = nz ? p.c[0] : Fr::one();
+            val[3 * DBL_VARS] = run; val[3 * DBL_VARS + 1] = x8;
+            run = Fr::lmul(run, x8);
+        }
+        const fe *e = fbtab + 3 * (size_t)(int_bit(sw, 0) | (int_bit(sw, 1) << 1));   // fixed base: window i adds entry (s >> 2 i) & 3 of its row
+        row[L.window_var0] = e[0]; row[L.window_var0 + 1] = e[1];
+        from_affine(p, e[0], e[1]);
+#pragma clang loop unroll(disable)
+        for (uint32_t i = 1; i < FB_WINDOWS; i++) {
+            e = fbtab + 3 * ((size_t)4 * i + (int_bit(sw, 2 * i) | (int_bit(sw, 2 * i + 1) << 1)));
+            row[L.window_var0 + 2 * i] = e[0]; row[L.window_var0 + 2 * i + 1] = e[1];
+            jj_add(p, e, true);
+            park_point(row + L.fixed_adder_var0 + ADD_VARS * (size_t)(i - 1), ADD_VARS, p, run);
+        }
+        xch[0][j] = run;
+    }
+    __syncthreads();
+
+    // ---- one inversion on every role, then each role's own segments on the way back
+    fe t = Fr::zero();
+    if (live) {
+        t = xch[T_SLOT][j];
+        fe tot[NSEG];
+        for (uint32_t k = 0; k < NSEG; k++) tot[k] = xch[k][j];
+        fe all = tot[0];
+        for (uint32_t k = 1; k < NSEG; k++) all = jj_mul(all, tot[k]);
+        const fe inv_all = jj_inv(all);
+        for (uint32_t sg = 0; sg < NSEG; sg++) {
+            if (Cut::owner(sg) != role) continue;
+            fe inv = inv_all;                                   // 1 / (this segment's total) = 1 / (all) x the other totals
+            for (uint32_t k = 0; k < NSEG; k++) if (k != sg) inv = jj_mul(inv, tot[k]);
+            if (sg == 0) wide_unpark_fixed(row, L, inv);
+            else wide_unpark_var(row, L, sg == 1 ? 1 : Cut::var_end(sg - 2) + 1, Cut::var_end(sg - 1), sg == Cut::NV, inv);
+        }
+    }
+    __syncthreads();
+
+    // ---- the products of affine inputs: adders f0 .. f1 - 1 of the fixed base and steps s0 .. s1 - 1 of the variable base on this role
+    if (live) {
+        const uint32_t f0 = (FB_WINDOWS - 1) * role / ROLES, f1 = (FB_WINDOWS - 1) * (role + 1) / ROLES;
+#pragma clang loop unroll(disable)
+        for (uint32_t i = f0; i < f1; i++) {                    // adder i: (window 0 | the previous sum) + window i + 1
+            fe *blk = row + L.fixed_adder_var0 + ADD_VARS * (size_t)i;
+            const fe *prev = i ? blk - 2 : row + L.window_var0, *w = row + L.window_var0 + 2 * (size_t)(i + 1);
+            fill_adder(blk, prev[0], prev[1], w[0], w[1]);
+        }
+        const uint32_t s0 = 1 + N_STEPS * role / ROLES, s1 = 1 + N_STEPS * (role + 1) / ROLES;
+#pragma clang loop unroll(disable)
+        for (uint32_t i = s0; i < s1; i++) {
+            const size_t off = (size_t)(i - 1) * L.step_stride;
+            fe *dbl = row + L.doubler_var0 + off, *cond = row + L.cond_var0 + off, *add = row + L.adder_var0 + off;
+            const fe *dprev = i > 1 ? dbl - L.step_stride + (DBL_VARS - 2) : row + L.ax_var;
+            const fe *sprev = i > 1 ? add - L.step_stride + (ADD_VARS - 2) : row + L.cond0_var;
+            fill_doubler(dbl, dprev[0], dprev[1]);
+            const bool b = int_bit(t.l, i);
+            cond[0] = b ? dbl[4] : Fr::zero(); cond[1] = b ? dbl[5] : Fr::one();
+            fill_adder(add, sprev[0], sprev[1], cond[0], cond[1]);
+        }
+        if (role == ROLES - 1) {
+            fill_doubler(val, rx, ry);
+            fill_doubler(val + DBL_VARS, val[4], val[5]);
+            fill_doubler(val + 2 * DBL_VARS, val[DBL_VARS + 4], val[DBL_VARS + 5]);
+            val[3 * DBL_VARS + 2] = Fr::canon(jj_mul(rx, rx)); val[3 * DBL_VARS + 3] = Fr::canon(jj_mul(ry, ry));
+        }
+    }
+    if (role == 0 && in_range) {                                // the one role that answers
+        uint8_t ok = 0;
+        if (live) {
+            const fe *sprev = row + L.adder_var0 + (size_t)(N_STEPS - 1) * L.step_stride + (ADD_VARS - 2);
+            fill_adder(row + L.last_adder_var0, rx, ry, sprev[0], sprev[1]);
+            const fe *lhs = row + L.fixed_adder_var0 + ADD_VARS * (size_t)(FB_WINDOWS - 2) + ADD_VARS - 2, *rhs = row + L.last_adder_var0 + ADD_VARS - 2;
+            ok = Fr::eq(lhs[0], rhs[0]) && Fr::eq(lhs[1], rhs[1]) ? 1 : 0;
+        }
+        verdicts[g] = ok;
+    }
 }
 
 // ---- the complete witness of the PureEdDSA circuit (jubjub_gadgets.py, eddsa_pure_circuit): the row of k_eddsa_fill with the windowed Pedersen

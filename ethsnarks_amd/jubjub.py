@@ -39,6 +39,7 @@ _SYMBOLS = ("zk_jj_hash_to_point", "zk_jj_pedersen_basepoint", "zk_jj_point_op",
             "zk_pedersen_hash", "zk_pedersen_table", "zk_eddsa_create", "zk_eddsa_free", "zk_eddsa_verify_batch", "zk_eddsa_fill_witnesses",
             "zk_eddsa_fill_pure_witnesses")
 _HASH_FILL_SYMBOLS = ("zk_eddsa_fill_hash_witnesses",)           # checked by the first fill_hash_witnesses alone, likewise
+_WIDE_FILL_SYMBOLS = ("zk_eddsa_fill_witnesses_wide",)           # checked by the first fill_witnesses(lanes > 1) alone, likewise
 _SIGN_SYMBOLS = ("zk_eddsa_sign_batch", "zk_eddsa_sign_probe")   # checked by the signer alone: a library without them still serves the rest
 
 
@@ -90,6 +91,15 @@ def _hash_fill_lib():
     if missing:
         raise ImportError("%s has no witness fill for the EdDSA (\"hash\") circuit (%s): it was built before k_eddsa_fill_hash" % (P._lib_path_loaded or P.LIB_PATH, missing[0]))
     lib.zk_eddsa_fill_hash_witnesses.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    return lib
+
+
+def _wide_fill_lib():
+    lib = _lib()
+    missing = [n for n in _WIDE_FILL_SYMBOLS if not hasattr(lib, n)]
+    if missing:
+        raise ImportError("%s has no witness fill with several lanes per signature (%s): it was built before k_eddsa_fill_wide" % (P._lib_path_loaded or P.LIB_PATH, missing[0]))
+    lib.zk_eddsa_fill_witnesses_wide.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32]
     return lib
 
 
@@ -300,11 +310,16 @@ class EdDSAVerifier:
         c = self._circuit_object()
         return c.r1cs(), c.layout
 
-    def fill_witnesses(self, A, sigs, msgs, out=None, row_elems=None, layout=None):
+    def fill_witnesses(self, A, sigs, msgs, out=None, row_elems=None, layout=None, lanes=1):
         """The complete witness rows of the circuit for a batch, written on the device, Montgomery, ready for submit_batch(device_ptr=...):
         row i of `out` (a prover.DeviceBuffer or a device address; None: a new DeviceBuffer) belongs to signature i.  Returns (verdicts, out).
         A wrong signature still gets its row (only the two closing constraints fail; the prover refuses a batch that holds it: ZK_ERR_DEGREE); an item with A or R off the curve or s >= 2^254 gets the
-        verdict False and its row is left as it was.  s may be any integer below 2^256.  A, sigs, msgs as verify()"""
+        verdict False and its row is left as it was.  s may be any integer below 2^256.  A, sigs, msgs as verify().
+        lanes: 1 (one lane walks a signature's whole row), 2 or 4 (that many lanes share it: zk_eddsa_fill_witnesses_wide -- the same rows, a shorter
+        dependent chain, for small batches).  The caller chooses; nothing here does"""
+        if lanes not in (1, 2, 4):
+            raise ValueError("lanes per signature: 1, 2 or 4")
+        wide = _wide_fill_lib() if lanes != 1 else None
         c = self._circuit_object()
         A, sigs, msgs, n = self._items(A, sigs, msgs)
         lay = c.layout if layout is None else layout
@@ -322,8 +337,12 @@ class EdDSAVerifier:
         s = F.ints_to_limbs([int(v) for _, v in sigs]) if n else np.zeros((0, 4), dtype=np.uint64)
         m = F.ints_to_limbs([int(v) for msg in msgs for v in msg]) if n else np.zeros((0, 4), dtype=np.uint64)
         verdicts = np.full(max(n, 1), 255, dtype=np.uint8)
-        P._check(self._lib.zk_eddsa_fill_witnesses(self._h, _ptr(a), _ptr(r), _ptr(s), _ptr(m), n, C.c_void_p(ptr), C.c_uint64(int(row_elems)),
-                                                   C.byref(EddsaLayout(*lay)), _ptr(verdicts)))
+        if wide is None:
+            P._check(self._lib.zk_eddsa_fill_witnesses(self._h, _ptr(a), _ptr(r), _ptr(s), _ptr(m), n, C.c_void_p(ptr), C.c_uint64(int(row_elems)),
+                                                       C.byref(EddsaLayout(*lay)), _ptr(verdicts)))
+        else:
+            P._check(wide.zk_eddsa_fill_witnesses_wide(self._h, _ptr(a), _ptr(r), _ptr(s), _ptr(m), n, C.c_void_p(ptr), C.c_uint64(int(row_elems)),
+                                                       C.byref(EddsaLayout(*lay)), _ptr(verdicts), lanes))
         return [bool(v) for v in verdicts[:n]], out
 
     def _pedersen_circuit_object(self):

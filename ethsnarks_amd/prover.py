@@ -76,7 +76,7 @@ EXPORTS = [
     "zk_mtree_create_ex", "zk_mtree_info", "zk_poseidon_constants", "zk_poseidon_hash", "zk_poseidon_permute",
     "zk_jj_hash_to_point", "zk_jj_pedersen_basepoint", "zk_jj_point_op", "zk_jj_scalar_mul", "zk_pedersen_create", "zk_pedersen_free", "zk_pedersen_hash",
     "zk_pedersen_table", "zk_eddsa_create", "zk_eddsa_free", "zk_eddsa_verify_batch", "zk_eddsa_fill_witnesses", "zk_eddsa_fill_pure_witnesses",
-    "zk_eddsa_sign_batch", "zk_eddsa_sign_probe", "zk_eddsa_fill_hash_witnesses",
+    "zk_eddsa_sign_batch", "zk_eddsa_sign_probe", "zk_eddsa_fill_hash_witnesses", "zk_eddsa_fill_witnesses_wide",
     "zk_ntt", "zk_witness_map", "zk_msm_g1", "zk_msm_g2", "zk_field_mul", "zk_fr_convert",
     "zk_arith_probe", "zk_arith_probe_shape",
     "zk_pairing_probe", "zk_pairing_probe_shape", "zk_vctx_probe_prepare",

@@ -67,7 +67,8 @@ extern "C" {
  * 9: zk_eddsa_fill_pure_witnesses and zk_eddsa_pure_layout.
  *    (zk_eddsa_sign_batch and zk_eddsa_sign_probe came later WITHOUT a bump: no struct changed layout and no function changed signature.  A
  *    client that needs the signer detects it by its symbol.  zk_eddsa_fill_hash_witnesses and zk_eddsa_hash_layout came the same way: a new
- *    function and a new struct beside the old ones, detected by the symbol.)
+ *    function and a new struct beside the old ones, detected by the symbol.  zk_eddsa_fill_witnesses_wide likewise: a new function beside
+ *    zk_eddsa_fill_witnesses, which keeps its signature; a client that wants several lanes per witness detects it by the symbol.)
  * A client checks zk_abi_version() == ZK_ABI_VERSION once after loading the library, or passes the size of the zk_config
  * it was compiled with to zk_ctx_create_sized (members it does not know read as 0 = their defaults). */
 #define ZK_ABI_VERSION 9
@@ -528,6 +529,13 @@ typedef struct {
 } zk_eddsa_layout;
 int zk_eddsa_fill_witnesses(zk_eddsa *v, const uint64_t *A /* n x 8 */, const uint64_t *R /* n x 8 */, const uint64_t *s /* n x 4 */, const uint64_t *msgs /* n x msg_len x 4 */,
                             uint32_t n, void *d_w, uint64_t row_elems, const zk_eddsa_layout *layout, uint8_t *verdicts /* n */);
+/* zk_eddsa_fill_witnesses with `lanes` lanes per witness -- the same contract, the same refusals with nothing written, the same rows byte for byte.
+ * lanes = 1 IS zk_eddsa_fill_witnesses.  lanes = 2 or 4 shortens the dependent chain of one witness (14 816 field products on one lane) to about
+ * 10 700 or 9 300: the lanes are one lane of each wave of a workgroup of 64 x lanes threads, they split the two forward walks, the way back after
+ * the one inversion and the gadgets' products, and meet at two barriers (csrc/jubjub.hpp k_eddsa_fill_wide).  For small batches, where
+ * the call's time is that chain's latency; the total work is not smaller.  Any other value of lanes: ZK_ERR_ARG.  The library never chooses lanes itself. */
+int zk_eddsa_fill_witnesses_wide(zk_eddsa *v, const uint64_t *A /* n x 8 */, const uint64_t *R /* n x 8 */, const uint64_t *s /* n x 4 */, const uint64_t *msgs /* n x msg_len x 4 */,
+                                 uint32_t n, void *d_w, uint64_t row_elems, const zk_eddsa_layout *layout, uint8_t *verdicts /* n */, uint32_t lanes);
 /* The PureEdDSA circuit (ZK_EDDSA_PURE only) -- eddsa_pure_circuit of ethsnarks_amd/jubjub_gadgets.py, the reference's PureEdDSA gadget: PointValidator(R),
  * fixed_base_mul(B, the 254 bits of s), field2bits_strict of R.x and of A.x, the windowed Pedersen hash "EdDSA_Verify.RAM" of those bits and the
  * message bits IN THE CIRCUIT (fixed_base_mul_zcash: lookup_signed_3bit, MontgomeryAdder, MontgomeryToEdwards, PointAdder), field2bits_strict of its
