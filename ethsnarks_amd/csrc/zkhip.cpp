@@ -1187,14 +1187,23 @@ extern "C" int zk_ctx_create_sized(const zk_pk *pk, const zk_csr *A, const zk_cs
 } ZK_GUARD
 extern "C" void zk_ctx_destroy(zk_ctx *ctx) try { delete ctx; } ZK_GUARD_VOID
 
+// ---- the row evaluations of the k = cur_batch witnesses in d_w: [A: k x m][B: k x m][C: k x m] in d_a, Montgomery; the row kernels write the
+// padding and A's input-consistency rows too.  Both H pipelines start with it, and zk_ctx_probe_rows is nothing else.
+static int enqueue_rows(zk_ctx *c, hipStream_t st) {
+    const uint32_t m = c->m, k = c->cur_batch, ws = c->V + 1;
+    fe *a = c->d_a, *b = c->d_a + (size_t)m * k, *cc = c->d_a + 2 * (size_t)m * k;
+    ZK_TRY(c->cA.enqueue(c->d_w, a, st, k, ws, m, m, c->nIn + 1));
+    ZK_TRY(c->cB.enqueue(c->d_w, b, st, k, ws, m, m, 0));
+    ZK_TRY(c->cC.enqueue(c->d_w, cc, st, k, ws, m, m, 0));
+    return ZK_OK;
+}
+
 // ---- "Compute the polynomial H" (tcc:460-475) on s_main; result in d_t (natural order), h[m-1] copied to h_tail
 // for the k = cur_batch proofs in flight: polynomials laid out [A: k x m][B: k x m][C: k x m] in d_a, h of proof p at d_t + p m
 static int enqueue_compute_h(zk_ctx *c, hipStream_t st) {
-    const uint32_t m = c->m, k = c->cur_batch, ws = c->V + 1;
+    const uint32_t m = c->m, k = c->cur_batch;
     fe *a = c->d_a, *b = c->d_a + (size_t)m * k, *cc = c->d_a + 2 * (size_t)m * k;
-    ZK_TRY(c->cA.enqueue(c->d_w, a, st, k, ws, m, m, c->nIn + 1));         // (the row kernels write the padding and A's input-consistency rows too)
-    ZK_TRY(c->cB.enqueue(c->d_w, b, st, k, ws, m, m, 0));
-    ZK_TRY(c->cC.enqueue(c->d_w, cc, st, k, ws, m, m, 0));
+    ZK_TRY(enqueue_rows(c, st));
     // all 3 k polynomials go through each pass together (blockIdx.y): fewer, larger launches
     // SIX transforms, not the reference's seven (libsnark: iFFT and cosetFFT of A, B and C, divide by Z on the coset, icosetFFT): C never
     // goes to the coset.  With P = A B, icosetFFT(P on the coset) is P mod (x^m - g^m) = Z(g) H + C for every witness (deg H, deg C < m,
@@ -1217,11 +1226,9 @@ static int enqueue_compute_h(zk_ctx *c, hipStream_t st) {
 // products p_j = A(g w^j) B(g w^j), canonical, in d_t (proof p at d_t + p m); the C row evaluations are scalars of nothing -- their part of h
 // is in the L-query's bases -- and only enter the degree check: h[m-1] as a dot product over p and c, copied to h_tail as above.
 static int enqueue_compute_h4(zk_ctx *c, hipStream_t st) {
-    const uint32_t m = c->m, k = c->cur_batch, ws = c->V + 1;
+    const uint32_t m = c->m, k = c->cur_batch;
     fe *a = c->d_a, *b = c->d_a + (size_t)m * k, *cc = c->d_a + 2 * (size_t)m * k;
-    ZK_TRY(c->cA.enqueue(c->d_w, a, st, k, ws, m, m, c->nIn + 1));
-    ZK_TRY(c->cB.enqueue(c->d_w, b, st, k, ws, m, m, 0));
-    ZK_TRY(c->cC.enqueue(c->d_w, cc, st, k, ws, m, m, 0));
+    ZK_TRY(enqueue_rows(c, st));
     NttFuse bscale; bscale.post_alt = c->d_bscale; bscale.alt_from = k;                                 // vectors [k, 2k) are the B polynomials: x 1 / R as well
     ZK_TRY(ntt_run(c->tab, a, c->d_t, true, nullptr, c->tab.inv_then_coset, st, 2 * k, m, bscale));   // iFFT of A, B (x g^i / m: cosetFFT pre-scale)
     ZK_TRY(ntt_run(c->tab, c->d_t, a, false, nullptr, nullptr, st, 2 * k, m));                        // FFT: A, B on the coset
@@ -2414,6 +2421,20 @@ extern "C" int zk_witness_map(zk_ctx *c, const uint64_t *witness, int canonical,
     ZK_HIP(hipStreamSynchronize(c->s_main));
     ZK_HIP(hipMemcpy(h_out, c->d_t, 32 * (size_t)c->m, hipMemcpyDeviceToHost));
     memset(h_out + 4 * (size_t)c->m, 0, 32);
+    return ZK_OK;
+} ZK_GUARD
+
+// TEST INFRASTRUCTURE: the row evaluations of a batch as the kernels left them (include/zkhip.h)
+extern "C" int zk_ctx_probe_rows(zk_ctx *c, const uint64_t *witnesses, uint32_t k, int canonical, uint64_t *out) try {
+    if (!c || !witnesses || !out) return fail(ZK_ERR_ARG, "null argument");
+    if (c->in_flight) return fail(ZK_ERR_ARG, "a proof is in flight on this context (collect it first): its witness and row buffers are in use");
+    if (!k || k > c->max_batch) return fail(ZK_ERR_ARG, "batch size exceeds zk_config.max_batch of this context");
+    ZK_TRY(use_device(c->device));
+    c->cur_batch = k;
+    ZK_TRY(upload_witness(c, witnesses, canonical));
+    ZK_TRY(enqueue_rows(c, c->s_main));
+    ZK_HIP(hipStreamSynchronize(c->s_main));
+    ZK_HIP(hipMemcpy(out, c->d_a, 3 * 32 * (size_t)c->m * k, hipMemcpyDeviceToHost));
     return ZK_OK;
 } ZK_GUARD
 

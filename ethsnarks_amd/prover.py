@@ -68,7 +68,7 @@ EXPORTS = [
     "zk_wplan_create", "zk_wplan_create_hinted", "zk_wplan_create_wide", "zk_wplan_info", "zk_wplan_solve", "zk_wplan_free", "zk_wplan_probe_program", "zk_dev_alloc", "zk_dev_free", "zk_dev_upload", "zk_dev_download",
     "zk_chain_submit", "zk_chain_device", "zk_h_from_chains_submit", "zk_h_device", "zk_chain_wait", "zk_prove_submit_with_h", "zk_prove_submit_defer_h", "zk_prove_submit_h", "zk_prove_abort",
     "zk_prove_submit_pinned", "zk_prove_batch_submit_pinned", "zk_host_alloc", "zk_host_free", "zk_host_register", "zk_host_unregister",
-    "zk_prove_submit_resident", "zk_prove_stage", "zk_prove_stage_pinned", "zk_prove_submit_staged", "zk_ctx_info", "zk_ctx_table_info", "zk_ctx_hlagrange_info", "zk_hl_probe_dft", "zk_hl_probe_columns", "zk_ctx_partials_device", "zk_prove_collect_device", "zk_prove_combine_device", "zk_launch_count", "zk_profile_begin", "zk_profile_end", "zk_device_info", "zk_device_pci_bus_id",
+    "zk_prove_submit_resident", "zk_prove_stage", "zk_prove_stage_pinned", "zk_prove_submit_staged", "zk_ctx_info", "zk_ctx_table_info", "zk_ctx_hlagrange_info", "zk_hl_probe_dft", "zk_hl_probe_columns", "zk_ctx_probe_rows", "zk_ctx_partials_device", "zk_prove_collect_device", "zk_prove_combine_device", "zk_launch_count", "zk_profile_begin", "zk_profile_end", "zk_device_info", "zk_device_pci_bus_id",
     "zk_verify",
     "zk_vctx_create", "zk_vctx_destroy", "zk_verify_batch", "zk_verify_batch_json", "zk_pairing_check", "zk_pairing_tower_op",
     "zk_mtree_create", "zk_mtree_free", "zk_mtree_size", "zk_mtree_append", "zk_mtree_append_resident", "zk_mtree_update", "zk_mtree_root", "zk_mtree_node",
@@ -594,6 +594,14 @@ class ProverContext:
         h = np.zeros((m + 1, 4), dtype=np.uint64)
         _check(_lib.zk_witness_map(self._h, _p64(w), int(canonical), _p64(h)))
         return h
+
+    def probe_rows(self, witnesses, canonical=False):
+        """zk_ctx_probe_rows (test infrastructure): the row evaluations of k witnesses as the row kernels leave them, (3, k, m, 4) raw
+        Montgomery limbs: [A, B, C][proof][row of the domain, padding and input rows included]"""
+        w, k = self._wk(witnesses)
+        out = np.zeros((3, k, self.r1cs.domain_size, 4), dtype=np.uint64)
+        _check(_lib.zk_ctx_probe_rows(self._h, _p64(w), C.c_uint32(k), int(canonical), _p64(out)))
+        return out
 
     def close(self):
         if getattr(self, "_h", None) is not None and _lib is not None:

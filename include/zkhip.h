@@ -306,6 +306,12 @@ int zk_ctx_hlagrange_info(const zk_ctx *ctx, uint64_t info[4]);
  * zk_hl_probe_columns: out[v] = L_v - sum_j C[j][v] lambda[j], v <= V; L_v = l_bases[v - nIn - 1], the point at infinity for v <= nIn */
 int zk_hl_probe_dft(const uint64_t *points, uint32_t n, uint32_t logm, int coset, int device, uint64_t *out);
 int zk_hl_probe_columns(const zk_csr *C, uint32_t nIn, uint32_t V, const uint64_t *lambda, uint32_t m, const uint64_t *l_bases, int device, uint64_t *out);
+/* row probe: TEST INFRASTRUCTURE.  Uploads the k witnesses (contiguous, V + 1 elements each) as a batch submit does, runs the R1CS row
+ * evaluation that every H pipeline starts with -- the same helper, the same arguments -- and copies back what the row kernels left:
+ * out = [A: k x m][B: k x m][C: k x m], m = the domain size, 4 x u64 per element, RAW Montgomery limbs (no canon), rows nC .. m - 1 (A's
+ * input-consistency rows and the padding) included.  ZK_ERR_ARG: a proof is in flight, k = 0, k > zk_config.max_batch.  (A new function
+ * WITHOUT an ABI bump: detected by its symbol.) */
+int zk_ctx_probe_rows(zk_ctx *ctx, const uint64_t *witnesses, uint32_t k, int canonical, uint64_t *out /* 3 x k x m x 4 */);
 
 /* inputs: nIn Fr elements = witness[1..nIn] (Montgomery unless canonical); returns the JSON length
  * (excluding NUL) through *len; ZK_ERR_BUFFER if cap is too small (len still set) */
