@@ -444,169 +444,25 @@ extern "C" int zk_eddsa_verify_batch(zk_eddsa *v, const uint64_t *A, const uint6
     return ZK_OK;
 } ZK_GUARD
 
+// ---- the witness fills
 namespace {
-// every segment of the layout inside variables 1 .. n_vars, n_vars + 1 <= row_elems, no two segments overlapping.  The three blocks of a step
-// of the variable-base multiplication must lie, disjoint, within one stride of the lowest of them
-bool layout_fits(const FillLayout &L, uint32_t msg_len, uint64_t row_elems) {
-    if (L.msg_len != msg_len || (uint64_t)L.n_vars + 1 > row_elems) return false;
-    uint32_t range_vars = 0;
-    for (uint32_t i = 1; i + 1 < FIELD_BITS; i++) range_vars += modulus_m1_bit(i);
-    if (range_vars != T_RANGE_VARS) return false;
-    const uint64_t step0 = std::min(L.doubler_var0, std::min(L.cond_var0, L.adder_var0));
-    struct Seg { uint64_t at, len; };
-    const Seg step[3] = {{L.doubler_var0, DBL_VARS}, {L.cond_var0, 2}, {L.adder_var0, ADD_VARS}};
+struct Seg { uint64_t at, len; };
+// every segment of a row inside variables 1 .. n_vars, n_vars + 1 <= row_elems, no two segments overlapping.  own: the segments that only this
+// circuit has; the chain's segments are added here.  The three blocks of a step of the variable-base multiplication must lie, disjoint, within
+// one stride of the lowest of them.  A segment without elements (no padding bits, no Edwards adder of the message hash) is not there: its
+// offset is not looked at
+bool row_fits(std::vector<Seg> segs, const ChainLayout &C, uint32_t n_vars, uint64_t row_elems) {
+    if ((uint64_t)n_vars + 1 > row_elems) return false;
+    const uint64_t step0 = std::min(C.doubler_var0, std::min(C.cond_var0, C.adder_var0));
+    const Seg step[3] = {{C.doubler_var0, DBL_VARS}, {C.cond_var0, 2}, {C.adder_var0, ADD_VARS}};
     for (int i = 0; i < 3; i++) {
-        if (step[i].at + step[i].len > step0 + L.step_stride) return false;
+        if (step[i].at + step[i].len > step0 + C.step_stride) return false;
         for (int j = 0; j < i; j++) if (step[i].at < step[j].at + step[j].len && step[j].at < step[i].at + step[i].len) return false;
     }
-    std::vector<Seg> segs = {{L.ax_var, 2}, {L.msg_var0, msg_len}, {L.rx_var, 2}, {L.s_bit0, FIELD_BITS}, {L.iv_var, 1}, {L.validator_var0, VALIDATOR_VARS},
-                             {L.window_var0, 2 * FB_WINDOWS}, {L.fixed_adder_var0, ADD_VARS * (FB_WINDOWS - 1)},
-                             {L.mimc_var0, (uint64_t)(4 + msg_len) * (1 + MIMC_ROUND_VARS)}, {L.t_bit0, T_BITS_VARS}, {L.t_range_var0, T_RANGE_VARS},
-                             {L.cond0_var, 2}, {step0, (uint64_t)N_STEPS * L.step_stride}, {L.last_adder_var0, ADD_VARS}};
-    std::sort(segs.begin(), segs.end(), [](const Seg &a, const Seg &b) { return a.at < b.at; });
-    uint64_t end = 1;                                           // variable 0 is ONE
-    for (const Seg &g : segs) {
-        if (g.at < end) return false;
-        end = g.at + g.len;
-    }
-    return end <= (uint64_t)L.n_vars + 1;
-}
-}  // namespace
-
-extern "C" int zk_eddsa_fill_witnesses(zk_eddsa *v, const uint64_t *A, const uint64_t *R, const uint64_t *s, const uint64_t *msgs, uint32_t n, void *d_w,
-                                       uint64_t row_elems, const zk_eddsa_layout *layout, uint8_t *verdicts) try {
-    if (!v || !A || !R || !s || !msgs || !d_w || !layout || !verdicts) return jfail(ZK_ERR_ARG, "null argument");
-    if (v->scheme != SCHEME_MIMC) return jfail(ZK_ERR_ARG, "only a ZK_EDDSA_MIMC verifier has a circuit to fill witnesses of");
-    FillLayout L;
-    memcpy(&L, layout, sizeof(L));
-    if (!layout_fits(L, v->msg_len, row_elems)) return jfail(ZK_ERR_ARG, "the layout does not fit the verifier's msg_len, overlaps itself or leaves the row");
-    if (n == 0) return ZK_OK;
-    if (!all_below_modulus(A, 2 * (uint64_t)n) || !all_below_modulus(R, 2 * (uint64_t)n)) return jfail(ZK_ERR_ARG, "a coordinate is not below the Fr modulus");
-    if (!all_below_modulus(msgs, (uint64_t)n * v->msg_len)) return jfail(ZK_ERR_ARG, "a message element is not below the Fr modulus");
-    ZK_TRY(jj_use_device(v->device));
-    const size_t pb = 2 * sizeof(fe) * (size_t)n, sb = sizeof(fe) * (size_t)n, mb = sb * v->msg_len;
-    ZK_TRY(v->scratch.ensure(2 * pb + sb + mb + align32(n)));
-    char *d = (char *)v->scratch.p;
-    char *dA = d, *dR = d + pb, *dS = d + 2 * pb, *dM = dS + sb, *dV = dM + mb;
-    ZK_HIP(hipMemcpyAsync(dA, A, pb, hipMemcpyHostToDevice, v->st));
-    ZK_HIP(hipMemcpyAsync(dR, R, pb, hipMemcpyHostToDevice, v->st));
-    ZK_HIP(hipMemcpyAsync(dS, s, sb, hipMemcpyHostToDevice, v->st));
-    ZK_HIP(hipMemcpyAsync(dM, msgs, mb, hipMemcpyHostToDevice, v->st));
-    ZK_LAUNCH(k_eddsa_fill, zk_div_up(n, BLOCK), BLOCK, v->st, v->view, v->fbtab, L, (const fe *)dA, (const fe *)dR, (const fe *)dS, (const fe *)dM, n, (fe *)d_w,
-              row_elems, (uint8_t *)dV);
-    ZK_HIP(hipGetLastError());
-    ZK_HIP(hipMemcpyAsync(verdicts, dV, n, hipMemcpyDeviceToHost, v->st));
-    ZK_HIP(hipStreamSynchronize(v->st));
-    return ZK_OK;
-} ZK_GUARD
-
-// zk_eddsa_fill_witnesses with `lanes` lanes per witness: 1 is that call itself (k_eddsa_fill), 2 and 4 launch k_eddsa_fill_wide over workgroups of
-// 64 x lanes threads.  lanes is checked first, then that call's checks in its order; the same rows byte for byte
-extern "C" int zk_eddsa_fill_witnesses_wide(zk_eddsa *v, const uint64_t *A, const uint64_t *R, const uint64_t *s, const uint64_t *msgs, uint32_t n, void *d_w,
-                                            uint64_t row_elems, const zk_eddsa_layout *layout, uint8_t *verdicts, uint32_t lanes) try {
-    if (lanes != 1 && lanes != 2 && lanes != 4) return jfail(ZK_ERR_ARG, "lanes per witness: 1, 2 or 4");
-    if (lanes == 1) return zk_eddsa_fill_witnesses(v, A, R, s, msgs, n, d_w, row_elems, layout, verdicts);
-    if (!v || !A || !R || !s || !msgs || !d_w || !layout || !verdicts) return jfail(ZK_ERR_ARG, "null argument");
-    if (v->scheme != SCHEME_MIMC) return jfail(ZK_ERR_ARG, "only a ZK_EDDSA_MIMC verifier has a circuit to fill witnesses of");
-    FillLayout L;
-    memcpy(&L, layout, sizeof(L));
-    if (!layout_fits(L, v->msg_len, row_elems)) return jfail(ZK_ERR_ARG, "the layout does not fit the verifier's msg_len, overlaps itself or leaves the row");
-    if (n == 0) return ZK_OK;
-    if (!all_below_modulus(A, 2 * (uint64_t)n) || !all_below_modulus(R, 2 * (uint64_t)n)) return jfail(ZK_ERR_ARG, "a coordinate is not below the Fr modulus");
-    if (!all_below_modulus(msgs, (uint64_t)n * v->msg_len)) return jfail(ZK_ERR_ARG, "a message element is not below the Fr modulus");
-    ZK_TRY(jj_use_device(v->device));
-    const size_t pb = 2 * sizeof(fe) * (size_t)n, sb = sizeof(fe) * (size_t)n, mb = sb * v->msg_len;
-    ZK_TRY(v->scratch.ensure(2 * pb + sb + mb + align32(n)));
-    char *d = (char *)v->scratch.p;
-    char *dA = d, *dR = d + pb, *dS = d + 2 * pb, *dM = dS + sb, *dV = dM + mb;
-    ZK_HIP(hipMemcpyAsync(dA, A, pb, hipMemcpyHostToDevice, v->st));
-    ZK_HIP(hipMemcpyAsync(dR, R, pb, hipMemcpyHostToDevice, v->st));
-    ZK_HIP(hipMemcpyAsync(dS, s, sb, hipMemcpyHostToDevice, v->st));
-    ZK_HIP(hipMemcpyAsync(dM, msgs, mb, hipMemcpyHostToDevice, v->st));
-    if (lanes == 2) ZK_LAUNCH_SYNC((k_eddsa_fill_wide<2>), zk_div_up(n, BLOCK), BLOCK * 2, v->st, v->view, v->fbtab, L, (const fe *)dA, (const fe *)dR, (const fe *)dS,
-                                   (const fe *)dM, n, (fe *)d_w, row_elems, (uint8_t *)dV);
-    else ZK_LAUNCH_SYNC((k_eddsa_fill_wide<4>), zk_div_up(n, BLOCK), BLOCK * 4, v->st, v->view, v->fbtab, L, (const fe *)dA, (const fe *)dR, (const fe *)dS,
-                        (const fe *)dM, n, (fe *)d_w, row_elems, (uint8_t *)dV);
-    ZK_HIP(hipGetLastError());
-    ZK_HIP(hipMemcpyAsync(verdicts, dV, n, hipMemcpyDeviceToHost, v->st));
-    ZK_HIP(hipStreamSynchronize(v->st));
-    return ZK_OK;
-} ZK_GUARD
-
-namespace {
-// the PureEdDSA row: as layout_fits, with the hash's segments sized by the window count of the verifier's msg_len
-bool pure_layout_fits(const PureLayout &L, uint32_t msg_len, uint64_t row_elems) {
-    if (L.msg_len != msg_len || (uint64_t)L.n_vars + 1 > row_elems) return false;
-    const uint64_t W = pure_windows(msg_len), S = (W + SEG_WINDOWS - 1) / SEG_WINDOWS;
-    const uint64_t step0 = std::min(L.doubler_var0, std::min(L.cond_var0, L.adder_var0));
-    struct Seg { uint64_t at, len; };
-    const Seg step[3] = {{L.doubler_var0, DBL_VARS}, {L.cond_var0, 2}, {L.adder_var0, ADD_VARS}};
-    for (int i = 0; i < 3; i++) {
-        if (step[i].at + step[i].len > step0 + L.step_stride) return false;
-        for (int j = 0; j < i; j++) if (step[i].at < step[j].at + step[j].len && step[j].at < step[i].at + step[i].len) return false;
-    }
-    std::vector<Seg> segs = {{L.ax_var, 2}, {L.msg_bit0, 8 * (uint64_t)msg_len}, {L.rx_var, 2}, {L.s_bit0, FIELD_BITS}, {L.pad_bit0, 3 * W - 2 * FIELD_BITS - 8 * (uint64_t)msg_len},
-                             {L.validator_var0, VALIDATOR_VARS}, {L.window_var0, 2 * FB_WINDOWS}, {L.fixed_adder_var0, ADD_VARS * (FB_WINDOWS - 1)},
-                             {L.rx_bit0, T_BITS_VARS}, {L.rx_range_var0, T_RANGE_VARS}, {L.ax_bit0, T_BITS_VARS}, {L.ax_range_var0, T_RANGE_VARS},
-                             {L.hash_window_var0, 2 * W}, {L.mont_adder_var0, MADD_VARS * (W - S)}, {L.converter_var0, 2 * S}, {L.edwards_adder_var0, ADD_VARS * (S - 1)},
-                             {L.t_bit0, T_BITS_VARS}, {L.t_range_var0, T_RANGE_VARS}, {L.cond0_var, 2}, {step0, (uint64_t)N_STEPS * L.step_stride}, {L.last_adder_var0, ADD_VARS}};
-    std::sort(segs.begin(), segs.end(), [](const Seg &a, const Seg &b) { return a.at < b.at; });
-    uint64_t end = 1;                                           // variable 0 is ONE
-    for (const Seg &g : segs) {
-        if (g.len == 0) continue;                               // (no padding bits at this msg_len)
-        if (g.at < end) return false;
-        end = g.at + g.len;
-    }
-    return end <= (uint64_t)L.n_vars + 1;
-}
-}  // namespace
-
-extern "C" int zk_eddsa_fill_pure_witnesses(zk_eddsa *v, const uint64_t *A, const uint64_t *R, const uint64_t *s, const uint8_t *msgs, uint32_t n, void *d_w,
-                                            uint64_t row_elems, const zk_eddsa_pure_layout *layout, uint8_t *verdicts) try {
-    if (!v || !A || !R || !s || !msgs || !d_w || !layout || !verdicts) return jfail(ZK_ERR_ARG, "null argument");
-    if (v->scheme != SCHEME_PURE) return jfail(ZK_ERR_ARG, "only a ZK_EDDSA_PURE verifier has a PureEdDSA circuit to fill witnesses of");
-    PureLayout L;
-    memcpy(&L, layout, sizeof(L));
-    if (!pure_layout_fits(L, v->msg_len, row_elems)) return jfail(ZK_ERR_ARG, "the layout does not fit the verifier's msg_len, overlaps itself or leaves the row");
-    if (n == 0) return ZK_OK;
-    if (!all_below_modulus(A, 2 * (uint64_t)n) || !all_below_modulus(R, 2 * (uint64_t)n)) return jfail(ZK_ERR_ARG, "a coordinate is not below the Fr modulus");
-    ZK_TRY(jj_use_device(v->device));
-    const size_t pb = 2 * sizeof(fe) * (size_t)n, sb = sizeof(fe) * (size_t)n, mb = (size_t)n * v->msg_len, mb_al = align32(mb);
-    ZK_TRY(v->scratch.ensure(2 * pb + sb + mb_al + align32(n)));
-    char *d = (char *)v->scratch.p;
-    char *dA = d, *dR = d + pb, *dS = d + 2 * pb, *dM = dS + sb, *dV = dM + mb_al;
-    ZK_HIP(hipMemcpyAsync(dA, A, pb, hipMemcpyHostToDevice, v->st));
-    ZK_HIP(hipMemcpyAsync(dR, R, pb, hipMemcpyHostToDevice, v->st));
-    ZK_HIP(hipMemcpyAsync(dS, s, sb, hipMemcpyHostToDevice, v->st));
-    ZK_HIP(hipMemcpyAsync(dM, msgs, mb, hipMemcpyHostToDevice, v->st));
-    ZK_LAUNCH(k_eddsa_fill_pure, zk_div_up(n, BLOCK), BLOCK, v->st, v->view, v->fbtab, v->mtab, L, (const fe *)dA, (const fe *)dR, (const fe *)dS, (const uint8_t *)dM, n,
-              (fe *)d_w, row_elems, (uint8_t *)dV);
-    ZK_HIP(hipGetLastError());
-    ZK_HIP(hipMemcpyAsync(verdicts, dV, n, hipMemcpyDeviceToHost, v->st));
-    ZK_HIP(hipStreamSynchronize(v->st));
-    return ZK_OK;
-} ZK_GUARD
-
-namespace {
-// the EdDSA (hash scheme) row: as pure_layout_fits, the RAM hash over 3 x 254 bits and the message hash sized by the verifier's msg_len.  A segment
-// without elements (no padding bits, no Edwards adder of the message hash) is not there: its offset is not looked at
-bool hash_layout_fits(const HashLayout &L, uint32_t msg_len, uint64_t row_elems) {
-    if (L.msg_len != msg_len || (uint64_t)L.n_vars + 1 > row_elems) return false;
-    const uint64_t W = HASH_RAM_WINDOWS, S = (W + SEG_WINDOWS - 1) / SEG_WINDOWS, Wm = hash_msg_windows(msg_len), Sm = (Wm + SEG_WINDOWS - 1) / SEG_WINDOWS;
-    const uint64_t step0 = std::min(L.doubler_var0, std::min(L.cond_var0, L.adder_var0));
-    struct Seg { uint64_t at, len; };
-    const Seg step[3] = {{L.doubler_var0, DBL_VARS}, {L.cond_var0, 2}, {L.adder_var0, ADD_VARS}};
-    for (int i = 0; i < 3; i++) {
-        if (step[i].at + step[i].len > step0 + L.step_stride) return false;
-        for (int j = 0; j < i; j++) if (step[i].at < step[j].at + step[j].len && step[j].at < step[i].at + step[i].len) return false;
-    }
-    std::vector<Seg> segs = {{L.ax_var, 2}, {L.msg_bit0, 8 * (uint64_t)msg_len}, {L.rx_var, 2}, {L.s_bit0, FIELD_BITS},
-                             {L.m_pad_bit0, 3 * Wm - 8 * (uint64_t)msg_len}, {L.m_window_var0, 2 * Wm}, {L.m_mont_adder_var0, MADD_VARS * (Wm - Sm)},
-                             {L.m_converter_var0, 2 * Sm}, {L.m_edwards_adder_var0, ADD_VARS * (Sm - 1)}, {L.m_bit0, T_BITS_VARS}, {L.m_range_var0, T_RANGE_VARS},
-                             {L.validator_var0, VALIDATOR_VARS}, {L.window_var0, 2 * FB_WINDOWS}, {L.fixed_adder_var0, ADD_VARS * (FB_WINDOWS - 1)},
-                             {L.rx_bit0, T_BITS_VARS}, {L.rx_range_var0, T_RANGE_VARS}, {L.ax_bit0, T_BITS_VARS}, {L.ax_range_var0, T_RANGE_VARS},
-                             {L.hash_window_var0, 2 * W}, {L.mont_adder_var0, MADD_VARS * (W - S)}, {L.converter_var0, 2 * S}, {L.edwards_adder_var0, ADD_VARS * (S - 1)},
-                             {L.t_bit0, T_BITS_VARS}, {L.t_range_var0, T_RANGE_VARS}, {L.cond0_var, 2}, {step0, (uint64_t)N_STEPS * L.step_stride}, {L.last_adder_var0, ADD_VARS}};
+    const Seg chain[] = {{C.ax_var, 2}, {C.rx_var, 2}, {C.s_bit0, FIELD_BITS}, {C.validator_var0, VALIDATOR_VARS}, {C.window_var0, 2 * FB_WINDOWS},
+                         {C.fixed_adder_var0, ADD_VARS * (FB_WINDOWS - 1)}, {C.cond0_var, 2}, {step0, (uint64_t)N_STEPS * C.step_stride},
+                         {C.last_adder_var0, ADD_VARS}};
+    segs.insert(segs.end(), std::begin(chain), std::end(chain));
     std::sort(segs.begin(), segs.end(), [](const Seg &a, const Seg &b) { return a.at < b.at; });
     uint64_t end = 1;                                           // variable 0 is ONE
     for (const Seg &g : segs) {
@@ -614,8 +470,88 @@ bool hash_layout_fits(const HashLayout &L, uint32_t msg_len, uint64_t row_elems)
         if (g.at < end) return false;
         end = g.at + g.len;
     }
-    return end <= (uint64_t)L.n_vars + 1;
+    return end <= (uint64_t)n_vars + 1;
 }
+// the segments of one in-circuit Pedersen hash of W windows: its windows, Montgomery adders, converters and Edwards adders
+void hash_segs(std::vector<Seg> &segs, uint64_t W, uint32_t window_var0, uint32_t mont_adder_var0, uint32_t converter_var0, uint32_t edwards_adder_var0) {
+    const uint64_t S = (W + SEG_WINDOWS - 1) / SEG_WINDOWS;
+    segs.insert(segs.end(), {{window_var0, 2 * W}, {mont_adder_var0, MADD_VARS * (W - S)}, {converter_var0, 2 * S}, {edwards_adder_var0, ADD_VARS * (S - 1)}});
+}
+// the MiMC-EdDSA row
+bool layout_fits(const FillLayout &L, uint32_t msg_len, uint64_t row_elems) {
+    if (L.msg_len != msg_len) return false;
+    uint32_t range_vars = 0;
+    for (uint32_t i = 1; i + 1 < FIELD_BITS; i++) range_vars += modulus_m1_bit(i);
+    if (range_vars != T_RANGE_VARS) return false;
+    return row_fits({{L.msg_var0, msg_len}, {L.iv_var, 1}, {L.mimc_var0, (uint64_t)(4 + msg_len) * (1 + MIMC_ROUND_VARS)}, {L.t_bit0, T_BITS_VARS},
+                     {L.t_range_var0, T_RANGE_VARS}}, chain_layout(L), L.n_vars, row_elems);
+}
+// the PureEdDSA row: the hash's segments sized by the window count of the verifier's msg_len
+bool pure_layout_fits(const PureLayout &L, uint32_t msg_len, uint64_t row_elems) {
+    if (L.msg_len != msg_len) return false;
+    const uint64_t W = pure_windows(msg_len);
+    std::vector<Seg> segs = {{L.msg_bit0, 8 * (uint64_t)msg_len}, {L.pad_bit0, 3 * W - 2 * FIELD_BITS - 8 * (uint64_t)msg_len}, {L.rx_bit0, T_BITS_VARS},
+                             {L.rx_range_var0, T_RANGE_VARS}, {L.ax_bit0, T_BITS_VARS}, {L.ax_range_var0, T_RANGE_VARS}, {L.t_bit0, T_BITS_VARS},
+                             {L.t_range_var0, T_RANGE_VARS}};
+    hash_segs(segs, W, L.hash_window_var0, L.mont_adder_var0, L.converter_var0, L.edwards_adder_var0);
+    return row_fits(segs, chain_layout(L), L.n_vars, row_elems);
+}
+// the EdDSA (hash scheme) row: the RAM hash over 3 x 254 bits and the message hash sized by the verifier's msg_len
+bool hash_layout_fits(const HashLayout &L, uint32_t msg_len, uint64_t row_elems) {
+    if (L.msg_len != msg_len) return false;
+    const uint64_t Wm = hash_msg_windows(msg_len);
+    std::vector<Seg> segs = {{L.msg_bit0, 8 * (uint64_t)msg_len}, {L.m_pad_bit0, 3 * Wm - 8 * (uint64_t)msg_len}, {L.m_bit0, T_BITS_VARS},
+                             {L.m_range_var0, T_RANGE_VARS}, {L.rx_bit0, T_BITS_VARS}, {L.rx_range_var0, T_RANGE_VARS}, {L.ax_bit0, T_BITS_VARS},
+                             {L.ax_range_var0, T_RANGE_VARS}, {L.t_bit0, T_BITS_VARS}, {L.t_range_var0, T_RANGE_VARS}};
+    hash_segs(segs, Wm, L.m_window_var0, L.m_mont_adder_var0, L.m_converter_var0, L.m_edwards_adder_var0);
+    hash_segs(segs, HASH_RAM_WINDOWS, L.hash_window_var0, L.mont_adder_var0, L.converter_var0, L.edwards_adder_var0);
+    return row_fits(segs, chain_layout(L), L.n_vars, row_elems);
+}
+
+// a batch on the device: what a fill kernel reads and where its verdicts go
+struct Staged { const fe *A, *R, *s; const void *msgs; uint8_t *verdicts; };
+// what every fill does once its arguments are checked: A, R, s and the messages (msg_stride bytes an item) go to the handle's scratch, `launch`
+// starts the kernel over them, the verdicts come back
+template <class Launch>
+int stage_and_fill(zk_eddsa *v, const uint64_t *A, const uint64_t *R, const uint64_t *s, const void *msgs, size_t msg_stride, uint32_t n, uint8_t *verdicts,
+                   Launch launch) {
+    const size_t pb = 2 * sizeof(fe) * (size_t)n, sb = sizeof(fe) * (size_t)n, mb = (size_t)n * msg_stride, mb_al = align32(mb);
+    ZK_TRY(v->scratch.ensure(2 * pb + sb + mb_al + align32(n)));
+    char *d = (char *)v->scratch.p;
+    char *dA = d, *dR = d + pb, *dS = d + 2 * pb, *dM = dS + sb, *dV = dM + mb_al;
+    ZK_HIP(hipMemcpyAsync(dA, A, pb, hipMemcpyHostToDevice, v->st));
+    ZK_HIP(hipMemcpyAsync(dR, R, pb, hipMemcpyHostToDevice, v->st));
+    ZK_HIP(hipMemcpyAsync(dS, s, sb, hipMemcpyHostToDevice, v->st));
+    ZK_HIP(hipMemcpyAsync(dM, msgs, mb, hipMemcpyHostToDevice, v->st));
+    launch(Staged{(const fe *)dA, (const fe *)dR, (const fe *)dS, (const void *)dM, (uint8_t *)dV});
+    ZK_HIP(hipGetLastError());
+    ZK_HIP(hipMemcpyAsync(verdicts, dV, n, hipMemcpyDeviceToHost, v->st));
+    ZK_HIP(hipStreamSynchronize(v->st));
+    return ZK_OK;
+}
+
+// zk_eddsa_fill_witnesses and zk_eddsa_fill_witnesses_wide behind the check of `lanes`: 1 launches k_eddsa_fill, 2 and 4 k_eddsa_fill_wide over
+// workgroups of 64 x lanes threads
+int fill_mimc(zk_eddsa *v, const uint64_t *A, const uint64_t *R, const uint64_t *s, const uint64_t *msgs, uint32_t n, void *d_w, uint64_t row_elems,
+              const zk_eddsa_layout *layout, uint8_t *verdicts, uint32_t lanes) {
+    if (!v || !A || !R || !s || !msgs || !d_w || !layout || !verdicts) return jfail(ZK_ERR_ARG, "null argument");
+    if (v->scheme != SCHEME_MIMC) return jfail(ZK_ERR_ARG, "only a ZK_EDDSA_MIMC verifier has a circuit to fill witnesses of");
+    FillLayout L;
+    memcpy(&L, layout, sizeof(L));
+    if (!layout_fits(L, v->msg_len, row_elems)) return jfail(ZK_ERR_ARG, "the layout does not fit the verifier's msg_len, overlaps itself or leaves the row");
+    if (n == 0) return ZK_OK;
+    if (!all_below_modulus(A, 2 * (uint64_t)n) || !all_below_modulus(R, 2 * (uint64_t)n)) return jfail(ZK_ERR_ARG, "a coordinate is not below the Fr modulus");
+    if (!all_below_modulus(msgs, (uint64_t)n * v->msg_len)) return jfail(ZK_ERR_ARG, "a message element is not below the Fr modulus");
+    ZK_TRY(jj_use_device(v->device));
+    return stage_and_fill(v, A, R, s, msgs, sizeof(fe) * v->msg_len, n, verdicts, [&](const Staged &d) {
+        if (lanes == 1) ZK_LAUNCH(k_eddsa_fill, zk_div_up(n, BLOCK), BLOCK, v->st, v->view, v->fbtab, L, d.A, d.R, d.s, (const fe *)d.msgs, n, (fe *)d_w, row_elems, d.verdicts);
+        else if (lanes == 2) ZK_LAUNCH_SYNC((k_eddsa_fill_wide<2>), zk_div_up(n, BLOCK), BLOCK * 2, v->st, v->view, v->fbtab, L, d.A, d.R, d.s, (const fe *)d.msgs, n,
+                                            (fe *)d_w, row_elems, d.verdicts);
+        else ZK_LAUNCH_SYNC((k_eddsa_fill_wide<4>), zk_div_up(n, BLOCK), BLOCK * 4, v->st, v->view, v->fbtab, L, d.A, d.R, d.s, (const fe *)d.msgs, n, (fe *)d_w,
+                            row_elems, d.verdicts);
+    });
+}
+
 // what the fill of a ZK_EDDSA_HASH handle reads beyond the verifier's tables: the circuit's fixed-base windows and the Montgomery form of the two
 // Pedersen tables (read back from the device: the handle keeps no host copy).  Built once, freed with the handle
 int build_hash_fill_tables(zk_eddsa *v) {
@@ -638,6 +574,34 @@ int build_hash_fill_tables(zk_eddsa *v) {
 }
 }  // namespace
 
+extern "C" int zk_eddsa_fill_witnesses(zk_eddsa *v, const uint64_t *A, const uint64_t *R, const uint64_t *s, const uint64_t *msgs, uint32_t n, void *d_w,
+                                       uint64_t row_elems, const zk_eddsa_layout *layout, uint8_t *verdicts) try {
+    return fill_mimc(v, A, R, s, msgs, n, d_w, row_elems, layout, verdicts, 1);
+} ZK_GUARD
+
+// zk_eddsa_fill_witnesses with `lanes` lanes per witness.  lanes is checked first, then that call's checks in its order; the same rows byte for byte
+extern "C" int zk_eddsa_fill_witnesses_wide(zk_eddsa *v, const uint64_t *A, const uint64_t *R, const uint64_t *s, const uint64_t *msgs, uint32_t n, void *d_w,
+                                            uint64_t row_elems, const zk_eddsa_layout *layout, uint8_t *verdicts, uint32_t lanes) try {
+    if (lanes != 1 && lanes != 2 && lanes != 4) return jfail(ZK_ERR_ARG, "lanes per witness: 1, 2 or 4");
+    return fill_mimc(v, A, R, s, msgs, n, d_w, row_elems, layout, verdicts, lanes);
+} ZK_GUARD
+
+extern "C" int zk_eddsa_fill_pure_witnesses(zk_eddsa *v, const uint64_t *A, const uint64_t *R, const uint64_t *s, const uint8_t *msgs, uint32_t n, void *d_w,
+                                            uint64_t row_elems, const zk_eddsa_pure_layout *layout, uint8_t *verdicts) try {
+    if (!v || !A || !R || !s || !msgs || !d_w || !layout || !verdicts) return jfail(ZK_ERR_ARG, "null argument");
+    if (v->scheme != SCHEME_PURE) return jfail(ZK_ERR_ARG, "only a ZK_EDDSA_PURE verifier has a PureEdDSA circuit to fill witnesses of");
+    PureLayout L;
+    memcpy(&L, layout, sizeof(L));
+    if (!pure_layout_fits(L, v->msg_len, row_elems)) return jfail(ZK_ERR_ARG, "the layout does not fit the verifier's msg_len, overlaps itself or leaves the row");
+    if (n == 0) return ZK_OK;
+    if (!all_below_modulus(A, 2 * (uint64_t)n) || !all_below_modulus(R, 2 * (uint64_t)n)) return jfail(ZK_ERR_ARG, "a coordinate is not below the Fr modulus");
+    ZK_TRY(jj_use_device(v->device));
+    return stage_and_fill(v, A, R, s, msgs, v->msg_len, n, verdicts, [&](const Staged &d) {
+        ZK_LAUNCH(k_eddsa_fill_pure, zk_div_up(n, BLOCK), BLOCK, v->st, v->view, v->fbtab, v->mtab, L, d.A, d.R, d.s, (const uint8_t *)d.msgs, n, (fe *)d_w, row_elems,
+                  d.verdicts);
+    });
+} ZK_GUARD
+
 extern "C" int zk_eddsa_fill_hash_witnesses(zk_eddsa *v, const uint64_t *A, const uint64_t *R, const uint64_t *s, const uint8_t *msgs, uint32_t n, void *d_w,
                                             uint64_t row_elems, const zk_eddsa_hash_layout *layout, uint8_t *verdicts) try {
     if (!v || !layout) return jfail(ZK_ERR_ARG, "null argument");
@@ -650,20 +614,10 @@ extern "C" int zk_eddsa_fill_hash_witnesses(zk_eddsa *v, const uint64_t *A, cons
     if (!all_below_modulus(A, 2 * (uint64_t)n) || !all_below_modulus(R, 2 * (uint64_t)n)) return jfail(ZK_ERR_ARG, "a coordinate is not below the Fr modulus");
     ZK_TRY(jj_use_device(v->device));
     ZK_TRY(build_hash_fill_tables(v));
-    const size_t pb = 2 * sizeof(fe) * (size_t)n, sb = sizeof(fe) * (size_t)n, mb = (size_t)n * v->msg_len, mb_al = align32(mb);
-    ZK_TRY(v->scratch.ensure(2 * pb + sb + mb_al + align32(n)));
-    char *d = (char *)v->scratch.p;
-    char *dA = d, *dR = d + pb, *dS = d + 2 * pb, *dM = dS + sb, *dV = dM + mb_al;
-    ZK_HIP(hipMemcpyAsync(dA, A, pb, hipMemcpyHostToDevice, v->st));
-    ZK_HIP(hipMemcpyAsync(dR, R, pb, hipMemcpyHostToDevice, v->st));
-    ZK_HIP(hipMemcpyAsync(dS, s, sb, hipMemcpyHostToDevice, v->st));
-    ZK_HIP(hipMemcpyAsync(dM, msgs, mb, hipMemcpyHostToDevice, v->st));
-    ZK_LAUNCH(k_eddsa_fill_hash, zk_div_up(n, BLOCK), BLOCK, v->st, v->view, v->fbtab, v->mtab, v->m_mtab, L, (const fe *)dA, (const fe *)dR, (const fe *)dS,
-              (const uint8_t *)dM, n, (fe *)d_w, row_elems, (uint8_t *)dV);
-    ZK_HIP(hipGetLastError());
-    ZK_HIP(hipMemcpyAsync(verdicts, dV, n, hipMemcpyDeviceToHost, v->st));
-    ZK_HIP(hipStreamSynchronize(v->st));
-    return ZK_OK;
+    return stage_and_fill(v, A, R, s, msgs, v->msg_len, n, verdicts, [&](const Staged &d) {
+        ZK_LAUNCH(k_eddsa_fill_hash, zk_div_up(n, BLOCK), BLOCK, v->st, v->view, v->fbtab, v->mtab, v->m_mtab, L, d.A, d.R, d.s, (const uint8_t *)d.msgs, n, (fe *)d_w,
+                  row_elems, d.verdicts);
+    });
 } ZK_GUARD
 
 // ---- the signer (eddsa_sign.hpp)

@@ -332,6 +332,7 @@ ZK_HD uint32_t modulus_m1_bit(uint32_t i) {
     return (limb >> (i & 31)) & 1;
 }
 ZK_HD fe bit_fe(uint32_t b) { return b ? Fr::one() : Fr::zero(); }
+ZK_HD fe neg_if(const fe &a, bool neg) { return neg ? Fr::lneg(a) : a; }
 
 // one step of a chain: park the projective point in the gadget's block of nv variables and take its Z into the running product
 ZK_JFN void park_point(fe *blk, uint32_t nv, const jpoint &p, fe &run) {
@@ -373,59 +374,54 @@ ZK_JFN fe mimc_cipher_rounds(const fe *__restrict__ rc, const fe &x0, const fe &
     }
     return x;
 }
+// field2bits_strict and BitsNotAbove(bits, r - 1) of the canonical integer t: 254 bits, 253 results, 254 comparisons at tb; 99 products at range
+ZK_JFN void fill_strict_bits(fe *tb, fe *range, const uint32_t *t) {
+    fe *res = tb + FIELD_BITS, *cmp = res + (FIELD_BITS - 1);
+    uint32_t run = 1, eq = int_bit(t, FIELD_BITS - 1), slot = 0;
+#pragma clang loop unroll(disable)
+    for (int i = FIELD_BITS - 1; i >= 0; i--) {                 // from the top bit down
+        const uint32_t b = int_bit(t, i), c = modulus_m1_bit(i) ? 1u : b;
+        tb[i] = bit_fe(b); cmp[i] = bit_fe(c);
+        run &= c;
+        if (i < (int)FIELD_BITS - 1) res[i] = bit_fe(run);      // results[i] = comparisons[i] * results[i + 1] (results[253] = comparisons[253])
+        if (i < (int)FIELD_BITS - 1 && i > 0 && modulus_m1_bit(i)) { eq &= b; range[slot++] = bit_fe(eq); }
+    }
+}
 
-// fbtab: FB_WINDOWS x 4 entries (x, y, d x y) of m 4^i B, m = 0 .. 3 (m = 0: the identity), canonical Montgomery.  s: any 256-bit integer.
-// A or R off the curve or s >= 2^254: verdict 0 and the row is not touched.  Otherwise the whole row, and verdict = (lhs == rhs)
-__global__ void __launch_bounds__(BLOCK)
-k_eddsa_fill(EddsaView v, const fe *__restrict__ fbtab, FillLayout L, const fe *__restrict__ A, const fe *__restrict__ R, const fe *__restrict__ s,
-             const fe *__restrict__ msgs, uint32_t n, fe *d_w, uint64_t row_elems, uint8_t *__restrict__ verdicts) {
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n) return;
-    fe ax, ay, rx, ry;
+// ---- what the rows of the three circuits (FillLayout, PureLayout, HashLayout) have in common, written once: the inputs, the validator with
+// NotLowOrder, the fixed-base chain, the variable-base chains with the closing R + t A, their ways back and their gadgets' products.  Every
+// piece takes the row and a ChainLayout, the twelve offsets that all three layouts hold; the four fill kernels are their own hash, the order
+// of their inversions, and calls of these
+struct ChainLayout {
+    uint32_t ax_var, rx_var, s_bit0, validator_var0, window_var0, fixed_adder_var0, cond0_var, doubler_var0, cond_var0, adder_var0, step_stride,
+             last_adder_var0;
+};
+template <class Layout> ZK_HD ChainLayout chain_layout(const Layout &L) {
+    return {L.ax_var, L.rx_var, L.s_bit0, L.validator_var0, L.window_var0, L.fixed_adder_var0, L.cond0_var, L.doubler_var0, L.cond_var0, L.adder_var0,
+            L.step_stride, L.last_adder_var0};
+}
+
+// item g: A and R in canonical Montgomery form; false when A or R is off the curve or s >= 2^254 (verdict 0, the row is not touched)
+ZK_HD bool fill_load_item(const fe *__restrict__ A, const fe *__restrict__ R, const fe *__restrict__ s, size_t g, fe &ax, fe &ay, fe &rx, fe &ry) {
     load_point(A, g, ax, ay);
     load_point(R, g, rx, ry);
-    const uint32_t *__restrict__ sw = s[g].l;
-    if (!on_curve(ax, ay) || !on_curve(rx, ry) || (sw[7] >> 30)) { verdicts[g] = 0; return; }
+    const bool live = on_curve(ax, ay) && on_curve(rx, ry) && !(s[g].l[7] >> 30);
     ax = Fr::canon(ax); ay = Fr::canon(ay); rx = Fr::canon(rx); ry = Fr::canon(ry);
-    fe *row = d_w + (size_t)g * row_elems;
-    const uint32_t n_hash = 4 + L.msg_len;
-
-    // ---- the inputs
+    return live;
+}
+// ONE, A, R and the 254 bits of s
+ZK_HD void fill_inputs(fe *row, const ChainLayout &C, const fe &ax, const fe &ay, const fe &rx, const fe &ry, const uint32_t *__restrict__ sw) {
     row[0] = Fr::one();
-    row[L.ax_var] = ax; row[L.ax_var + 1] = ay; row[L.rx_var] = rx; row[L.rx_var + 1] = ry;
-    row[L.iv_var] = Fr::zero();
+    row[C.ax_var] = ax; row[C.ax_var + 1] = ay; row[C.rx_var] = rx; row[C.rx_var + 1] = ry;
 #pragma clang loop unroll(disable)
-    for (uint32_t i = 0; i < FIELD_BITS; i++) row[L.s_bit0 + i] = bit_fe(int_bit(sw, i));
+    for (uint32_t i = 0; i < FIELD_BITS; i++) row[C.s_bit0 + i] = bit_fe(int_bit(sw, i));
+}
 
-    // ---- t = the hash, its rounds stored; outputs[i] = key + E_key(x_i) + key + x_i
-    fe k = Fr::zero();
-#pragma clang loop unroll(disable)
-    for (uint32_t i = 0; i < n_hash; i++) {
-        fe xi;
-        if (i < 4) xi = i == 0 ? rx : i == 1 ? ry : i == 2 ? ax : ay;
-        else { xi = Fr::canon(jj_to_mont(msgs[(size_t)g * L.msg_len + (i - 4)])); row[L.msg_var0 + (i - 4)] = xi; }
-        const fe e = mimc_cipher_rounds(v.rc, xi, k, row + L.mimc_var0 + n_hash + (size_t)i * MIMC_ROUND_VARS);
-        k = Fr::ladd(Fr::ladd(k, xi), e);
-        row[L.mimc_var0 + i] = Fr::canon(k);
-    }
-    const fe t = jj_from_mont(k);                               // the canonical integer: its bits are the canonical decomposition
-    {
-        fe *tb = row + L.t_bit0, *res = tb + FIELD_BITS, *cmp = res + (FIELD_BITS - 1);
-        uint32_t run = 1, eq = int_bit(t.l, FIELD_BITS - 1), slot = 0;
-#pragma clang loop unroll(disable)
-        for (int i = FIELD_BITS - 1; i >= 0; i--) {             // from the top bit down
-            const uint32_t b = int_bit(t.l, i), c = modulus_m1_bit(i) ? 1u : b;
-            tb[i] = bit_fe(b); cmp[i] = bit_fe(c);
-            run &= c;
-            if (i < (int)FIELD_BITS - 1) res[i] = bit_fe(run);  // results[i] = comparisons[i] * results[i + 1] (results[253] = comparisons[253])
-            if (i < (int)FIELD_BITS - 1 && i > 0 && modulus_m1_bit(i)) { eq &= b; row[L.t_range_var0 + slot++] = bit_fe(eq); }
-        }
-    }
-
-    // ---- the chains, projective
-    fe run = Fr::one();
+// the fixed segment, projective: the validator's three doublings of R, the x of 8 R, and the 126 additions of s B parked behind them on `run`.
+// fbtab: FB_WINDOWS x 4 entries (x, y, d x y) of m 4^i B, m = 0 .. 3 (m = 0: the identity), canonical Montgomery
+ZK_HD void fixed_forward(fe *row, const ChainLayout &C, const fe *__restrict__ fbtab, const fe &rx, const fe &ry, const uint32_t *__restrict__ sw, fe &run) {
+    fe *val = row + C.validator_var0;
     jpoint p;
-    fe *val = row + L.validator_var0;
     from_affine(p, rx, ry);
 #pragma clang loop unroll(disable)
     for (uint32_t j = 0; j < 3; j++) { jj_dbl(p, false); park_point(val + DBL_VARS * j, DBL_VARS, p, run); }
@@ -435,52 +431,22 @@ k_eddsa_fill(EddsaView v, const fe *__restrict__ fbtab, FillLayout L, const fe *
         val[3 * DBL_VARS] = run; val[3 * DBL_VARS + 1] = x8;
         run = Fr::lmul(run, x8);
     }
-    {                                                           // fixed base: window i adds entry (s >> 2 i) & 3 of its row
-        const fe *e = fbtab + 3 * (size_t)(int_bit(sw, 0) | (int_bit(sw, 1) << 1));
-        row[L.window_var0] = e[0]; row[L.window_var0 + 1] = e[1];
-        from_affine(p, e[0], e[1]);
+    const fe *e = fbtab + 3 * (size_t)(int_bit(sw, 0) | (int_bit(sw, 1) << 1));   // fixed base: window i adds entry (s >> 2 i) & 3 of its row
+    row[C.window_var0] = e[0]; row[C.window_var0 + 1] = e[1];
+    from_affine(p, e[0], e[1]);
 #pragma clang loop unroll(disable)
-        for (uint32_t i = 1; i < FB_WINDOWS; i++) {
-            e = fbtab + 3 * ((size_t)4 * i + (int_bit(sw, 2 * i) | (int_bit(sw, 2 * i + 1) << 1)));
-            row[L.window_var0 + 2 * i] = e[0]; row[L.window_var0 + 2 * i + 1] = e[1];
-            jj_add(p, e, true);
-            park_point(row + L.fixed_adder_var0 + ADD_VARS * (size_t)(i - 1), ADD_VARS, p, run);
-        }
+    for (uint32_t i = 1; i < FB_WINDOWS; i++) {
+        e = fbtab + 3 * ((size_t)4 * i + (int_bit(sw, 2 * i) | (int_bit(sw, 2 * i + 1) << 1)));
+        row[C.window_var0 + 2 * i] = e[0]; row[C.window_var0 + 2 * i + 1] = e[1];
+        jj_add(p, e, true);
+        park_point(row + C.fixed_adder_var0 + ADD_VARS * (size_t)(i - 1), ADD_VARS, p, run);
     }
-    {                                                           // variable base: D = 2^i A, S += bit_i ? D : identity (the same instructions either way)
-        jpoint d;
-        from_affine(d, ax, ay);
-        const uint32_t b0 = int_bit(t.l, 0);
-        row[L.cond0_var] = b0 ? ax : Fr::zero(); row[L.cond0_var + 1] = b0 ? ay : Fr::one();
-        from_affine(p, row[L.cond0_var], row[L.cond0_var + 1]);
+}
+// the way back over the fixed segment: the fixed-base adders, 1 / x of 8 R, the validator's doublings
+ZK_HD void fixed_back(fe *row, const ChainLayout &C, fe &inv) {
+    fe *val = row + C.validator_var0;
 #pragma clang loop unroll(disable)
-        for (uint32_t i = 1; i <= N_STEPS; i++) {
-            const size_t off = (size_t)(i - 1) * L.step_stride;
-            jj_dbl(d, true);
-            park_point(row + L.doubler_var0 + off, DBL_VARS, d, run);
-            const bool b = int_bit(t.l, i);
-            fe q[4];
-            q[0] = b ? d.c[0] : Fr::zero(); q[1] = b ? d.c[1] : Fr::one(); q[2] = b ? jj_mul(coef_d(), d.c[2]) : Fr::zero(); q[3] = b ? d.c[3] : Fr::one();
-            jj_add(p, q, false);
-            park_point(row + L.adder_var0 + off, ADD_VARS, p, run);
-        }
-        fe q[3];                                                // rhs = R + t A
-        q[0] = rx; q[1] = ry; q[2] = jj_mul(coef_d(), jj_mul(rx, ry));
-        jj_add(p, q, true);
-        park_point(row + L.last_adder_var0, ADD_VARS, p, run);
-    }
-
-    // ---- one inversion, then the way back
-    fe inv = jj_inv(run);
-    unpark_point(row + L.last_adder_var0, ADD_VARS, inv);
-#pragma clang loop unroll(disable)
-    for (uint32_t i = N_STEPS; i >= 1; i--) {
-        const size_t off = (size_t)(i - 1) * L.step_stride;
-        unpark_point(row + L.adder_var0 + off, ADD_VARS, inv);
-        unpark_point(row + L.doubler_var0 + off, DBL_VARS, inv);
-    }
-#pragma clang loop unroll(disable)
-    for (uint32_t i = FB_WINDOWS - 1; i >= 1; i--) unpark_point(row + L.fixed_adder_var0 + ADD_VARS * (size_t)(i - 1), ADD_VARS, inv);
+    for (uint32_t i = FB_WINDOWS - 1; i >= 1; i--) unpark_point(row + C.fixed_adder_var0 + ADD_VARS * (size_t)(i - 1), ADD_VARS, inv);
     {
         fe *blk8 = val + 2 * DBL_VARS;                          // still projective: X, Y at [4], [5], Z at [0]
         const bool nz = !Fr::is_zero(Fr::canon(blk8[4]));
@@ -491,46 +457,149 @@ k_eddsa_fill(EddsaView v, const fe *__restrict__ fbtab, FillLayout L, const fe *
     }
 #pragma clang loop unroll(disable)
     for (int j = 2; j >= 0; j--) unpark_point(val + DBL_VARS * j, DBL_VARS, inv);
+}
 
-    // ---- the products of affine inputs
+// variable base: D = 2^i A, S += bit_i of t ? D : identity (the same instructions either way).  var_start: step 0, D = A and S = the first
+// conditional point; var_forward: the steps first .. last (first >= 1), so a caller may restart `run` between two ranges; var_close: rhs = R + t A
+ZK_HD void var_start(fe *row, const ChainLayout &C, const fe &ax, const fe &ay, const uint32_t *t, jpoint &d, jpoint &p) {
+    from_affine(d, ax, ay);
+    const uint32_t b0 = int_bit(t, 0);
+    row[C.cond0_var] = b0 ? ax : Fr::zero(); row[C.cond0_var + 1] = b0 ? ay : Fr::one();
+    from_affine(p, row[C.cond0_var], row[C.cond0_var + 1]);
+}
+ZK_HD void var_forward(fe *row, const ChainLayout &C, const uint32_t *t, uint32_t first, uint32_t last, jpoint &d, jpoint &p, fe &run) {
+#pragma clang loop unroll(disable)
+    for (uint32_t i = first; i <= last; i++) {
+        const size_t off = (size_t)(i - 1) * C.step_stride;
+        jj_dbl(d, true);
+        park_point(row + C.doubler_var0 + off, DBL_VARS, d, run);
+        const bool b = int_bit(t, i);
+        fe q[4];
+        q[0] = b ? d.c[0] : Fr::zero(); q[1] = b ? d.c[1] : Fr::one(); q[2] = b ? jj_mul(coef_d(), d.c[2]) : Fr::zero(); q[3] = b ? d.c[3] : Fr::one();
+        jj_add(p, q, false);
+        park_point(row + C.adder_var0 + off, ADD_VARS, p, run);
+    }
+}
+ZK_HD void var_close(fe *row, const ChainLayout &C, const fe &rx, const fe &ry, jpoint &p, fe &run) {
+    fe q[3];
+    q[0] = rx; q[1] = ry; q[2] = jj_mul(coef_d(), jj_mul(rx, ry));
+    jj_add(p, q, true);
+    park_point(row + C.last_adder_var0, ADD_VARS, p, run);
+}
+// the way back over the steps first .. last (first >= 1) of the variable-base chains, behind the closing adder where the range holds it
+ZK_HD void var_back(fe *row, const ChainLayout &C, uint32_t first, uint32_t last, bool closing, fe &inv) {
+    if (closing) unpark_point(row + C.last_adder_var0, ADD_VARS, inv);
+#pragma clang loop unroll(disable)
+    for (uint32_t i = last; i >= first; i--) {
+        const size_t off = (size_t)(i - 1) * C.step_stride;
+        unpark_point(row + C.adder_var0 + off, ADD_VARS, inv);
+        unpark_point(row + C.doubler_var0 + off, DBL_VARS, inv);
+    }
+}
+
+// ---- the products of affine inputs, once every x3, y3 is affine.  The validator's three doublers and NotLowOrder's x x, y y
+ZK_HD void fill_validator_products(fe *row, const ChainLayout &C, const fe &rx, const fe &ry) {
+    fe *val = row + C.validator_var0;
     fill_doubler(val, rx, ry);
     fill_doubler(val + DBL_VARS, val[4], val[5]);
     fill_doubler(val + 2 * DBL_VARS, val[DBL_VARS + 4], val[DBL_VARS + 5]);
     val[3 * DBL_VARS + 2] = Fr::canon(jj_mul(rx, rx)); val[3 * DBL_VARS + 3] = Fr::canon(jj_mul(ry, ry));
-    {
-        const fe *prev = row + L.window_var0;                   // adder i: (window 0 | the previous sum) + window i + 1
+}
+// the fixed-base adders begin .. end - 1 of 0 .. FB_WINDOWS - 2.  adder i: (window 0 | the previous sum) + window i + 1
+ZK_HD void fill_fixed_products(fe *row, const ChainLayout &C, uint32_t begin, uint32_t end) {
 #pragma clang loop unroll(disable)
-        for (uint32_t i = 0; i + 1 < FB_WINDOWS; i++) {
-            fe *blk = row + L.fixed_adder_var0 + ADD_VARS * (size_t)i;
-            const fe *w = row + L.window_var0 + 2 * (size_t)(i + 1);
-            fill_adder(blk, prev[0], prev[1], w[0], w[1]);
-            prev = blk + ADD_VARS - 2;
-        }
+    for (uint32_t i = begin; i < end; i++) {
+        fe *blk = row + C.fixed_adder_var0 + ADD_VARS * (size_t)i;
+        const fe *prev = i ? blk - 2 : row + C.window_var0, *w = row + C.window_var0 + 2 * (size_t)(i + 1);
+        fill_adder(blk, prev[0], prev[1], w[0], w[1]);
     }
-    {
-        const fe *dprev = row + L.ax_var, *sprev = row + L.cond0_var;
+}
+// the steps begin .. end - 1 of 1 .. N_STEPS: doubler, conditional point, adder; each takes its inputs from the step before (step 1: A, cond0)
+ZK_HD void fill_step_products(fe *row, const ChainLayout &C, const uint32_t *t, uint32_t begin, uint32_t end) {
 #pragma clang loop unroll(disable)
-        for (uint32_t i = 1; i <= N_STEPS; i++) {
-            const size_t off = (size_t)(i - 1) * L.step_stride;
-            fe *dbl = row + L.doubler_var0 + off, *cond = row + L.cond_var0 + off, *add = row + L.adder_var0 + off;
-            fill_doubler(dbl, dprev[0], dprev[1]);
-            const bool b = int_bit(t.l, i);
-            cond[0] = b ? dbl[4] : Fr::zero(); cond[1] = b ? dbl[5] : Fr::one();
-            fill_adder(add, sprev[0], sprev[1], cond[0], cond[1]);
-            dprev = dbl + DBL_VARS - 2; sprev = add + ADD_VARS - 2;
-        }
-        fill_adder(row + L.last_adder_var0, rx, ry, sprev[0], sprev[1]);
+    for (uint32_t i = begin; i < end; i++) {
+        const size_t off = (size_t)(i - 1) * C.step_stride;
+        fe *dbl = row + C.doubler_var0 + off, *cond = row + C.cond_var0 + off, *add = row + C.adder_var0 + off;
+        const fe *dprev = i > 1 ? dbl - C.step_stride + (DBL_VARS - 2) : row + C.ax_var;
+        const fe *sprev = i > 1 ? add - C.step_stride + (ADD_VARS - 2) : row + C.cond0_var;
+        fill_doubler(dbl, dprev[0], dprev[1]);
+        const bool b = int_bit(t, i);
+        cond[0] = b ? dbl[4] : Fr::zero(); cond[1] = b ? dbl[5] : Fr::one();
+        fill_adder(add, sprev[0], sprev[1], cond[0], cond[1]);
     }
-    const fe *lhs = row + L.fixed_adder_var0 + ADD_VARS * (size_t)(FB_WINDOWS - 2) + ADD_VARS - 2, *rhs = row + L.last_adder_var0 + ADD_VARS - 2;
-    verdicts[g] = Fr::eq(lhs[0], rhs[0]) && Fr::eq(lhs[1], rhs[1]) ? 1 : 0;
+}
+// the closing adder R + (t A) and the verdict: lhs = s B, the last fixed-base sum, == rhs
+ZK_HD uint8_t fill_closing(fe *row, const ChainLayout &C, const fe &rx, const fe &ry) {
+    const fe *sprev = row + C.adder_var0 + (size_t)(N_STEPS - 1) * C.step_stride + (ADD_VARS - 2);
+    fill_adder(row + C.last_adder_var0, rx, ry, sprev[0], sprev[1]);
+    const fe *lhs = row + C.fixed_adder_var0 + ADD_VARS * (size_t)(FB_WINDOWS - 2) + ADD_VARS - 2, *rhs = row + C.last_adder_var0 + ADD_VARS - 2;
+    return Fr::eq(lhs[0], rhs[0]) && Fr::eq(lhs[1], rhs[1]) ? 1 : 0;
+}
+// all of them on one lane; returns the verdict
+ZK_HD uint8_t fill_all_products(fe *row, const ChainLayout &C, const fe &rx, const fe &ry, const uint32_t *t) {
+    fill_validator_products(row, C, rx, ry);
+    fill_fixed_products(row, C, 0, FB_WINDOWS - 1);
+    fill_step_products(row, C, t, 1, N_STEPS + 1);
+    return fill_closing(row, C, rx, ry);
+}
+
+// the MiMC hash of R, A and the item's message elements msg, its rounds stored: iv, outputs[i] = key + E_key(x_i) + key + x_i.  Returns t, the
+// canonical integer: its bits are the canonical decomposition
+ZK_HD fe fill_mimc_hash(fe *row, const FillLayout &L, const fe *__restrict__ rc, const fe *__restrict__ msg, const fe &ax, const fe &ay, const fe &rx, const fe &ry) {
+    const uint32_t n_hash = 4 + L.msg_len;
+    row[L.iv_var] = Fr::zero();
+    fe k = Fr::zero();
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0; i < n_hash; i++) {
+        fe xi;
+        if (i < 4) xi = i == 0 ? rx : i == 1 ? ry : i == 2 ? ax : ay;
+        else { xi = Fr::canon(jj_to_mont(msg[i - 4])); row[L.msg_var0 + (i - 4)] = xi; }
+        const fe e = mimc_cipher_rounds(rc, xi, k, row + L.mimc_var0 + n_hash + (size_t)i * MIMC_ROUND_VARS);
+        k = Fr::ladd(Fr::ladd(k, xi), e);
+        row[L.mimc_var0 + i] = Fr::canon(k);
+    }
+    return jj_from_mont(k);
+}
+
+// fbtab as fixed_forward takes it.  s: any 256-bit integer.  A or R off the curve or s >= 2^254: verdict 0 and the row is not touched.
+// Otherwise the whole row, and verdict = (lhs == rhs)
+__global__ void __launch_bounds__(BLOCK)
+k_eddsa_fill(EddsaView v, const fe *__restrict__ fbtab, FillLayout L, const fe *__restrict__ A, const fe *__restrict__ R, const fe *__restrict__ s,
+             const fe *__restrict__ msgs, uint32_t n, fe *d_w, uint64_t row_elems, uint8_t *__restrict__ verdicts) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    fe ax, ay, rx, ry;
+    if (!fill_load_item(A, R, s, g, ax, ay, rx, ry)) { verdicts[g] = 0; return; }
+    const uint32_t *__restrict__ sw = s[g].l;
+    fe *row = d_w + (size_t)g * row_elems;
+    const ChainLayout C = chain_layout(L);
+
+    fill_inputs(row, C, ax, ay, rx, ry, sw);
+    const fe t = fill_mimc_hash(row, L, v.rc, msgs + (size_t)g * L.msg_len, ax, ay, rx, ry);
+    fill_strict_bits(row + L.t_bit0, row + L.t_range_var0, t.l);
+
+    // ---- the chains, projective, on one running product
+    fe run = Fr::one();
+    jpoint d, p;
+    fixed_forward(row, C, fbtab, rx, ry, sw, run);
+    var_start(row, C, ax, ay, t.l, d, p);
+    var_forward(row, C, t.l, 1, N_STEPS, d, p, run);
+    var_close(row, C, rx, ry, p, run);
+
+    // ---- one inversion, then the way back
+    fe inv = jj_inv(run);
+    var_back(row, C, 1, N_STEPS, true, inv);
+    fixed_back(row, C, inv);
+
+    verdicts[g] = fill_all_products(row, C, rx, ry, t.l);
 }
 
 // ---- k_eddsa_fill with ROLES = 2 or 4 lanes per witness: the same row, byte for byte, off a shorter dependent chain.
 //
 // Roles are WAVE-UNIFORM.  A workgroup is ROLES waves; witness blockIdx.x * 64 + (threadIdx.x & 63) is served by lane (threadIdx.x & 63) of every
 // wave, and the wave number threadIdx.x >> 6 is the role, so a branch on the role never splits a wave.  Three phases, two barriers:
-//   forward   role 0: the message elements, MiMC, t with its bits and range products, then both variable-base chains and R + t A, parked as
-//             k_eddsa_fill parks them; role 1: the other inputs, the bits of s, the validator, the x of 8 R and the fixed-base chain.  The 637
+//   forward   role 0: the message elements, MiMC with its iv, t with its bits and range products, then both variable-base chains and
+//             R + t A, parked as k_eddsa_fill parks them; role 1: the other inputs, the bits of s, the validator, the x of 8 R and the fixed-base chain.  The 637
 //             parked items form NSEG segments (WideCut) with a running product each: role 1's 130 items are segment 0, role 0 restarts its
 //             running product after the steps var_end(k).  Every segment's total, and t, go to LDS.  Further roles idle here.
 //   way back  every role multiplies the totals and inverts the product itself (381 products on all waves at once instead of a third barrier and
@@ -559,33 +628,6 @@ template <uint32_t ROLES> struct WideCut {
     ZK_HD static constexpr uint32_t owner(uint32_t sg) { return ROLES == 4 ? (sg == 0 ? 1 : sg == 1 ? 0 : sg) : (sg == 2 ? 0 : 1); }
 };
 
-// the way back over the steps first .. last (first >= 1) of the variable-base chains, behind the closing adder where the segment holds it
-ZK_HD void wide_unpark_var(fe *row, const FillLayout &L, uint32_t first, uint32_t last, bool closing, fe &inv) {
-    if (closing) unpark_point(row + L.last_adder_var0, ADD_VARS, inv);
-#pragma clang loop unroll(disable)
-    for (uint32_t i = last; i >= first; i--) {
-        const size_t off = (size_t)(i - 1) * L.step_stride;
-        unpark_point(row + L.adder_var0 + off, ADD_VARS, inv);
-        unpark_point(row + L.doubler_var0 + off, DBL_VARS, inv);
-    }
-}
-// the way back over segment 0: the fixed-base adders, 1 / x of 8 R, the validator's doublings
-ZK_HD void wide_unpark_fixed(fe *row, const FillLayout &L, fe &inv) {
-    fe *val = row + L.validator_var0;
-#pragma clang loop unroll(disable)
-    for (uint32_t i = FB_WINDOWS - 1; i >= 1; i--) unpark_point(row + L.fixed_adder_var0 + ADD_VARS * (size_t)(i - 1), ADD_VARS, inv);
-    {
-        fe *blk8 = val + 2 * DBL_VARS;                          // still projective: X, Y at [4], [5], Z at [0]
-        const bool nz = !Fr::is_zero(Fr::canon(blk8[4]));
-        const fe xi = Fr::lmul(inv, val[3 * DBL_VARS]);         // 1 / X (or 1 / 1)
-        inv = Fr::lmul(inv, val[3 * DBL_VARS + 1]);
-        val[3 * DBL_VARS] = bit_fe(nz);
-        val[3 * DBL_VARS + 1] = nz ? Fr::canon(Fr::lmul(blk8[0], xi)) : Fr::zero();   // 1 / x = Z / X
-    }
-#pragma clang loop unroll(disable)
-    for (int j = 2; j >= 0; j--) unpark_point(val + DBL_VARS * j, DBL_VARS, inv);
-}
-
 // arguments, malformed items, verdicts and the row as k_eddsa_fill; launched with zk_div_up(n, 64) workgroups of 64 ROLES threads
 template <uint32_t ROLES>
 __global__ void __launch_bounds__(BLOCK * ROLES)
@@ -600,94 +642,44 @@ k_eddsa_fill_wide(EddsaView v, const fe *__restrict__ fbtab, FillLayout L, const
     const size_t gi = in_range ? g : 0;                         // a lane out of range forms no address past the arrays
     const uint32_t *__restrict__ sw = s[gi].l;
     fe ax = Fr::zero(), ay = ax, rx = ax, ry = ax;
-    bool live = in_range;
-    if (live) {
-        load_point(A, g, ax, ay);
-        load_point(R, g, rx, ry);
-        live = on_curve(ax, ay) && on_curve(rx, ry) && !(sw[7] >> 30);
-        ax = Fr::canon(ax); ay = Fr::canon(ay); rx = Fr::canon(rx); ry = Fr::canon(ry);
-    }
+    const bool live = in_range && fill_load_item(A, R, s, gi, ax, ay, rx, ry);
     fe *row = d_w + gi * row_elems;
-    fe *val = row + L.validator_var0;
+    const ChainLayout C = chain_layout(L);
 
     // ---- forward
     if (live && role == 0) {
+        // the hash is fill_mimc_hash written out.  Called as that function the loop's temporaries share a stack slot and the kernel's scratch
+        // falls from 1 088 to 1 056 B a lane, a wave's from 17 to 16.5 pages of 4 KiB -- and at 2^14 witnesses, a workgroup on every compute
+        // unit, the kernel is 1 % slower for it (profiles/eddsa_fill_refactor_ab.txt).  k_eddsa_fill, a quarter of the waves, does not notice
         const uint32_t n_hash = 4 + L.msg_len;
+        row[L.iv_var] = Fr::zero();
         fe k = Fr::zero();
 #pragma clang loop unroll(disable)
-        for (uint32_t i = 0; i < n_hash; i++) {                 // t = the hash, its rounds stored
+        for (uint32_t i = 0; i < n_hash; i++) {
             fe xi;
             if (i < 4) xi = i == 0 ? rx : i == 1 ? ry : i == 2 ? ax : ay;
-            else { xi = Fr::canon(jj_to_mont(msgs[(size_t)g * L.msg_len + (i - 4)])); row[L.msg_var0 + (i - 4)] = xi; }
+            else { xi = Fr::canon(jj_to_mont(msgs[gi * L.msg_len + (i - 4)])); row[L.msg_var0 + (i - 4)] = xi; }
             const fe e = mimc_cipher_rounds(v.rc, xi, k, row + L.mimc_var0 + n_hash + (size_t)i * MIMC_ROUND_VARS);
             k = Fr::ladd(Fr::ladd(k, xi), e);
             row[L.mimc_var0 + i] = Fr::canon(k);
         }
         const fe t = jj_from_mont(k);
         xch[T_SLOT][j] = t;
-        {
-            fe *tb = row + L.t_bit0, *res = tb + FIELD_BITS, *cmp = res + (FIELD_BITS - 1);
-            uint32_t run = 1, eq = int_bit(t.l, FIELD_BITS - 1), slot = 0;
-#pragma clang loop unroll(disable)
-            for (int i = FIELD_BITS - 1; i >= 0; i--) {         // from the top bit down, as k_eddsa_fill
-                const uint32_t b = int_bit(t.l, i), c = modulus_m1_bit(i) ? 1u : b;
-                tb[i] = bit_fe(b); cmp[i] = bit_fe(c);
-                run &= c;
-                if (i < (int)FIELD_BITS - 1) res[i] = bit_fe(run);
-                if (i < (int)FIELD_BITS - 1 && i > 0 && modulus_m1_bit(i)) { eq &= b; row[L.t_range_var0 + slot++] = bit_fe(eq); }
-            }
-        }
-        fe run = Fr::one();                                     // variable base: D = 2^i A, S += bit_i ? D : identity
-        jpoint d, p;
-        from_affine(d, ax, ay);
-        const uint32_t b0 = int_bit(t.l, 0);
-        row[L.cond0_var] = b0 ? ax : Fr::zero(); row[L.cond0_var + 1] = b0 ? ay : Fr::one();
-        from_affine(p, row[L.cond0_var], row[L.cond0_var + 1]);
-        uint32_t sg = 0;
-#pragma clang loop unroll(disable)
-        for (uint32_t i = 1; i <= N_STEPS; i++) {
-            const size_t off = (size_t)(i - 1) * L.step_stride;
-            jj_dbl(d, true);
-            park_point(row + L.doubler_var0 + off, DBL_VARS, d, run);
-            const bool b = int_bit(t.l, i);
-            fe q[4];
-            q[0] = b ? d.c[0] : Fr::zero(); q[1] = b ? d.c[1] : Fr::one(); q[2] = b ? jj_mul(coef_d(), d.c[2]) : Fr::zero(); q[3] = b ? d.c[3] : Fr::one();
-            jj_add(p, q, false);
-            park_point(row + L.adder_var0 + off, ADD_VARS, p, run);
-            if (sg + 1 < Cut::NV && i == Cut::var_end(sg)) { xch[1 + sg][j] = run; run = Fr::one(); sg++; }   // a segment ends: its total, a new product
-        }
-        fe q[3];                                                // rhs = R + t A
-        q[0] = rx; q[1] = ry; q[2] = jj_mul(coef_d(), jj_mul(rx, ry));
-        jj_add(p, q, true);
-        park_point(row + L.last_adder_var0, ADD_VARS, p, run);
-        xch[Cut::NV][j] = run;
-    } else if (live && role == 1) {
-        row[0] = Fr::one();
-        row[L.ax_var] = ax; row[L.ax_var + 1] = ay; row[L.rx_var] = rx; row[L.rx_var + 1] = ry;
-        row[L.iv_var] = Fr::zero();
-#pragma clang loop unroll(disable)
-        for (uint32_t i = 0; i < FIELD_BITS; i++) row[L.s_bit0 + i] = bit_fe(int_bit(sw, i));
+        fill_strict_bits(row + L.t_bit0, row + L.t_range_var0, t.l);
         fe run = Fr::one();
-        jpoint p;
-        from_affine(p, rx, ry);
+        jpoint d, p;
+        var_start(row, C, ax, ay, t.l, d, p);
 #pragma clang loop unroll(disable)
-        for (uint32_t i = 0; i < 3; i++) { jj_dbl(p, false); park_point(val + DBL_VARS * i, DBL_VARS, p, run); }
-        {                                                       // IsNonZero(x of 8 R): Y holds the prefix, M the value (1 in the place of 0)
-            const bool nz = !Fr::is_zero(Fr::canon(p.c[0]));
-            const fe x8 = nz ? p.c[0] : Fr::one();
-            val[3 * DBL_VARS] = run; val[3 * DBL_VARS + 1] = x8;
-            run = Fr::lmul(run, x8);
+        for (uint32_t k = 0; k < Cut::NV; k++) {                // a segment ends: its total, a new product
+            var_forward(row, C, t.l, k ? Cut::var_end(k - 1) + 1 : 1, Cut::var_end(k), d, p, run);
+            if (k + 1 == Cut::NV) var_close(row, C, rx, ry, p, run);
+            xch[1 + k][j] = run;
+            run = Fr::one();
         }
-        const fe *e = fbtab + 3 * (size_t)(int_bit(sw, 0) | (int_bit(sw, 1) << 1));   // fixed base: window i adds entry (s >> 2 i) & 3 of its row
-        row[L.window_var0] = e[0]; row[L.window_var0 + 1] = e[1];
-        from_affine(p, e[0], e[1]);
-#pragma clang loop unroll(disable)
-        for (uint32_t i = 1; i < FB_WINDOWS; i++) {
-            e = fbtab + 3 * ((size_t)4 * i + (int_bit(sw, 2 * i) | (int_bit(sw, 2 * i + 1) << 1)));
-            row[L.window_var0 + 2 * i] = e[0]; row[L.window_var0 + 2 * i + 1] = e[1];
-            jj_add(p, e, true);
-            park_point(row + L.fixed_adder_var0 + ADD_VARS * (size_t)(i - 1), ADD_VARS, p, run);
-        }
+    } else if (live && role == 1) {
+        fill_inputs(row, C, ax, ay, rx, ry, sw);
+        fe run = Fr::one();
+        fixed_forward(row, C, fbtab, rx, ry, sw, run);
         xch[0][j] = run;
     }
     __syncthreads();
@@ -705,61 +697,30 @@ k_eddsa_fill_wide(EddsaView v, const fe *__restrict__ fbtab, FillLayout L, const
             if (Cut::owner(sg) != role) continue;
             fe inv = inv_all;                                   // 1 / (this segment's total) = 1 / (all) x the other totals
             for (uint32_t k = 0; k < NSEG; k++) if (k != sg) inv = jj_mul(inv, tot[k]);
-            if (sg == 0) wide_unpark_fixed(row, L, inv);
-            else wide_unpark_var(row, L, sg == 1 ? 1 : Cut::var_end(sg - 2) + 1, Cut::var_end(sg - 1), sg == Cut::NV, inv);
+            if (sg == 0) fixed_back(row, C, inv);
+            else var_back(row, C, sg == 1 ? 1 : Cut::var_end(sg - 2) + 1, Cut::var_end(sg - 1), sg == Cut::NV, inv);
         }
     }
     __syncthreads();
 
-    // ---- the products of affine inputs: adders f0 .. f1 - 1 of the fixed base and steps s0 .. s1 - 1 of the variable base on this role
+    // ---- the products of affine inputs: an even share of the fixed-base adders and of the steps on every role
     if (live) {
-        const uint32_t f0 = (FB_WINDOWS - 1) * role / ROLES, f1 = (FB_WINDOWS - 1) * (role + 1) / ROLES;
-#pragma clang loop unroll(disable)
-        for (uint32_t i = f0; i < f1; i++) {                    // adder i: (window 0 | the previous sum) + window i + 1
-            fe *blk = row + L.fixed_adder_var0 + ADD_VARS * (size_t)i;
-            const fe *prev = i ? blk - 2 : row + L.window_var0, *w = row + L.window_var0 + 2 * (size_t)(i + 1);
-            fill_adder(blk, prev[0], prev[1], w[0], w[1]);
-        }
-        const uint32_t s0 = 1 + N_STEPS * role / ROLES, s1 = 1 + N_STEPS * (role + 1) / ROLES;
-#pragma clang loop unroll(disable)
-        for (uint32_t i = s0; i < s1; i++) {
-            const size_t off = (size_t)(i - 1) * L.step_stride;
-            fe *dbl = row + L.doubler_var0 + off, *cond = row + L.cond_var0 + off, *add = row + L.adder_var0 + off;
-            const fe *dprev = i > 1 ? dbl - L.step_stride + (DBL_VARS - 2) : row + L.ax_var;
-            const fe *sprev = i > 1 ? add - L.step_stride + (ADD_VARS - 2) : row + L.cond0_var;
-            fill_doubler(dbl, dprev[0], dprev[1]);
-            const bool b = int_bit(t.l, i);
-            cond[0] = b ? dbl[4] : Fr::zero(); cond[1] = b ? dbl[5] : Fr::one();
-            fill_adder(add, sprev[0], sprev[1], cond[0], cond[1]);
-        }
-        if (role == ROLES - 1) {
-            fill_doubler(val, rx, ry);
-            fill_doubler(val + DBL_VARS, val[4], val[5]);
-            fill_doubler(val + 2 * DBL_VARS, val[DBL_VARS + 4], val[DBL_VARS + 5]);
-            val[3 * DBL_VARS + 2] = Fr::canon(jj_mul(rx, rx)); val[3 * DBL_VARS + 3] = Fr::canon(jj_mul(ry, ry));
-        }
+        fill_fixed_products(row, C, (FB_WINDOWS - 1) * role / ROLES, (FB_WINDOWS - 1) * (role + 1) / ROLES);
+        fill_step_products(row, C, t.l, 1 + N_STEPS * role / ROLES, 1 + N_STEPS * (role + 1) / ROLES);
+        if (role == ROLES - 1) fill_validator_products(row, C, rx, ry);
     }
-    if (role == 0 && in_range) {                                // the one role that answers
-        uint8_t ok = 0;
-        if (live) {
-            const fe *sprev = row + L.adder_var0 + (size_t)(N_STEPS - 1) * L.step_stride + (ADD_VARS - 2);
-            fill_adder(row + L.last_adder_var0, rx, ry, sprev[0], sprev[1]);
-            const fe *lhs = row + L.fixed_adder_var0 + ADD_VARS * (size_t)(FB_WINDOWS - 2) + ADD_VARS - 2, *rhs = row + L.last_adder_var0 + ADD_VARS - 2;
-            ok = Fr::eq(lhs[0], rhs[0]) && Fr::eq(lhs[1], rhs[1]) ? 1 : 0;
-        }
-        verdicts[g] = ok;
-    }
+    if (role == 0 && in_range) verdicts[g] = live ? fill_closing(row, C, rx, ry) : 0;   // the one role that answers
 }
 
-// ---- the complete witness of the PureEdDSA circuit (jubjub_gadgets.py, eddsa_pure_circuit): the row of k_eddsa_fill with the windowed Pedersen
-// hash in the place of MiMC.  PureLayout is zk_eddsa_pure_layout of zkhip.h; the host has checked it as it checks FillLayout.
+// ---- the complete witness of the PureEdDSA circuit (jubjub_gadgets.py, eddsa_pure_circuit): the row of the MiMC-EdDSA circuit with the
+// windowed Pedersen hash in the place of MiMC.  PureLayout is zk_eddsa_pure_layout of zkhip.h; the host has checked it as it checks FillLayout.
 //
 // TWO inversions per witness, whatever the number of windows.  The hash names, per window past the first of a segment, the AFFINE MONTGOMERY
 // running sum (X3, Y3 of a MontgomeryAdder) and the slope lambda = (v2 - v1) / (u2 - u1) that led to it, and per segment the affine Edwards sum
 // (MontgomeryToEdwards).  The lane walks a segment's running sum in extended Edwards coordinates with the mixed additions of k_jj_pedersen and
 // takes every quotient from (X : Y : Z):  u = (Z + Y) / (Z - Y),  v = u Z / X,  u2 - u = (u2 (Z - Y) - (Z + Y)) / (Z - Y), u2 the tabulated
 // Montgomery x of the next window's table point.  One denominator a step, E = (Z - Y) X D3 with D3 = u2 (Z - Y) - (Z + Y) -- or Z at the end of a
-// segment, where 1 / Z gives the converter's Edwards point -- joins the running product of k_eddsa_fill: 1 / (Z - Y) = X D3 / E,
+// segment, where 1 / Z gives the converter's Edwards point -- joins the running product of the chains: 1 / (Z - Y) = X D3 / E,
 // 1 / ((Z - Y) X) = D3 / E, 1 / D3 = (Z - Y) X / E.  (X, Y, Z) wait in the adder's three slots, the prefix product and E in the window's two.
 // The first window of a segment is a table point: its step's denominator is u2 - u0, two table values.  No step has a special case (the argument
 // is at FixedBaseMulZcash in jubjub_gadgets.py and in DESIGN 5k).  The first inversion closes the validator, the fixed-base chain and the hash
@@ -772,278 +733,9 @@ struct PureLayout {
 constexpr uint32_t MADD_VARS = 3, SEG_ADDERS = SEG_WINDOWS - 1;
 ZK_HD uint32_t pure_windows(uint32_t msg_len) { return (2 * FIELD_BITS + 8 * msg_len + 2) / 3; }
 
-// field2bits_strict and BitsNotAbove(bits, r - 1) of the canonical integer t: 254 bits, 253 results, 254 comparisons at tb; 99 products at range
-ZK_JFN void fill_strict_bits(fe *tb, fe *range, const uint32_t *t) {
-    fe *res = tb + FIELD_BITS, *cmp = res + (FIELD_BITS - 1);
-    uint32_t run = 1, eq = int_bit(t, FIELD_BITS - 1), slot = 0;
-#pragma clang loop unroll(disable)
-    for (int i = FIELD_BITS - 1; i >= 0; i--) {
-        const uint32_t b = int_bit(t, i), c = modulus_m1_bit(i) ? 1u : b;
-        tb[i] = bit_fe(b); cmp[i] = bit_fe(c);
-        run &= c;
-        if (i < (int)FIELD_BITS - 1) res[i] = bit_fe(run);
-        if (i < (int)FIELD_BITS - 1 && i > 0 && modulus_m1_bit(i)) { eq &= b; range[slot++] = bit_fe(eq); }
-    }
-}
-ZK_HD fe neg_if(const fe &a, bool neg) { return neg ? Fr::lneg(a) : a; }
-
-// mtab: per entry of ram_tab the Montgomery form (u, v) = ((1 + y) / (1 - y), u / x) of the table point, canonical Montgomery.  msgs: msg_len
-// bytes an item.  Malformed items, verdicts and the row's form as k_eddsa_fill
-__global__ void __launch_bounds__(BLOCK)
-k_eddsa_fill_pure(EddsaView v, const fe *__restrict__ fbtab, const fe *__restrict__ mtab, PureLayout L, const fe *__restrict__ A, const fe *__restrict__ R,
-                  const fe *__restrict__ s, const uint8_t *__restrict__ msgs, uint32_t n, fe *d_w, uint64_t row_elems, uint8_t *__restrict__ verdicts) {
-    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n) return;
-    fe ax, ay, rx, ry;
-    load_point(A, g, ax, ay);
-    load_point(R, g, rx, ry);
-    const uint32_t *__restrict__ sw = s[g].l;
-    if (!on_curve(ax, ay) || !on_curve(rx, ry) || (sw[7] >> 30)) { verdicts[g] = 0; return; }
-    ax = Fr::canon(ax); ay = Fr::canon(ay); rx = Fr::canon(rx); ry = Fr::canon(ry);
-    fe *row = d_w + (size_t)g * row_elems;
-    BitStream bs;
-    bs.rx = R[2 * (size_t)g].l; bs.ax = A[2 * (size_t)g].l; bs.mx = nullptr; bs.msg = msgs + (size_t)g * L.msg_len; bs.msg_bits = 8 * L.msg_len;
-    const uint32_t W = v.ram_windows, lone = W % SEG_WINDOWS == 1 ? 1u : 0u, n_seg = (W - lone + SEG_WINDOWS - 1) / SEG_WINDOWS;
-
-    // ---- the inputs and the two decompositions that feed the hash
-    row[0] = Fr::one();
-    row[L.ax_var] = ax; row[L.ax_var + 1] = ay; row[L.rx_var] = rx; row[L.rx_var + 1] = ry;
-#pragma clang loop unroll(disable)
-    for (uint32_t i = 0; i < FIELD_BITS; i++) row[L.s_bit0 + i] = bit_fe(int_bit(sw, i));
-#pragma clang loop unroll(disable)
-    for (uint32_t i = 0; i < bs.msg_bits; i++) row[L.msg_bit0 + i] = bit_fe(bs.bit(2 * FIELD_BITS + i));
-#pragma clang loop unroll(disable)
-    for (uint32_t i = 0; i < 3 * W - 2 * FIELD_BITS - bs.msg_bits; i++) row[L.pad_bit0 + i] = Fr::zero();
-    fill_strict_bits(row + L.rx_bit0, row + L.rx_range_var0, bs.rx);
-    fill_strict_bits(row + L.ax_bit0, row + L.ax_range_var0, bs.ax);
-
-    // ---- the first set of chains, projective: validator, fixed base, hash
-    fe run = Fr::one();
-    jpoint p;
-    fe *val = row + L.validator_var0;
-    from_affine(p, rx, ry);
-#pragma clang loop unroll(disable)
-    for (uint32_t j = 0; j < 3; j++) { jj_dbl(p, false); park_point(val + DBL_VARS * j, DBL_VARS, p, run); }
-    {
-        const bool nz = !Fr::is_zero(Fr::canon(p.c[0]));
-        const fe x8 = nz ? p.c[0] : Fr::one();
-        val[3 * DBL_VARS] = run; val[3 * DBL_VARS + 1] = x8;
-        run = Fr::lmul(run, x8);
-    }
-    {
-        const fe *e = fbtab + 3 * (size_t)(int_bit(sw, 0) | (int_bit(sw, 1) << 1));
-        row[L.window_var0] = e[0]; row[L.window_var0 + 1] = e[1];
-        from_affine(p, e[0], e[1]);
-#pragma clang loop unroll(disable)
-        for (uint32_t i = 1; i < FB_WINDOWS; i++) {
-            e = fbtab + 3 * ((size_t)4 * i + (int_bit(sw, 2 * i) | (int_bit(sw, 2 * i + 1) << 1)));
-            row[L.window_var0 + 2 * i] = e[0]; row[L.window_var0 + 2 * i + 1] = e[1];
-            jj_add(p, e, true);
-            park_point(row + L.fixed_adder_var0 + ADD_VARS * (size_t)(i - 1), ADD_VARS, p, run);
-        }
-    }
-    fe *hw = row + L.hash_window_var0, *madd = row + L.mont_adder_var0, *conv = row + L.converter_var0, *ed = row + L.edwards_adder_var0;
-    {
-        jpoint hacc;
-        if (lone) {                                             // the last base point's single window: its converter is the table point itself
-            const uint32_t j = W - 1, w = bs.window(j);
-            const fe *e = v.ram_tab + ((size_t)j * 4 + (w & 3)) * 3;
-            const fe x = Fr::canon(neg_if(e[0], w > 3));
-            conv[0] = x; conv[1] = e[1];
-            from_affine(hacc, x, e[1]);
-        }
-#pragma clang loop unroll(disable)
-        for (uint32_t sg = 0; sg < n_seg; sg++) {
-            const uint32_t j0 = sg * SEG_WINDOWS, m = W - lone - j0 < SEG_WINDOWS ? W - lone - j0 : SEG_WINDOWS;   // m >= 2
-            uint32_t w = bs.window(j0);
-            {
-                const fe *e = v.ram_tab + ((size_t)j0 * 4 + (w & 3)) * 3;
-                from_affine(p, neg_if(e[0], w > 3), e[1]);
-            }
-#pragma clang loop unroll(disable)
-            for (uint32_t k = 0; k < m; k++) {
-                const uint32_t j = j0 + k;
-                const bool last = k + 1 == m;
-                const uint32_t w2 = last ? 0u : bs.window(j + 1);
-                const fe u2 = mtab[((size_t)(last ? j : j + 1) * 4 + (w2 & 3)) * 2];
-                fe E;
-                if (k == 0) E = Fr::lsub(u2, mtab[((size_t)j * 4 + (w & 3)) * 2]);
-                else {
-                    fe *blk = madd + MADD_VARS * (size_t)(sg * SEG_ADDERS + k - 1);
-                    blk[0] = p.c[0]; blk[1] = p.c[1]; blk[2] = p.c[3];
-                    const fe d1 = Fr::lsub(p.c[3], p.c[1]);
-                    const fe d3 = last ? p.c[3] : Fr::lsub(Fr::lmul(u2, d1), Fr::ladd(p.c[3], p.c[1]));
-                    E = Fr::lmul(Fr::lmul(d1, p.c[0]), d3);
-                }
-                hw[2 * (size_t)j] = run; hw[2 * (size_t)j + 1] = E;
-                run = Fr::lmul(run, E);
-                if (!last) { pedersen_step(p, v.ram_tab, j + 1, w2); w = w2; }
-            }
-            if (!lone && sg == 0) hacc = p;
-            else {
-                fe q[4];
-                q[0] = p.c[0]; q[1] = p.c[1]; q[2] = jj_mul(coef_d(), p.c[2]); q[3] = p.c[3];
-                jj_add(hacc, q, false);
-                park_point(ed + ADD_VARS * (size_t)(sg - 1 + lone), ADD_VARS, hacc, run);
-            }
-        }
-    }
-
-    // ---- the first inversion and its way back
-    fe inv = jj_inv(run);
-#pragma clang loop unroll(disable)
-    for (int sg = (int)n_seg - 1; sg >= 0; sg--) {
-        const uint32_t j0 = sg * SEG_WINDOWS, m = W - lone - j0 < SEG_WINDOWS ? W - lone - j0 : SEG_WINDOWS;
-        if (lone || sg > 0) unpark_point(ed + ADD_VARS * (size_t)(sg - 1 + lone), ADD_VARS, inv);
-#pragma clang loop unroll(disable)
-        for (int k = (int)m - 1; k >= 0; k--) {
-            const uint32_t j = j0 + k;
-            const bool last = k + 1 == (int)m;
-            fe *win = hw + 2 * (size_t)j;
-            const fe einv = Fr::lmul(inv, win[0]);              // 1 / E of this step
-            inv = Fr::lmul(inv, win[1]);
-            const uint32_t w = bs.window(j), w2 = last ? 0u : bs.window(j + 1);
-            const fe vown = Fr::canon(neg_if(mtab[((size_t)j * 4 + (w & 3)) * 2 + 1], w > 3));
-            const fe *m2 = mtab + ((size_t)(last ? j : j + 1) * 4 + (w2 & 3)) * 2;
-            const fe u2 = m2[0], v2 = neg_if(m2[1], w2 > 3);
-            if (k == 0) madd[MADD_VARS * (size_t)(sg * SEG_ADDERS)] = Fr::canon(Fr::lmul(Fr::lsub(v2, vown), einv));
-            else {
-                fe *blk = madd + MADD_VARS * (size_t)(sg * SEG_ADDERS + k - 1);
-                const fe X = blk[0], Y = blk[1], Z = blk[2];
-                const fe d1 = Fr::lsub(Z, Y), zpy = Fr::ladd(Z, Y);
-                const fe d3 = last ? Z : Fr::lsub(Fr::lmul(u2, d1), zpy);
-                const fe i2 = Fr::lmul(einv, d3), i1 = Fr::lmul(i2, X);                  // 1 / ((Z - Y) X), 1 / (Z - Y)
-                const fe i3 = Fr::lmul(einv, Fr::lmul(d1, X));                            // 1 / D3
-                const fe vv = Fr::lmul(Fr::lmul(zpy, Z), i2);
-                blk[1] = Fr::canon(Fr::lmul(zpy, i1)); blk[2] = Fr::canon(vv);
-                if (last) {
-                    fe *c = conv + 2 * (size_t)(sg + lone);
-                    c[0] = Fr::canon(Fr::lmul(X, i3)); c[1] = Fr::canon(Fr::lmul(Y, i3));
-                } else blk[MADD_VARS] = Fr::canon(Fr::lmul(Fr::lsub(v2, vv), Fr::lmul(i3, d1)));   // the next adder's lambda
-            }
-            win[0] = bit_fe((w & 3) == 3); win[1] = vown;
-        }
-    }
-    if (lone) {
-        const uint32_t j = W - 1, w = bs.window(j);
-        hw[2 * (size_t)j] = bit_fe((w & 3) == 3);
-        hw[2 * (size_t)j + 1] = Fr::canon(neg_if(mtab[((size_t)j * 4 + (w & 3)) * 2 + 1], w > 3));
-    }
-#pragma clang loop unroll(disable)
-    for (uint32_t i = FB_WINDOWS - 1; i >= 1; i--) unpark_point(row + L.fixed_adder_var0 + ADD_VARS * (size_t)(i - 1), ADD_VARS, inv);
-    {
-        fe *blk8 = val + 2 * DBL_VARS;
-        const bool nz = !Fr::is_zero(Fr::canon(blk8[4]));
-        const fe xi = Fr::lmul(inv, val[3 * DBL_VARS]);
-        inv = Fr::lmul(inv, val[3 * DBL_VARS + 1]);
-        val[3 * DBL_VARS] = bit_fe(nz);
-        val[3 * DBL_VARS + 1] = nz ? Fr::canon(Fr::lmul(blk8[0], xi)) : Fr::zero();
-    }
-#pragma clang loop unroll(disable)
-    for (int j = 2; j >= 0; j--) unpark_point(val + DBL_VARS * j, DBL_VARS, inv);
-
-    // ---- the Edwards adders over the converted segments; t = the x of the last, its bits
-    const uint32_t n_conv = n_seg + lone;
-    {
-        const fe *prev = conv;
-#pragma clang loop unroll(disable)
-        for (uint32_t i = 0; i + 1 < n_conv; i++) {
-            fe *blk = ed + ADD_VARS * (size_t)i;
-            fill_adder(blk, prev[0], prev[1], conv[2 * (size_t)(i + 1)], conv[2 * (size_t)(i + 1) + 1]);
-            prev = blk + ADD_VARS - 2;
-        }
-    }
-    const fe t = jj_from_mont(ed[ADD_VARS * (size_t)(n_conv - 2) + ADD_VARS - 2]);
-    fill_strict_bits(row + L.t_bit0, row + L.t_range_var0, t.l);
-
-    // ---- the second set: variable base and R + t A
-    run = Fr::one();
-    {
-        jpoint d;
-        from_affine(d, ax, ay);
-        const uint32_t b0 = int_bit(t.l, 0);
-        row[L.cond0_var] = b0 ? ax : Fr::zero(); row[L.cond0_var + 1] = b0 ? ay : Fr::one();
-        from_affine(p, row[L.cond0_var], row[L.cond0_var + 1]);
-#pragma clang loop unroll(disable)
-        for (uint32_t i = 1; i <= N_STEPS; i++) {
-            const size_t off = (size_t)(i - 1) * L.step_stride;
-            jj_dbl(d, true);
-            park_point(row + L.doubler_var0 + off, DBL_VARS, d, run);
-            const bool b = int_bit(t.l, i);
-            fe q[4];
-            q[0] = b ? d.c[0] : Fr::zero(); q[1] = b ? d.c[1] : Fr::one(); q[2] = b ? jj_mul(coef_d(), d.c[2]) : Fr::zero(); q[3] = b ? d.c[3] : Fr::one();
-            jj_add(p, q, false);
-            park_point(row + L.adder_var0 + off, ADD_VARS, p, run);
-        }
-        fe q[3];
-        q[0] = rx; q[1] = ry; q[2] = jj_mul(coef_d(), jj_mul(rx, ry));
-        jj_add(p, q, true);
-        park_point(row + L.last_adder_var0, ADD_VARS, p, run);
-    }
-    inv = jj_inv(run);
-    unpark_point(row + L.last_adder_var0, ADD_VARS, inv);
-#pragma clang loop unroll(disable)
-    for (uint32_t i = N_STEPS; i >= 1; i--) {
-        const size_t off = (size_t)(i - 1) * L.step_stride;
-        unpark_point(row + L.adder_var0 + off, ADD_VARS, inv);
-        unpark_point(row + L.doubler_var0 + off, DBL_VARS, inv);
-    }
-
-    // ---- the products of affine inputs
-    fill_doubler(val, rx, ry);
-    fill_doubler(val + DBL_VARS, val[4], val[5]);
-    fill_doubler(val + 2 * DBL_VARS, val[DBL_VARS + 4], val[DBL_VARS + 5]);
-    val[3 * DBL_VARS + 2] = Fr::canon(jj_mul(rx, rx)); val[3 * DBL_VARS + 3] = Fr::canon(jj_mul(ry, ry));
-    {
-        const fe *prev = row + L.window_var0;
-#pragma clang loop unroll(disable)
-        for (uint32_t i = 0; i + 1 < FB_WINDOWS; i++) {
-            fe *blk = row + L.fixed_adder_var0 + ADD_VARS * (size_t)i;
-            const fe *w = row + L.window_var0 + 2 * (size_t)(i + 1);
-            fill_adder(blk, prev[0], prev[1], w[0], w[1]);
-            prev = blk + ADD_VARS - 2;
-        }
-    }
-    {
-        const fe *dprev = row + L.ax_var, *sprev = row + L.cond0_var;
-#pragma clang loop unroll(disable)
-        for (uint32_t i = 1; i <= N_STEPS; i++) {
-            const size_t off = (size_t)(i - 1) * L.step_stride;
-            fe *dbl = row + L.doubler_var0 + off, *cond = row + L.cond_var0 + off, *add = row + L.adder_var0 + off;
-            fill_doubler(dbl, dprev[0], dprev[1]);
-            const bool b = int_bit(t.l, i);
-            cond[0] = b ? dbl[4] : Fr::zero(); cond[1] = b ? dbl[5] : Fr::one();
-            fill_adder(add, sprev[0], sprev[1], cond[0], cond[1]);
-            dprev = dbl + DBL_VARS - 2; sprev = add + ADD_VARS - 2;
-        }
-        fill_adder(row + L.last_adder_var0, rx, ry, sprev[0], sprev[1]);
-    }
-    const fe *lhs = row + L.fixed_adder_var0 + ADD_VARS * (size_t)(FB_WINDOWS - 2) + ADD_VARS - 2, *rhs = row + L.last_adder_var0 + ADD_VARS - 2;
-    verdicts[g] = Fr::eq(lhs[0], rhs[0]) && Fr::eq(lhs[1], rhs[1]) ? 1 : 0;
-}
-
-// ---- the complete witness of the EdDSA circuit of the "hash" scheme (jubjub_gadgets.py, EddsaHashCircuit): the row of k_eddsa_fill_pure with a
-// SECOND in-circuit Pedersen hash in front, M = the hash "EdDSA_Verify.M" of the message bits, whose 254 strict bits are the third part of the
-// input of the hash "EdDSA_Verify.RAM".  HashLayout is zk_eddsa_hash_layout of zkhip.h; the host has checked it as it checks PureLayout.
-//
-// THREE inversions per witness, whatever msg_len.  The walk of one hash is that of k_eddsa_fill_pure, here as two device functions over a HashWalk
-// (the table, its Montgomery form, the four segments of the row, the window count, the first bit of the stream): hash_walk_forward parks every
-// denominator on the caller's running product, hash_walk_back takes the quotients on the way back.  The message hash joins the product of the
-// validator and of the fixed-base chain, which need nothing from it: the first inversion closes all three and yields M.x.  The RAM hash needs
-// the bits of M.x and yields t (the second inversion); the variable-base chain needs the bits of t (the third).  The message hash may have a
-// single segment (msg_len <= 23: no Edwards adder, M is the converter's point) and, unlike the RAM hash of this circuit, a lone last window
-// (W_m % 62 == 1).  No step has a special case: DESIGN 5m restates the argument of 5k for the table of "EdDSA_Verify.M".
-struct HashLayout {
-    uint32_t msg_len, n_vars, ax_var, msg_bit0, rx_var, s_bit0, validator_var0, window_var0, fixed_adder_var0, rx_bit0, rx_range_var0,
-             ax_bit0, ax_range_var0, hash_window_var0, mont_adder_var0, converter_var0, edwards_adder_var0, t_bit0, t_range_var0, cond0_var,
-             doubler_var0, cond_var0, adder_var0, step_stride, last_adder_var0, m_pad_bit0, m_window_var0, m_mont_adder_var0, m_converter_var0,
-             m_edwards_adder_var0, m_bit0, m_range_var0;
-};
-constexpr uint32_t HASH_RAM_WINDOWS = FIELD_BITS;                // 3 x 254 bits: 254 windows, segments of 62, 62, 62, 62 and 6
-ZK_HD uint32_t hash_msg_windows(uint32_t msg_len) { return (8 * msg_len + 2) / 3; }
-
-// one in-circuit hash: tab / mtab = its table and the (u, v) of every entry; hw, madd, conv, ed = its windows, Montgomery adders, converters and
-// Edwards adders in the row; W windows over the bits of the stream from bit0 on
+// one in-circuit hash: tab / mtab = its table and, per entry of it, the Montgomery form (u, v) = ((1 + y) / (1 - y), u / x) of the table point,
+// canonical Montgomery; hw, madd, conv, ed = its windows, Montgomery adders, converters and Edwards adders in the row; W windows over the bits
+// of the stream from bit0 on
 struct HashWalk {
     const fe *tab, *mtab;
     fe *hw, *madd, *conv, *ed;
@@ -1054,9 +746,9 @@ struct HashWalk {
     ZK_HD uint32_t window(const BitStream &bs, uint32_t j) const { const uint32_t i = bit0 + 3 * j; return bs.bit(i) | (bs.bit(i + 1) << 1) | (bs.bit(i + 2) << 2); }
 };
 
-// the forward walk of k_eddsa_fill_pure's hash: per window the prefix product and the denominator E wait in the window's two slots, (X, Y, Z) in
-// the adder's three; the Edwards sums of the segments are parked like every other point
-ZK_JFN void hash_walk_forward(const HashWalk &h, const BitStream &bs, fe &run) {
+// the forward walk of one hash: per window the prefix product and the denominator E wait in the window's two slots, (X, Y, Z) in the adder's
+// three; the Edwards sums of the segments are parked like every other point
+ZK_HD void hash_walk_forward(const HashWalk &h, const BitStream &bs, fe &run) {
     const uint32_t W = h.W, lone = h.lone(), n_seg = h.n_seg();
     jpoint hacc, p;
     if (lone) {                                                 // the last base point's single window: its converter is the table point itself
@@ -1105,7 +797,7 @@ ZK_JFN void hash_walk_forward(const HashWalk &h, const BitStream &bs, fe &run) {
 
 // the way back: inv = 1 / (the product up to and including the hash's last denominator) on entry, 1 / (the product before its first) on return.
 // Leaves every window, Montgomery adder and converter of the hash as the front end has it, and x3, y3 of every Edwards adder
-ZK_JFN void hash_walk_back(const HashWalk &h, const BitStream &bs, fe &inv) {
+ZK_HD void hash_walk_back(const HashWalk &h, const BitStream &bs, fe &inv) {
     const uint32_t W = h.W, lone = h.lone(), n_seg = h.n_seg();
 #pragma clang loop unroll(disable)
     for (int sg = (int)n_seg - 1; sg >= 0; sg--) {
@@ -1148,8 +840,8 @@ ZK_JFN void hash_walk_back(const HashWalk &h, const BitStream &bs, fe &inv) {
 }
 
 // the products of the Edwards adders over the converted segments; returns the x of the hash (canonical Montgomery): the last adder's, or the
-// only converter's when the hash has one segment
-ZK_JFN fe hash_walk_close(const HashWalk &h) {
+// only converter's when the hash has one segment (the message hash of a short message; the hash over R, A, M always has three or more)
+ZK_HD fe hash_walk_close(const HashWalk &h) {
     const uint32_t n_conv = h.n_seg() + h.lone();
     const fe *prev = h.conv;
 #pragma clang loop unroll(disable)
@@ -1161,8 +853,75 @@ ZK_JFN fe hash_walk_close(const HashWalk &h) {
     return prev[0];
 }
 
-// mtab / m_mtab: the Montgomery forms of ram_tab / m_tab as k_eddsa_fill_pure takes its mtab.  msgs: msg_len bytes an item.  Malformed items,
-// verdicts and the row's form as k_eddsa_fill
+// mtab: the (u, v) of every entry of ram_tab, as HashWalk takes it.  msgs: msg_len bytes an item.  Malformed items, verdicts and the row's form
+// as k_eddsa_fill
+__global__ void __launch_bounds__(BLOCK)
+k_eddsa_fill_pure(EddsaView v, const fe *__restrict__ fbtab, const fe *__restrict__ mtab, PureLayout L, const fe *__restrict__ A, const fe *__restrict__ R,
+                  const fe *__restrict__ s, const uint8_t *__restrict__ msgs, uint32_t n, fe *d_w, uint64_t row_elems, uint8_t *__restrict__ verdicts) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    fe ax, ay, rx, ry;
+    if (!fill_load_item(A, R, s, g, ax, ay, rx, ry)) { verdicts[g] = 0; return; }
+    const uint32_t *__restrict__ sw = s[g].l;
+    fe *row = d_w + (size_t)g * row_elems;
+    const ChainLayout C = chain_layout(L);
+    BitStream bs;
+    bs.rx = R[2 * (size_t)g].l; bs.ax = A[2 * (size_t)g].l; bs.mx = nullptr; bs.msg = msgs + (size_t)g * L.msg_len; bs.msg_bits = 8 * L.msg_len;
+    HashWalk h;                                                 // the whole stream: bits(R.x) || bits(A.x) || the message bits
+    h.tab = v.ram_tab; h.mtab = mtab; h.W = v.ram_windows; h.bit0 = 0;
+    h.hw = row + L.hash_window_var0; h.madd = row + L.mont_adder_var0; h.conv = row + L.converter_var0; h.ed = row + L.edwards_adder_var0;
+
+    // ---- the inputs and the two decompositions that feed the hash
+    fill_inputs(row, C, ax, ay, rx, ry, sw);
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0; i < bs.msg_bits; i++) row[L.msg_bit0 + i] = bit_fe(bs.bit(2 * FIELD_BITS + i));
+#pragma clang loop unroll(disable)
+    for (uint32_t i = 0; i < 3 * h.W - 2 * FIELD_BITS - bs.msg_bits; i++) row[L.pad_bit0 + i] = Fr::zero();
+    fill_strict_bits(row + L.rx_bit0, row + L.rx_range_var0, bs.rx);
+    fill_strict_bits(row + L.ax_bit0, row + L.ax_range_var0, bs.ax);
+
+    // ---- the first set of chains, projective: validator, fixed base, hash; the first inversion and its way back; t = the hash's x, its bits
+    fe run = Fr::one();
+    fixed_forward(row, C, fbtab, rx, ry, sw, run);
+    hash_walk_forward(h, bs, run);
+    fe inv = jj_inv(run);
+    hash_walk_back(h, bs, inv);
+    fixed_back(row, C, inv);
+    const fe t = jj_from_mont(hash_walk_close(h));
+    fill_strict_bits(row + L.t_bit0, row + L.t_range_var0, t.l);
+
+    // ---- the second set: variable base and R + t A
+    run = Fr::one();
+    jpoint d, p;
+    var_start(row, C, ax, ay, t.l, d, p);
+    var_forward(row, C, t.l, 1, N_STEPS, d, p, run);
+    var_close(row, C, rx, ry, p, run);
+    inv = jj_inv(run);
+    var_back(row, C, 1, N_STEPS, true, inv);
+
+    verdicts[g] = fill_all_products(row, C, rx, ry, t.l);
+}
+
+// ---- the complete witness of the EdDSA circuit of the "hash" scheme (jubjub_gadgets.py, EddsaHashCircuit): the row of k_eddsa_fill_pure with a
+// SECOND in-circuit Pedersen hash in front, M = the hash "EdDSA_Verify.M" of the message bits, whose 254 strict bits are the third part of the
+// input of the hash "EdDSA_Verify.RAM".  HashLayout is zk_eddsa_hash_layout of zkhip.h; the host has checked it as it checks PureLayout.
+//
+// THREE inversions per witness, whatever msg_len.  The message hash joins the product of the validator and of the fixed-base chain, which need
+// nothing from it: the first inversion closes all three and yields M.x.  The RAM hash needs the bits of M.x and yields t (the second
+// inversion); the variable-base chain needs the bits of t (the third).  The message hash may have a single segment (msg_len <= 23: no Edwards
+// adder, M is the converter's point) and, unlike the RAM hash of this circuit, a lone last window (W_m % 62 == 1).  No step has a special case:
+// DESIGN 5m restates the argument of 5k for the table of "EdDSA_Verify.M".
+struct HashLayout {
+    uint32_t msg_len, n_vars, ax_var, msg_bit0, rx_var, s_bit0, validator_var0, window_var0, fixed_adder_var0, rx_bit0, rx_range_var0,
+             ax_bit0, ax_range_var0, hash_window_var0, mont_adder_var0, converter_var0, edwards_adder_var0, t_bit0, t_range_var0, cond0_var,
+             doubler_var0, cond_var0, adder_var0, step_stride, last_adder_var0, m_pad_bit0, m_window_var0, m_mont_adder_var0, m_converter_var0,
+             m_edwards_adder_var0, m_bit0, m_range_var0;
+};
+constexpr uint32_t HASH_RAM_WINDOWS = FIELD_BITS;                // 3 x 254 bits: 254 windows, segments of 62, 62, 62, 62 and 6
+ZK_HD uint32_t hash_msg_windows(uint32_t msg_len) { return (8 * msg_len + 2) / 3; }
+
+// mtab / m_mtab: the (u, v) of every entry of ram_tab / m_tab.  msgs: msg_len bytes an item.  Malformed items, verdicts and the row's form as
+// k_eddsa_fill
 __global__ void __launch_bounds__(BLOCK)
 k_eddsa_fill_hash(EddsaView v, const fe *__restrict__ fbtab, const fe *__restrict__ mtab, const fe *__restrict__ m_mtab, HashLayout L, const fe *__restrict__ A,
                   const fe *__restrict__ R, const fe *__restrict__ s, const uint8_t *__restrict__ msgs, uint32_t n, fe *d_w, uint64_t row_elems,
@@ -1170,12 +929,10 @@ k_eddsa_fill_hash(EddsaView v, const fe *__restrict__ fbtab, const fe *__restric
     const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n) return;
     fe ax, ay, rx, ry;
-    load_point(A, g, ax, ay);
-    load_point(R, g, rx, ry);
+    if (!fill_load_item(A, R, s, g, ax, ay, rx, ry)) { verdicts[g] = 0; return; }
     const uint32_t *__restrict__ sw = s[g].l;
-    if (!on_curve(ax, ay) || !on_curve(rx, ry) || (sw[7] >> 30)) { verdicts[g] = 0; return; }
-    ax = Fr::canon(ax); ay = Fr::canon(ay); rx = Fr::canon(rx); ry = Fr::canon(ry);
     fe *row = d_w + (size_t)g * row_elems;
+    const ChainLayout C = chain_layout(L);
     BitStream bs;
     bs.rx = R[2 * (size_t)g].l; bs.ax = A[2 * (size_t)g].l; bs.mx = nullptr; bs.msg = msgs + (size_t)g * L.msg_len; bs.msg_bits = 8 * L.msg_len;
     HashWalk hm, hr;                                            // the message hash reads the stream from the message on (past its end: the zero padding)
@@ -1185,10 +942,7 @@ k_eddsa_fill_hash(EddsaView v, const fe *__restrict__ fbtab, const fe *__restric
     hr.hw = row + L.hash_window_var0; hr.madd = row + L.mont_adder_var0; hr.conv = row + L.converter_var0; hr.ed = row + L.edwards_adder_var0;
 
     // ---- the inputs and the two decompositions that need nothing else
-    row[0] = Fr::one();
-    row[L.ax_var] = ax; row[L.ax_var + 1] = ay; row[L.rx_var] = rx; row[L.rx_var + 1] = ry;
-#pragma clang loop unroll(disable)
-    for (uint32_t i = 0; i < FIELD_BITS; i++) row[L.s_bit0 + i] = bit_fe(int_bit(sw, i));
+    fill_inputs(row, C, ax, ay, rx, ry, sw);
 #pragma clang loop unroll(disable)
     for (uint32_t i = 0; i < bs.msg_bits; i++) row[L.msg_bit0 + i] = bit_fe(bs.bit(2 * FIELD_BITS + i));
 #pragma clang loop unroll(disable)
@@ -1196,48 +950,14 @@ k_eddsa_fill_hash(EddsaView v, const fe *__restrict__ fbtab, const fe *__restric
     fill_strict_bits(row + L.rx_bit0, row + L.rx_range_var0, bs.rx);
     fill_strict_bits(row + L.ax_bit0, row + L.ax_range_var0, bs.ax);
 
-    // ---- the first set of chains, projective: validator, fixed base, the message hash
+    // ---- the first set of chains, projective: validator, fixed base, the message hash; the first inversion and its way back; M = the message
+    // hash, the strict bits of its x
     fe run = Fr::one();
-    jpoint p;
-    fe *val = row + L.validator_var0;
-    from_affine(p, rx, ry);
-#pragma clang loop unroll(disable)
-    for (uint32_t j = 0; j < 3; j++) { jj_dbl(p, false); park_point(val + DBL_VARS * j, DBL_VARS, p, run); }
-    {
-        const bool nz = !Fr::is_zero(Fr::canon(p.c[0]));
-        const fe x8 = nz ? p.c[0] : Fr::one();
-        val[3 * DBL_VARS] = run; val[3 * DBL_VARS + 1] = x8;
-        run = Fr::lmul(run, x8);
-    }
-    {
-        const fe *e = fbtab + 3 * (size_t)(int_bit(sw, 0) | (int_bit(sw, 1) << 1));
-        row[L.window_var0] = e[0]; row[L.window_var0 + 1] = e[1];
-        from_affine(p, e[0], e[1]);
-#pragma clang loop unroll(disable)
-        for (uint32_t i = 1; i < FB_WINDOWS; i++) {
-            e = fbtab + 3 * ((size_t)4 * i + (int_bit(sw, 2 * i) | (int_bit(sw, 2 * i + 1) << 1)));
-            row[L.window_var0 + 2 * i] = e[0]; row[L.window_var0 + 2 * i + 1] = e[1];
-            jj_add(p, e, true);
-            park_point(row + L.fixed_adder_var0 + ADD_VARS * (size_t)(i - 1), ADD_VARS, p, run);
-        }
-    }
+    fixed_forward(row, C, fbtab, rx, ry, sw, run);
     hash_walk_forward(hm, bs, run);
-
-    // ---- the first inversion and its way back; M = the message hash, the strict bits of its x
     fe inv = jj_inv(run);
     hash_walk_back(hm, bs, inv);
-#pragma clang loop unroll(disable)
-    for (uint32_t i = FB_WINDOWS - 1; i >= 1; i--) unpark_point(row + L.fixed_adder_var0 + ADD_VARS * (size_t)(i - 1), ADD_VARS, inv);
-    {
-        fe *blk8 = val + 2 * DBL_VARS;
-        const bool nz = !Fr::is_zero(Fr::canon(blk8[4]));
-        const fe xi = Fr::lmul(inv, val[3 * DBL_VARS]);
-        inv = Fr::lmul(inv, val[3 * DBL_VARS + 1]);
-        val[3 * DBL_VARS] = bit_fe(nz);
-        val[3 * DBL_VARS + 1] = nz ? Fr::canon(Fr::lmul(blk8[0], xi)) : Fr::zero();
-    }
-#pragma clang loop unroll(disable)
-    for (int j = 2; j >= 0; j--) unpark_point(val + DBL_VARS * j, DBL_VARS, inv);
+    fixed_back(row, C, inv);
     const fe mx = jj_from_mont(hash_walk_close(hm));            // the canonical integer: the third part of the RAM hash's input
     fill_strict_bits(row + L.m_bit0, row + L.m_range_var0, mx.l);
 
@@ -1252,68 +972,14 @@ k_eddsa_fill_hash(EddsaView v, const fe *__restrict__ fbtab, const fe *__restric
 
     // ---- the third set: variable base and R + t A
     run = Fr::one();
-    {
-        jpoint d;
-        from_affine(d, ax, ay);
-        const uint32_t b0 = int_bit(t.l, 0);
-        row[L.cond0_var] = b0 ? ax : Fr::zero(); row[L.cond0_var + 1] = b0 ? ay : Fr::one();
-        from_affine(p, row[L.cond0_var], row[L.cond0_var + 1]);
-#pragma clang loop unroll(disable)
-        for (uint32_t i = 1; i <= N_STEPS; i++) {
-            const size_t off = (size_t)(i - 1) * L.step_stride;
-            jj_dbl(d, true);
-            park_point(row + L.doubler_var0 + off, DBL_VARS, d, run);
-            const bool b = int_bit(t.l, i);
-            fe q[4];
-            q[0] = b ? d.c[0] : Fr::zero(); q[1] = b ? d.c[1] : Fr::one(); q[2] = b ? jj_mul(coef_d(), d.c[2]) : Fr::zero(); q[3] = b ? d.c[3] : Fr::one();
-            jj_add(p, q, false);
-            park_point(row + L.adder_var0 + off, ADD_VARS, p, run);
-        }
-        fe q[3];
-        q[0] = rx; q[1] = ry; q[2] = jj_mul(coef_d(), jj_mul(rx, ry));
-        jj_add(p, q, true);
-        park_point(row + L.last_adder_var0, ADD_VARS, p, run);
-    }
+    jpoint d, p;
+    var_start(row, C, ax, ay, t.l, d, p);
+    var_forward(row, C, t.l, 1, N_STEPS, d, p, run);
+    var_close(row, C, rx, ry, p, run);
     inv = jj_inv(run);
-    unpark_point(row + L.last_adder_var0, ADD_VARS, inv);
-#pragma clang loop unroll(disable)
-    for (uint32_t i = N_STEPS; i >= 1; i--) {
-        const size_t off = (size_t)(i - 1) * L.step_stride;
-        unpark_point(row + L.adder_var0 + off, ADD_VARS, inv);
-        unpark_point(row + L.doubler_var0 + off, DBL_VARS, inv);
-    }
+    var_back(row, C, 1, N_STEPS, true, inv);
 
-    // ---- the products of affine inputs
-    fill_doubler(val, rx, ry);
-    fill_doubler(val + DBL_VARS, val[4], val[5]);
-    fill_doubler(val + 2 * DBL_VARS, val[DBL_VARS + 4], val[DBL_VARS + 5]);
-    val[3 * DBL_VARS + 2] = Fr::canon(jj_mul(rx, rx)); val[3 * DBL_VARS + 3] = Fr::canon(jj_mul(ry, ry));
-    {
-        const fe *prev = row + L.window_var0;
-#pragma clang loop unroll(disable)
-        for (uint32_t i = 0; i + 1 < FB_WINDOWS; i++) {
-            fe *blk = row + L.fixed_adder_var0 + ADD_VARS * (size_t)i;
-            const fe *w = row + L.window_var0 + 2 * (size_t)(i + 1);
-            fill_adder(blk, prev[0], prev[1], w[0], w[1]);
-            prev = blk + ADD_VARS - 2;
-        }
-    }
-    {
-        const fe *dprev = row + L.ax_var, *sprev = row + L.cond0_var;
-#pragma clang loop unroll(disable)
-        for (uint32_t i = 1; i <= N_STEPS; i++) {
-            const size_t off = (size_t)(i - 1) * L.step_stride;
-            fe *dbl = row + L.doubler_var0 + off, *cond = row + L.cond_var0 + off, *add = row + L.adder_var0 + off;
-            fill_doubler(dbl, dprev[0], dprev[1]);
-            const bool b = int_bit(t.l, i);
-            cond[0] = b ? dbl[4] : Fr::zero(); cond[1] = b ? dbl[5] : Fr::one();
-            fill_adder(add, sprev[0], sprev[1], cond[0], cond[1]);
-            dprev = dbl + DBL_VARS - 2; sprev = add + ADD_VARS - 2;
-        }
-        fill_adder(row + L.last_adder_var0, rx, ry, sprev[0], sprev[1]);
-    }
-    const fe *lhs = row + L.fixed_adder_var0 + ADD_VARS * (size_t)(FB_WINDOWS - 2) + ADD_VARS - 2, *rhs = row + L.last_adder_var0 + ADD_VARS - 2;
-    verdicts[g] = Fr::eq(lhs[0], rhs[0]) && Fr::eq(lhs[1], rhs[1]) ? 1 : 0;
+    verdicts[g] = fill_all_products(row, C, rx, ry, t.l);
 }
 
 }  // namespace jubjub

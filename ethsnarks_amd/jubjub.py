@@ -321,12 +321,21 @@ class EdDSAVerifier:
             raise ValueError("lanes per signature: 1, 2 or 4")
         wide = _wide_fill_lib() if lanes != 1 else None
         c = self._circuit_object()
+        if wide is None:
+            return self._fill(self._lib.zk_eddsa_fill_witnesses, EddsaLayout, c.layout, A, sigs, msgs, out=out, row_elems=row_elems, layout=layout)
+        return self._fill(wide.zk_eddsa_fill_witnesses_wide, EddsaLayout, c.layout, A, sigs, msgs, out=out, row_elems=row_elems, layout=layout, extra=(lanes,))
+
+    def _fill(self, entry, layout_type, circuit_layout, A, sigs, msgs, *, out, row_elems, layout, byte_msgs=False, extra=()):
+        """What fill_witnesses, fill_pedersen_witnesses and fill_hash_witnesses share: checks the batch, packs it and calls `entry`, the library's
+        fill of one circuit, with the row layout as a `layout_type` and `extra` behind its arguments.  byte_msgs: a message is msg_len bytes, not msg_len field elements"""
         A, sigs, msgs, n = self._items(A, sigs, msgs)
-        lay = c.layout if layout is None else layout
+        lay = circuit_layout if layout is None else layout
         if row_elems is None:
             row_elems = lay.n_vars + 1
+        if byte_msgs:
+            msgs = [bytes(m) for m in msgs]
         if any(len(m) != self.msg_len for m in msgs):
-            raise ValueError("a message does not have msg_len elements")
+            raise ValueError("a message does not have msg_len %s" % ("bytes" if byte_msgs else "elements"))
         if out is None:
             out = P.DeviceBuffer(32 * int(row_elems) * max(n, 1))
         if isinstance(out, P.DeviceBuffer) and n * int(row_elems) * 32 > out.nbytes:
@@ -335,14 +344,13 @@ class EdDSAVerifier:
         a = _point_limbs(A)
         r = _point_limbs([R for R, _ in sigs])
         s = F.ints_to_limbs([int(v) for _, v in sigs]) if n else np.zeros((0, 4), dtype=np.uint64)
-        m = F.ints_to_limbs([int(v) for msg in msgs for v in msg]) if n else np.zeros((0, 4), dtype=np.uint64)
-        verdicts = np.full(max(n, 1), 255, dtype=np.uint8)
-        if wide is None:
-            P._check(self._lib.zk_eddsa_fill_witnesses(self._h, _ptr(a), _ptr(r), _ptr(s), _ptr(m), n, C.c_void_p(ptr), C.c_uint64(int(row_elems)),
-                                                       C.byref(EddsaLayout(*lay)), _ptr(verdicts)))
+        if byte_msgs:
+            m = np.frombuffer(b"".join(msgs), dtype=np.uint8).copy() if n else np.zeros(1, dtype=np.uint8)
         else:
-            P._check(wide.zk_eddsa_fill_witnesses_wide(self._h, _ptr(a), _ptr(r), _ptr(s), _ptr(m), n, C.c_void_p(ptr), C.c_uint64(int(row_elems)),
-                                                       C.byref(EddsaLayout(*lay)), _ptr(verdicts), lanes))
+            m = F.ints_to_limbs([int(v) for msg in msgs for v in msg]) if n else np.zeros((0, 4), dtype=np.uint64)
+        verdicts = np.full(max(n, 1), 255, dtype=np.uint8)
+        P._check(entry(self._h, _ptr(a), _ptr(r), _ptr(s), _ptr(m), n, C.c_void_p(ptr), C.c_uint64(int(row_elems)), C.byref(layout_type(*lay)),
+                       _ptr(verdicts), *extra))
         return [bool(v) for v in verdicts[:n]], out
 
     def _pedersen_circuit_object(self):
@@ -366,26 +374,8 @@ class EdDSAVerifier:
         s >= 2^254 gets the verdict False and its row is left as it was.  A, sigs, msgs as verify(); the circuit, unlike verify(), refuses an R of
         low order and takes any s below 2^254"""
         c = self._pedersen_circuit_object()
-        A, sigs, msgs, n = self._items(A, sigs, msgs)
-        lay = c.layout if layout is None else layout
-        if row_elems is None:
-            row_elems = lay.n_vars + 1
-        msgs = [bytes(m) for m in msgs]
-        if any(len(m) != self.msg_len for m in msgs):
-            raise ValueError("a message does not have msg_len bytes")
-        if out is None:
-            out = P.DeviceBuffer(32 * int(row_elems) * max(n, 1))
-        if isinstance(out, P.DeviceBuffer) and n * int(row_elems) * 32 > out.nbytes:
-            raise ValueError("the device buffer is smaller than n rows")
-        ptr = out.ptr if isinstance(out, P.DeviceBuffer) else int(out)
-        a = _point_limbs(A)
-        r = _point_limbs([R for R, _ in sigs])
-        s = F.ints_to_limbs([int(v) for _, v in sigs]) if n else np.zeros((0, 4), dtype=np.uint64)
-        m = np.frombuffer(b"".join(msgs), dtype=np.uint8).copy() if n else np.zeros(1, dtype=np.uint8)
-        verdicts = np.full(max(n, 1), 255, dtype=np.uint8)
-        P._check(self._lib.zk_eddsa_fill_pure_witnesses(self._h, _ptr(a), _ptr(r), _ptr(s), _ptr(m), n, C.c_void_p(ptr), C.c_uint64(int(row_elems)),
-                                                        C.byref(EddsaPureLayout(*lay)), _ptr(verdicts)))
-        return [bool(v) for v in verdicts[:n]], out
+        return self._fill(self._lib.zk_eddsa_fill_pure_witnesses, EddsaPureLayout, c.layout, A, sigs, msgs, out=out, row_elems=row_elems, layout=layout,
+                          byte_msgs=True)
 
     def _hash_circuit_object(self):
         if self.scheme != "hash":
@@ -409,26 +399,8 @@ class EdDSAVerifier:
         low order and takes any s below 2^254.  ImportError from a library that was built before this entry point"""
         c = self._hash_circuit_object()
         lib = _hash_fill_lib()
-        A, sigs, msgs, n = self._items(A, sigs, msgs)
-        lay = c.layout if layout is None else layout
-        if row_elems is None:
-            row_elems = lay.n_vars + 1
-        msgs = [bytes(m) for m in msgs]
-        if any(len(m) != self.msg_len for m in msgs):
-            raise ValueError("a message does not have msg_len bytes")
-        if out is None:
-            out = P.DeviceBuffer(32 * int(row_elems) * max(n, 1))
-        if isinstance(out, P.DeviceBuffer) and n * int(row_elems) * 32 > out.nbytes:
-            raise ValueError("the device buffer is smaller than n rows")
-        ptr = out.ptr if isinstance(out, P.DeviceBuffer) else int(out)
-        a = _point_limbs(A)
-        r = _point_limbs([R for R, _ in sigs])
-        s = F.ints_to_limbs([int(v) for _, v in sigs]) if n else np.zeros((0, 4), dtype=np.uint64)
-        m = np.frombuffer(b"".join(msgs), dtype=np.uint8).copy() if n else np.zeros(1, dtype=np.uint8)
-        verdicts = np.full(max(n, 1), 255, dtype=np.uint8)
-        P._check(lib.zk_eddsa_fill_hash_witnesses(self._h, _ptr(a), _ptr(r), _ptr(s), _ptr(m), n, C.c_void_p(ptr), C.c_uint64(int(row_elems)),
-                                                  C.byref(EddsaHashLayout(*lay)), _ptr(verdicts)))
-        return [bool(v) for v in verdicts[:n]], out
+        return self._fill(lib.zk_eddsa_fill_hash_witnesses, EddsaHashLayout, c.layout, A, sigs, msgs, out=out, row_elems=row_elems, layout=layout,
+                          byte_msgs=True)
 
     def verify(self, A, sigs, msgs):
         """A: one public key per signature (or a single point for all); sigs: [(R, s), ..]; msgs: bytes objects (lists of ints for "mimc")"""
