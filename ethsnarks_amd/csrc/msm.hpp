@@ -231,6 +231,7 @@ struct MsmWork {
     template <int Q> int launch_reduce(hipStream_t st, const MsmWork *also);
     const uint32_t *cur_off = nullptr;          // bucket offsets of the sort driving the current reduction
     uint32_t sort_batch = 1;                    // batch of the last enqueue_sort
+    bool sort_staged = true;                    // ... and its pass-1 scatter: k_sort_partition_staged, or the direct k_sort_partition (read by the sort probe only)
     uint32_t sort_kbits = 0;                    // sort-only objects (the shared witness sort): entries carry (window << kbits) | scalar -- set by use_shift_payload()
     void use_shift_payload() { uint32_t k = 1; while ((1ull << k) < table_n) k++; if (((uint64_t)sh.rows() << k) < (1ull << 31)) sort_kbits = k; }
     SortView view() const { SortView v; v.sorted = sorted; v.off = off; v.batch = sort_batch << sh.plog; v.nb = sh.nb * v.batch; v.entries_bound = (uint32_t)((uint64_t)table_n * sh.W * sort_batch); return v; }

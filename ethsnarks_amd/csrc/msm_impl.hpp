@@ -540,7 +540,8 @@ int MsmWork<C>::enqueue_sort(const fe *scalars, const uint32_t *gather, uint32_t
     ZK_LAUNCH_SYNC(k_sort_count<C>, sq.groups, SORT_THREADS, st, scalars, gather, n, batch, stride, canonical, c, W, plog, sq, counts);
     ZK_LAUNCH_SYNC(k_sort_colscan<C>, sq.cb, SORT_THREADS, st, counts, sq.groups, bin_total);
     ZK_LAUNCH_SYNC(k_sort_binscan<C>, 1, SORT_THREADS, st, (const uint32_t *)bin_total, sq.cb, bin_base);
-    if ((uint64_t)sq.per_group * W <= SORT_STAGE)
+    sort_staged = (uint64_t)sq.per_group * W <= SORT_STAGE;
+    if (sort_staged)
         ZK_LAUNCH_SYNC(k_sort_partition_staged<C>, sq.groups, SORT_THREADS, st, scalars, gather, n, batch, stride, canonical, c, W, plog, sq,
                        (const uint32_t *)counts, (const uint32_t *)bin_total, (const uint32_t *)bin_base, pairs, sort_kbits);
     else

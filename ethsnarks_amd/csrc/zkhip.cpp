@@ -2468,6 +2468,42 @@ extern "C" int zk_msm_g2(const uint64_t *bases, const uint64_t *scalars, uint32_
     return msm_host<G2>(bases, scalars, n, c, device, out);
 } ZK_GUARD
 
+// TEST INFRASTRUCTURE: the bucket sort alone, off[] and sorted[] as k_sort_fine left them (include/zkhip.h).  A sort-only MsmWork as the
+// shared witness sort of a context is one (zk_ctx_create: mW): no table, no curve arithmetic.
+extern "C" int zk_msm_sort_probe(const uint64_t *scalars, uint32_t n, uint32_t batch, uint32_t stride, int canonical, uint32_t c, uint32_t plog,
+                                 int shift_payload, int device, uint32_t *off, uint64_t off_cap, uint32_t *sorted, uint64_t sorted_cap, uint32_t info[16]) try {
+    if (!off || !sorted || !info || (n && !scalars)) return fail(ZK_ERR_ARG, "null argument");
+    if (!batch) return fail(ZK_ERR_ARG, "sort probe: batch = 0");
+    if (stride < n) return fail(ZK_ERR_ARG, "sort probe: stride below n");
+    if (plog > 7) return fail(ZK_ERR_ARG, "sort probe: plog above 7");
+    if ((uint64_t)batch * stride >= (1ull << 32)) return fail(ZK_ERR_ARG, "sort probe: batch * stride must stay below 2^32");
+    ZK_TRY(use_device(device));
+    fe *d_scalars = nullptr;
+    MsmWork<G1> work;
+    uint64_t entries = 0;
+    int rc = work.alloc(n, c, nullptr, nullptr, /*sort_only=*/true, batch, plog);
+    const uint64_t nb = ((uint64_t)work.sh.nb * batch) << plog;          // buckets of the whole batch, all planes (enqueue_sort's nb)
+    if (rc == ZK_OK && off_cap < nb + 1) rc = fail(ZK_ERR_ARG, "sort probe: off_cap below nb_total + 1");
+    if (rc == ZK_OK) rc = dev_upload(&d_scalars, (const fe *)scalars, n ? (size_t)(batch - 1) * stride + n : 0);
+    if (rc == ZK_OK && shift_payload) work.use_shift_payload();
+    if (rc == ZK_OK) rc = work.enqueue_sort(d_scalars, nullptr, n, canonical, nullptr, batch, stride);
+    if (rc == ZK_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(ZK_ERR_HIP, "sort kernels failed");
+    if (rc == ZK_OK && hipMemcpy(off, work.off, sizeof(uint32_t) * (nb + 1), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(ZK_ERR_HIP, "sort probe: copying off[] back failed");
+    if (rc == ZK_OK) {
+        SortShape sq = work.ss; sq.resize(n * batch ? n * batch : 1, (uint32_t)nb);      // the shape enqueue_sort launched with
+        entries = off[nb];
+        const uint32_t v[16] = {work.sh.c, work.sh.W, (uint32_t)nb, sq.cb, sq.fb, sq.fine_bits, sq.groups, sq.per_group, work.sort_kbits,
+                                work.sort_staged ? 1u : 0u, (uint32_t)entries, 0, 0, 0, 0, 0};
+        memcpy(info, v, sizeof(v));
+        if (entries > work.sh.max_entries() * batch) rc = fail(ZK_ERR_INTERNAL, "sort probe: off[nb_total] exceeds n * W * batch");   // nothing past the allocation is read back
+        else if (entries > sorted_cap) rc = fail(ZK_ERR_ARG, "sort probe: sorted_cap below off[nb_total] (info[10])");
+    }
+    if (rc == ZK_OK && entries && hipMemcpy(sorted, work.sorted, sizeof(uint32_t) * entries, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(ZK_ERR_HIP, "sort probe: copying sorted[] back failed");
+    work.release();
+    if (d_scalars) hipFree(d_scalars);
+    return rc;
+} ZK_GUARD
+
 // host-only: Fr elements between the canonical and the Montgomery (libff::Fp_model) representation, in place
 extern "C" int zk_fr_convert(uint64_t *io, uint32_t n, int to_montgomery) try {
     if (n && !io) return fail(ZK_ERR_ARG, "null argument");

@@ -68,7 +68,7 @@ EXPORTS = [
     "zk_wplan_create", "zk_wplan_create_hinted", "zk_wplan_create_wide", "zk_wplan_info", "zk_wplan_solve", "zk_wplan_free", "zk_wplan_probe_program", "zk_dev_alloc", "zk_dev_free", "zk_dev_upload", "zk_dev_download",
     "zk_chain_submit", "zk_chain_device", "zk_h_from_chains_submit", "zk_h_device", "zk_chain_wait", "zk_prove_submit_with_h", "zk_prove_submit_defer_h", "zk_prove_submit_h", "zk_prove_abort",
     "zk_prove_submit_pinned", "zk_prove_batch_submit_pinned", "zk_host_alloc", "zk_host_free", "zk_host_register", "zk_host_unregister",
-    "zk_prove_submit_resident", "zk_prove_stage", "zk_prove_stage_pinned", "zk_prove_submit_staged", "zk_ctx_info", "zk_ctx_table_info", "zk_ctx_hlagrange_info", "zk_hl_probe_dft", "zk_hl_probe_columns", "zk_ctx_probe_rows", "zk_ctx_partials_device", "zk_prove_collect_device", "zk_prove_combine_device", "zk_launch_count", "zk_profile_begin", "zk_profile_end", "zk_device_info", "zk_device_pci_bus_id",
+    "zk_prove_submit_resident", "zk_prove_stage", "zk_prove_stage_pinned", "zk_prove_submit_staged", "zk_ctx_info", "zk_ctx_table_info", "zk_ctx_hlagrange_info", "zk_hl_probe_dft", "zk_hl_probe_columns", "zk_ctx_probe_rows", "zk_msm_sort_probe", "zk_ctx_partials_device", "zk_prove_collect_device", "zk_prove_combine_device", "zk_launch_count", "zk_profile_begin", "zk_profile_end", "zk_device_info", "zk_device_pci_bus_id",
     "zk_verify",
     "zk_vctx_create", "zk_vctx_destroy", "zk_verify_batch", "zk_verify_batch_json", "zk_pairing_check", "zk_pairing_tower_op",
     "zk_mtree_create", "zk_mtree_free", "zk_mtree_size", "zk_mtree_append", "zk_mtree_append_resident", "zk_mtree_update", "zk_mtree_root", "zk_mtree_node",
@@ -943,6 +943,29 @@ def msm(bases, scalars, g2=False, c=0, device=0):
     fn = lib.zk_msm_g2 if g2 else lib.zk_msm_g1
     _check(fn(_p64(bases) if n else None, _p64(scalars) if n else None, C.c_uint32(n), C.c_uint32(c), device, _p64(out)))
     return out
+
+
+SORT_INFO = ("c", "W", "nb_total", "cb", "fb", "fine_bits", "groups", "per_group", "sort_kbits", "staged", "entries")    # include/zkhip.h
+
+
+def msm_sort_probe(scalars, n=None, c=0, plog=0, shift_payload=False, canonical=False, device=0):
+    """zk_msm_sort_probe (test infrastructure): the bucket sort of an MSM alone.  scalars: (batch, stride, 4) or (stride, 4) u64 limbs, of
+    which every proof's first n (default: stride) are sorted.  Returns (off [nb_total + 1], sorted [off[nb_total]], info dict of SORT_INFO):
+    the bucket offsets and entries as the sort kernels left them, and the window and sort shape the library used."""
+    lib = load_library(_lib_path_loaded)
+    s = _c64(scalars)
+    s = s.reshape((1,) + s.shape) if s.ndim == 2 else s
+    batch, stride = s.shape[0], s.shape[1]
+    n = stride if n is None else n
+    info = np.zeros(16, dtype=np.uint32)
+    cc = max(2, min(20, c)) if c else 0                                   # c = 0: the library picks one of 2 .. 17
+    W = 254 // cc + 1 if cc else 128
+    off = np.zeros(min(batch << plog << ((cc or 17) - 1), 1 << 20) + 1, dtype=np.uint32)    # (above 2^20 buckets the library refuses)
+    out = np.zeros(max(n * batch * W, 1), dtype=np.uint32)
+    _check(lib.zk_msm_sort_probe(_p64(s) if s.size else None, C.c_uint32(n), C.c_uint32(batch), C.c_uint32(stride), int(canonical), C.c_uint32(c),
+                                 C.c_uint32(plog), int(shift_payload), device, _p32(off), C.c_uint64(off.size), _p32(out), C.c_uint64(out.size), _p32(info)))
+    d = dict(zip(SORT_INFO, (int(v) for v in info)))
+    return off[:d["nb_total"] + 1], out[:d["entries"]], d
 
 
 def field_mul(a, b, field="fr", device=0):

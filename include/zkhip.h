@@ -312,6 +312,22 @@ int zk_hl_probe_columns(const zk_csr *C, uint32_t nIn, uint32_t V, const uint64_
  * input-consistency rows and the padding) included.  ZK_ERR_ARG: a proof is in flight, k = 0, k > zk_config.max_batch.  (A new function
  * WITHOUT an ABI bump: detected by its symbol.) */
 int zk_ctx_probe_rows(zk_ctx *ctx, const uint64_t *witnesses, uint32_t k, int canonical, uint64_t *out /* 3 x k x m x 4 */);
+/* sort probe: TEST INFRASTRUCTURE.  The bucket sort in front of every multi-exponentiation, alone: a sort-only work object (no table, no
+ * curve arithmetic) sized for exactly this call, one sort of `batch` scalar vectors of n elements each (proof p reads
+ * scalars[(p * stride + i) * 4 ..], stride >= n; Montgomery unless canonical), and what the last sort kernel left.
+ *   c: window bits, 0 = the library's choice for (n, batch), clamped to 2 .. 20;  plog: 2^plog bucket planes (frugal tables), <= 7;
+ *   shift_payload != 0: entries carry (row << kbits) | i as the shared witness sort of a context does, else row * n + i; the sign is bit 31.
+ *   off[0 .. nb_total]: entries before each bucket, nb_total = batch * 2^plog * 2^(c-1); bucket id = ((p << plog) | (w mod 2^plog)) * 2^(c-1)
+ *                       + |digit| - 1 for window w of proof p, row = w >> plog.  off_cap (in words) must be >= nb_total + 1.
+ *   sorted[0 .. off[nb_total]): the entries, bucket after bucket; the order INSIDE a bucket is not defined.
+ *   info = {c, W, nb_total, cb, fb, fine_bits, groups, per_group, kbits (0: row * n + i), 1 if the staged partition ran / 0 the direct
+ *           scatter, off[nb_total], 0 ...}: the window and sort shape actually used (ZK_SORT_PER_GROUP in the environment is read as the
+ *           proving path reads it).
+ * ZK_ERR_ARG: a null pointer (scalars may be null for n = 0), batch = 0, stride < n, plog > 7, more than 2^20 buckets ("batch too large"),
+ * off_cap too small, sorted_cap (in words) below off[nb_total] -- info is filled in that case, sorted is not written.  (A new function
+ * WITHOUT an ABI bump: detected by its symbol.) */
+int zk_msm_sort_probe(const uint64_t *scalars, uint32_t n, uint32_t batch, uint32_t stride, int canonical, uint32_t c, uint32_t plog,
+                      int shift_payload, int device, uint32_t *off, uint64_t off_cap, uint32_t *sorted, uint64_t sorted_cap, uint32_t info[16]);
 
 /* inputs: nIn Fr elements = witness[1..nIn] (Montgomery unless canonical); returns the JSON length
  * (excluding NUL) through *len; ZK_ERR_BUFFER if cap is too small (len still set) */
