@@ -5,13 +5,17 @@
 // bulk build costs (large levels + 1) hashing launches and a single append exactly one.  An update works the same way from the sorted,
 // de-duplicated parent lists the host derives from the indices (k x depth integers).  ZK_MTREE_NO_TAIL=1 in the environment at creation makes
 // a tree launch every level on its own instead: the form the tail kernel is measured against (profiles/merkle_tree.txt).
+// zk_mtree_update_seq (ordered updates with transition witnesses) has the same split at k = TAIL_BLOCK updates: up to there ONE k_mtree_useq_tail
+// launch walks every level, above (or with ZK_MTREE_NO_TAIL) every level is a k_mtree_useq_level launch; then the two witness launches and the commit.
 // A tree over the Poseidon hasher (zk_mtree_create_ex; node width 2, 3 or 4) has the same launch structure with the k_poseidon_merkle_* kernels.
 #include <algorithm>
 #include <memory>
 #include <mutex>
 #include <vector>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <time.h>
 #include "bn254.hpp"
 #include "merkle.hpp"
 #include "poseidon.hpp"
@@ -459,6 +463,128 @@ extern "C" int zk_mtree_fill_full_witnesses(const zk_mtree *ct, const uint64_t *
     else ZK_LAUNCH(k_mtree_fill_levels<false>, zk_div_up((uint64_t)k * D, LEVEL_BLOCK), LEVEL_BLOCK, t->st, v, d_idx, k, (fe *)d_w, row_elems, level_var0, level_stride);
     ZK_HIP(hipGetLastError());
     ZK_HIP(hipStreamSynchronize(t->st));
+    return ZK_OK;
+} ZK_GUARD
+
+// ---- ordered updates with transition witnesses (kernels and notation: merkle.hpp, "ordered leaf updates")
+static_assert(sizeof(zk_mtree_update_layout) == sizeof(UpdateLayout), "zk_mtree_update_layout and merkle::UpdateLayout are one struct");
+
+namespace {
+// node -> the last update seen on it, for one level at a time: open addressing over 2^b >= 2 k slots, emptied between levels
+struct LastSeen {
+    std::vector<uint64_t> key;
+    std::vector<int32_t> val;
+    uint32_t shift = 63;
+    explicit LastSeen(uint32_t k) { size_t n = 2; while (n < 2 * (size_t)k) { n *= 2; shift--; } key.resize(n); val.resize(n); }
+    void clear() { std::fill(val.begin(), val.end(), -1); }
+    int32_t &at(uint64_t node) {                                // the slot of `node`: -1 while no update has touched it
+        size_t h = (size_t)((node * 0x9E3779B97F4A7C15ull) >> shift);
+        while (val[h] >= 0 && key[h] != node) h = (h + 1) & (key.size() - 1);
+        key[h] = node;
+        return val[h];
+    }
+};
+
+// one ordered pass per level, O(k D): pred_same / pred_sib (D x k) and last ((D + 1) x k) of merkle::UpdateSeq
+void useq_predecessors(const uint64_t *indices, uint32_t k, uint32_t D, int32_t *pred_same, int32_t *pred_sib, uint8_t *last) {
+    LastSeen seen(k);
+    for (uint32_t d = 0; d <= D; d++) {
+        seen.clear();
+        for (uint32_t j = 0; j < k; j++) {
+            const uint64_t node = indices[j] >> d;
+            const int32_t sib = seen.at(node ^ 1);
+            int32_t &same = seen.at(node);
+            if (d < D) { pred_same[(size_t)d * k + j] = same; pred_sib[(size_t)d * k + j] = sib; }
+            if (same >= 0) last[(size_t)d * k + same] = 0;
+            last[(size_t)d * k + j] = 1;
+            same = (int32_t)j;
+        }
+    }
+}
+
+double ms_since(const struct timespec &t0) {
+    struct timespec t1;
+    clock_gettime(CLOCK_MONOTONIC, &t1);
+    return 1e3 * (double)(t1.tv_sec - t0.tv_sec) + 1e-6 * (double)(t1.tv_nsec - t0.tv_nsec);
+}
+}  // namespace
+
+extern "C" int zk_mtree_update_seq(zk_mtree *t, const uint64_t *indices, const uint64_t *leaves, uint32_t k, int canonical, void *d_w, uint64_t row_elems,
+                                   const zk_mtree_update_layout *layout, uint32_t level_var0, uint32_t level_stride, uint64_t *roots_canon) try {
+    if (!t || (k && (!indices || !leaves)) || (d_w && !layout)) return mfail(ZK_ERR_ARG, "null argument");
+    if (t->width != 2) return mfail(ZK_ERR_ARG, "the update circuit exists for node width 2 only (there is no wide path selector)");
+    if (t->n == 0) return mfail(ZK_ERR_ARG, "the tree is empty: it has no root and no leaf to update");
+    if (k > 0x7fffffffu) return mfail(ZK_ERR_ARG, "more than 2^31 - 1 updates in one call");
+    const uint32_t D = t->depth;
+    for (uint32_t i = 0; i < k; i++) if (indices[i] >= t->n) return mfail(ZK_ERR_ARG, "leaf index is not below the size of the tree");
+    if (!all_below_modulus(leaves, k)) return mfail(ZK_ERR_ARG, "a leaf is not below the Fr modulus");
+    UpdateLayout L = {};
+    if (d_w) {
+        memcpy(&L, layout, sizeof(L));
+        if (t->is_poseidon() && L.n_iv != 0) return mfail(ZK_ERR_ARG, "the Poseidon update circuit has no IV variables: layout.n_iv must be 0");
+        if (!t->is_poseidon() && L.n_iv < D) return mfail(ZK_ERR_ARG, "a complete MiMC witness reads the level IVs: layout.n_iv must be at least the depth");
+        if (L.n_iv > MAX_DEPTH || row_elems == 0 || L.old_root_var >= row_elems || L.new_root_var >= row_elems || L.old_leaf_var >= row_elems || L.new_leaf_var >= row_elems ||
+            (uint64_t)L.addr_var0 + D > row_elems || (uint64_t)L.path_var0 + D > row_elems || (uint64_t)L.iv_var0 + L.n_iv > row_elems)
+            return mfail(ZK_ERR_ARG, "the layout names a variable outside the witness row");
+        if (level_stride < (t->is_poseidon() ? POSEIDON_LEVEL_VARS : MIMC_LEVEL_VARS))
+            return mfail(ZK_ERR_ARG, "level_stride is below the variables of one level: 322 (Poseidon) or 736 (MiMC)");
+        const uint64_t lv0 = level_var0, lv1 = lv0 + 2 * (uint64_t)D * level_stride;       // the level blocks of both chains: [lv0, lv1)
+        if (lv1 > row_elems) return mfail(ZK_ERR_ARG, "the level blocks leave the witness row: level_var0 + 2 * depth * level_stride > row_elems");
+        const auto hits = [&](uint64_t v0, uint64_t n) { return n && v0 < lv1 && v0 + n > lv0; };
+        if (hits(0, 1) || hits(L.old_root_var, 1) || hits(L.new_root_var, 1) || hits(L.old_leaf_var, 1) || hits(L.new_leaf_var, 1) || hits(L.addr_var0, D) ||
+            hits(L.path_var0, D) || hits(L.iv_var0, L.n_iv))
+            return mfail(ZK_ERR_ARG, "the level blocks overlap an input variable of the layout");
+    }
+    if (k == 0) return roots_canon ? zk_mtree_root(t, roots_canon) : ZK_OK;
+    // host: the predecessor tables and the new leaves in Montgomery form.  MEASUREMENT ONLY: ZK_MTREE_USEQ_TIMING=1 in the environment makes the
+    // call report the time of the predecessor pass on stderr (tools/merkle_update_bench.py reads it); otherwise no clock is read
+    const char *e_timing = getenv("ZK_MTREE_USEQ_TIMING");
+    const bool timing = e_timing && e_timing[0] == '1';
+    struct timespec t_pred = {};
+    if (timing) clock_gettime(CLOCK_MONOTONIC, &t_pred);
+    std::vector<int32_t> pred(2 * (size_t)D * k);
+    std::vector<uint8_t> last((size_t)(D + 1) * k);
+    useq_predecessors(indices, k, D, pred.data(), pred.data() + (size_t)D * k, last.data());
+    if (timing) fprintf(stderr, "zk_mtree_update_seq: k = %u, host predecessor pass %.4f ms\n", k, ms_since(t_pred));
+    std::vector<fe> vals(k);
+    for (uint32_t i = 0; i < k; i++) { fe v; memcpy(v.l, leaves + 4 * (size_t)i, 32); vals[i] = canonical ? Fr::to_mont(v) : v; }
+    ZK_TRY(mt_use_device(t->device));
+    // scratch: idx | pred_same | pred_sib | last | nodes
+    const auto up32 = [](size_t o) { return (o + 31) & ~(size_t)31; };
+    const size_t o_pred = sizeof(uint64_t) * (size_t)k, o_last = o_pred + sizeof(int32_t) * pred.size(), o_nodes = up32(o_last + last.size());
+    ZK_TRY(mt_scratch(t, o_nodes + sizeof(fe) * (size_t)(D + 1) * k));
+    char *s = (char *)t->d_scratch;
+    UpdateSeq u;
+    u.idx = (const uint64_t *)s; u.pred_same = (const int32_t *)(s + o_pred); u.pred_sib = u.pred_same + (size_t)D * k;
+    u.last = (const uint8_t *)(s + o_last); u.nodes = (fe *)(s + o_nodes); u.k = k;
+    ZK_HIP(hipMemcpyAsync(s, indices, sizeof(uint64_t) * (size_t)k, hipMemcpyHostToDevice, t->st));
+    ZK_HIP(hipMemcpyAsync(s + o_pred, pred.data(), sizeof(int32_t) * pred.size(), hipMemcpyHostToDevice, t->st));
+    ZK_HIP(hipMemcpyAsync(s + o_last, last.data(), last.size(), hipMemcpyHostToDevice, t->st));
+    ZK_HIP(hipMemcpyAsync(u.nodes, vals.data(), sizeof(fe) * (size_t)k, hipMemcpyHostToDevice, t->st));
+    std::vector<fe> roots(roots_canon ? (size_t)k + 1 : 0);
+    if (roots_canon) ZK_HIP(hipMemcpyAsync(roots.data(), t->lvl[D], sizeof(fe), hipMemcpyDeviceToHost, t->st));     // (queued before the commit)
+    const TreeView v = t->view();
+    const bool pos = t->is_poseidon();
+    // phase 1: D dependent steps
+    if (t->use_tail && k <= TAIL_BLOCK) {
+        if (pos) ZK_LAUNCH_SYNC(k_mtree_useq_tail<true>, 1, TAIL_BLOCK, t->st, v, u);
+        else ZK_LAUNCH_SYNC(k_mtree_useq_tail<false>, 1, TAIL_BLOCK, t->st, v, u);
+    } else for (uint32_t d = 0; d < D; d++) {
+        if (pos) ZK_LAUNCH(k_mtree_useq_level<true>, zk_div_up(k, LEVEL_BLOCK), LEVEL_BLOCK, t->st, v, u, d);
+        else ZK_LAUNCH(k_mtree_useq_level<false>, zk_div_up(k, LEVEL_BLOCK), LEVEL_BLOCK, t->st, v, u, d);
+    }
+    // phase 2: the witness rows
+    if (d_w) {
+        ZK_LAUNCH(k_mtree_useq_fill_inputs, zk_div_up((uint64_t)k * (5 + 2 * D + L.n_iv), LEVEL_BLOCK), LEVEL_BLOCK, t->st, v, u, (fe *)d_w, row_elems, L);
+        if (pos) ZK_LAUNCH(k_mtree_useq_fill_levels<true>, zk_div_up((uint64_t)k * D * 2, LEVEL_BLOCK), LEVEL_BLOCK, t->st, v, u, (fe *)d_w, row_elems, level_var0, level_stride);
+        else ZK_LAUNCH(k_mtree_useq_fill_levels<false>, zk_div_up((uint64_t)k * D * 2, LEVEL_BLOCK), LEVEL_BLOCK, t->st, v, u, (fe *)d_w, row_elems, level_var0, level_stride);
+    }
+    // phase 3: the only writes to the tree
+    ZK_LAUNCH(k_mtree_useq_commit, zk_div_up((uint64_t)k * (D + 1), LEVEL_BLOCK), LEVEL_BLOCK, t->st, v, u);
+    ZK_HIP(hipGetLastError());
+    if (roots_canon) ZK_HIP(hipMemcpyAsync(roots.data() + 1, u.nodes + (size_t)D * k, sizeof(fe) * (size_t)k, hipMemcpyDeviceToHost, t->st));
+    ZK_HIP(hipStreamSynchronize(t->st));                        // (the staging vectors live until here)
+    for (size_t i = 0; i < roots.size(); i++) { const fe r = Fr::from_mont(roots[i]); memcpy(roots_canon + 4 * i, r.l, 32); }
     return ZK_OK;
 } ZK_GUARD
 

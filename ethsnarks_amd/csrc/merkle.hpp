@@ -20,6 +20,9 @@
 //   k_mtree_gather        leaves and authentication paths of k indices (canonical, for the host)
 //   k_mtree_fill_witness  the membership circuit's inputs of k indices, straight into k rows of a device witness buffer
 //   k_mtree_fill_levels   the rest of that row: one lane per (row, level) writes the level's selector and hash variables (both hashers)
+//   k_mtree_useq_*        ordered leaf updates, each seen by its successors, with the witnesses of the update circuit (both hashers): the k
+//                         chains advance one level per step (_tail: every level in one workgroup, _level: one launch per level), then one lane
+//                         per (row, level, side) traces the old and the new chain (_fill_inputs, _fill_levels), then _commit writes the tree
 //   k_mimc_hash2          n independent two-block hashes (test entry point)
 //
 // The same tree over the Poseidon hasher (MerkleHasher_Poseidon, merkletree.py:63-78; the permutation is poseidon.hpp) has node widths
@@ -247,6 +250,25 @@ ZK_HD fe mimc_cipher_traced(const fe *__restrict__ rc, const fe &x0, const fe &k
     return x;
 }
 
+// the variables of one level at o[0 .. 321 / 735]: the selector of own node x and sibling p under the address bit, then the hash of (left, right)
+template <bool POSEIDON>
+ZK_D void trace_level(const TreeView &t, uint32_t d, bool bit, const fe &x, const fe &p, fe *__restrict__ o) {
+    fe left, right;
+    store_selector(o, bit, x, p, left, right);
+    o += SELECTOR_VARS;
+    if constexpr (POSEIDON) {
+        fe s[poseidon::T] = {left, right, Fr::zero(), Fr::zero(), Fr::zero(), Fr::zero()};
+        poseidon::permute_traced<poseidon::POSEIDON_MIX_DOT6>(t.pc, s, o);
+        o[3 * poseidon::N_SBOX] = Fr::canon(s[0]);
+    } else {
+        const fe iv = t.iv[d];
+        const fe k1 = Fr::ladd(Fr::ladd(iv, mimc_cipher_traced(t.rc, left, iv, o + 2)), left);
+        o[0] = Fr::canon(k1);
+        const fe k2 = Fr::ladd(Fr::ladd(k1, mimc_cipher_traced(t.rc, right, k1, o + 2 + 4 * MIMC_ROUNDS)), right);
+        o[1] = Fr::canon(k2);
+    }
+}
+
 template <bool POSEIDON>
 __global__ void __launch_bounds__(LEVEL_BLOCK)
 k_mtree_fill_levels(TreeView t, const uint64_t *__restrict__ idx, uint32_t k, fe *__restrict__ w, uint64_t row_elems, uint32_t level_var0, uint32_t level_stride) {
@@ -255,21 +277,110 @@ k_mtree_fill_levels(TreeView t, const uint64_t *__restrict__ idx, uint32_t k, fe
     if (g >= (uint64_t)k * D) return;
     const uint32_t i = (uint32_t)(g / D), d = (uint32_t)(g % D);
     const uint64_t ad = idx[i] >> d;                             // the own node on level d
-    fe *__restrict__ o = w + (size_t)i * row_elems + level_var0 + (size_t)d * level_stride;
-    fe left, right;
-    store_selector(o, ad & 1, t.lvl[d][ad], node_or_placeholder(t, d, ad ^ 1), left, right);
-    o += SELECTOR_VARS;
+    trace_level<POSEIDON>(t, d, ad & 1, t.lvl[d][ad], node_or_placeholder(t, d, ad ^ 1), w + (size_t)i * row_elems + level_var0 + (size_t)d * level_stride);
+}
+
+// ---- ordered leaf updates with transition witnesses (zk_mtree_update_seq).  Update j of k replaces leaf a_j and is seen by every later update.
+// With n(d, j) = a_j >> d:  N[d][j] = node n(d, j) after update j (N[0][j] = the new leaf), S[d][j] = its sibling as update j sees it,
+// O[d][j] = the own node before update j.  S[d][j] = N[d][i] for the largest i < j with n(d, i) = n(d, j) ^ 1, O[d][j] likewise with
+// n(d, i) = n(d, j); without such an i they are what the tree holds.  N[d + 1][j] = H(N[d][j], S[d][j]) ordered by the address bit: level d + 1
+// needs level d of EVERY update and nothing else, so the k chains advance together and the call costs D dependent hashes, not k D.
+// The host finds the predecessors (UpdateSeq::pred_same, pred_sib: i or -1; last: update j is the last that touches n(d, j)); nodes is the
+// (D + 1) x k scratch N, level major.  Only k_mtree_useq_commit writes the tree.
+struct UpdateSeq {
+    const uint64_t *idx;                                        // k leaf indices
+    const int32_t *pred_same, *pred_sib;                        // D x k
+    const uint8_t *last;                                        // (D + 1) x k
+    fe *nodes;                                                  // (D + 1) x k, row 0 = the new leaves (Montgomery)
+    uint32_t k;
+};
+ZK_D fe useq_sibling(const TreeView &t, const UpdateSeq &u, uint32_t d, uint32_t j) {
+    const int32_t i = u.pred_sib[(size_t)d * u.k + j];
+    return i >= 0 ? u.nodes[(size_t)d * u.k + i] : node_or_placeholder(t, d, (u.idx[j] >> d) ^ 1);
+}
+ZK_D fe useq_own_before(const TreeView &t, const UpdateSeq &u, uint32_t d, uint32_t j) {
+    const int32_t i = u.pred_same[(size_t)d * u.k + j];
+    return i >= 0 ? u.nodes[(size_t)d * u.k + i] : t.lvl[d][u.idx[j] >> d];
+}
+template <bool POSEIDON>
+ZK_D void useq_step(const TreeView &t, const UpdateSeq &u, uint32_t d, uint32_t j) {
+    const bool bit = (u.idx[j] >> d) & 1;
+    const fe x = u.nodes[(size_t)d * u.k + j], p = useq_sibling(t, u, d, j);
+    const fe l = select(bit, p, x), r = select(bit, x, p);
+    fe out;
     if constexpr (POSEIDON) {
-        fe x[poseidon::T] = {left, right, Fr::zero(), Fr::zero(), Fr::zero(), Fr::zero()};
-        poseidon::permute_traced<poseidon::POSEIDON_MIX_DOT6>(t.pc, x, o);
-        o[3 * poseidon::N_SBOX] = Fr::canon(x[0]);
-    } else {
-        const fe iv = t.iv[d];
-        const fe k1 = Fr::ladd(Fr::ladd(iv, mimc_cipher_traced(t.rc, left, iv, o + 2)), left);
-        o[0] = Fr::canon(k1);
-        const fe k2 = Fr::ladd(Fr::ladd(k1, mimc_cipher_traced(t.rc, right, k1, o + 2 + 4 * MIMC_ROUNDS)), right);
-        o[1] = Fr::canon(k2);
+        fe s[poseidon::T] = {l, r, Fr::zero(), Fr::zero(), Fr::zero(), Fr::zero()};
+        poseidon::permute<poseidon::POSEIDON_MIX_DOT6>(t.pc, s);
+        out = Fr::canon(s[0]);
+    } else out = mimc_hash2(t.rc, l, r, t.iv[d]);
+    u.nodes[(size_t)(d + 1) * u.k + j] = out;
+}
+
+// phase 1, k > TAIL_BLOCK: one launch per level, one lane per update
+template <bool POSEIDON>
+__global__ void __launch_bounds__(LEVEL_BLOCK)
+k_mtree_useq_level(TreeView t, UpdateSeq u, uint32_t d) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < u.k) useq_step<POSEIDON>(t, u, d, j);
+}
+
+// phase 1, k <= TAIL_BLOCK: every level in ONE workgroup, as k_mimc_merkle_tail; the barrier makes level d + 1 of every update visible
+template <bool POSEIDON>
+__global__ void __launch_bounds__(TAIL_BLOCK)
+k_mtree_useq_tail(TreeView t, UpdateSeq u) {
+    for (uint32_t d = 0; d < t.depth; d++) {
+        if (threadIdx.x < u.k) useq_step<POSEIDON>(t, u, d, threadIdx.x);
+        __syncthreads();
     }
+}
+
+// where the update circuit keeps its inputs in a witness row (zk_mtree_update_layout of include/zkhip.h)
+struct UpdateLayout { uint32_t old_root_var, new_root_var, addr_var0, path_var0, old_leaf_var, new_leaf_var, iv_var0, n_iv; };
+
+// phase 2a, one lane per (row, slot): ONE, the two roots, depth address bits, depth path elements, the two leaves, n_iv IVs
+__global__ void __launch_bounds__(LEVEL_BLOCK)
+k_mtree_useq_fill_inputs(TreeView t, UpdateSeq u, fe *__restrict__ w, uint64_t row_elems, UpdateLayout L) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t D = t.depth, S = 5 + 2 * D + L.n_iv;
+    if (g >= (uint64_t)u.k * S) return;
+    const uint32_t j = (uint32_t)(g / S);
+    uint32_t s = (uint32_t)(g % S);
+    fe *__restrict__ row = w + (size_t)j * row_elems;
+    if (s == 0) { row[0] = Fr::one(); return; }
+    if (s == 1) { row[L.old_root_var] = j ? u.nodes[(size_t)D * u.k + (j - 1)] : t.lvl[D][0]; return; }
+    if (s == 2) { row[L.new_root_var] = u.nodes[(size_t)D * u.k + j]; return; }
+    s -= 3;
+    if (s < D) { row[L.addr_var0 + s] = ((u.idx[j] >> s) & 1) ? Fr::one() : Fr::zero(); return; }
+    s -= D;
+    if (s < D) { row[L.path_var0 + s] = useq_sibling(t, u, s, j); return; }
+    s -= D;
+    if (s == 0) { row[L.old_leaf_var] = useq_own_before(t, u, 0, j); return; }
+    if (s == 1) { row[L.new_leaf_var] = u.nodes[j]; return; }
+    row[L.iv_var0 + (s - 2)] = t.iv[s - 2];
+}
+
+// phase 2b, one lane per (row, level, side): the level's variables of the old chain (own node O[d][j]) at level_var0 + d level_stride, of the
+// new chain (own node N[d][j]) at level_var0 + (D + d) level_stride; both over the sibling S[d][j].  No lane waits for another
+template <bool POSEIDON>
+__global__ void __launch_bounds__(LEVEL_BLOCK)
+k_mtree_useq_fill_levels(TreeView t, UpdateSeq u, fe *__restrict__ w, uint64_t row_elems, uint32_t level_var0, uint32_t level_stride) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t D = t.depth;
+    if (g >= (uint64_t)u.k * D * 2) return;
+    const uint32_t j = (uint32_t)(g / (2 * D)), d = (uint32_t)(g % (2 * D)) >> 1;
+    const bool is_new = g & 1;
+    const fe x = is_new ? u.nodes[(size_t)d * u.k + j] : useq_own_before(t, u, d, j);
+    trace_level<POSEIDON>(t, d, (u.idx[j] >> d) & 1, x, useq_sibling(t, u, d, j),
+                          w + (size_t)j * row_elems + level_var0 + (size_t)((is_new ? D : 0) + d) * level_stride);
+}
+
+// phase 3, one lane per (update, level 0 .. D): the last update that touches a node stores it
+__global__ void __launch_bounds__(LEVEL_BLOCK)
+k_mtree_useq_commit(TreeView t, UpdateSeq u) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= (uint64_t)u.k * (t.depth + 1)) return;
+    const uint32_t d = (uint32_t)(g / u.k), j = (uint32_t)(g % u.k);
+    if (u.last[g]) t.lvl[d][u.idx[j] >> d] = u.nodes[g];
 }
 
 // out[i] = mimc_hash([l[i], r[i]], iv[i]); canonical in and out (the host has checked the operands against r)

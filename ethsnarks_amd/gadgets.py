@@ -619,6 +619,92 @@ def poseidon_membership_circuit(depth=29, leaf=None, address=0, path=None):
     return r1cs, w, root
 
 
+# ----------------------------------------------------------------------------- the update circuit
+class MerklePathCompute:
+    """markle_path_compute<MiMC_e7_hash_gadget>, src/gadgets/merkle_tree.hpp:16-68: the selector and hasher of every level and result(), the
+    root the leaf and path lead to -- no closing constraint, so nothing is authenticated"""
+
+    def __init__(self, pb, depth, address_bits, ivs, leaf, path):
+        assert depth > 0 and len(address_bits) == depth and len(ivs) >= depth
+        self.pb = pb
+        self.selectors, self.hashers = [], []
+        for i in range(depth):
+            inp = leaf if i == 0 else self.hashers[i - 1].result()
+            sel = MerklePathSelector(pb, inp, path[i], address_bits[i])
+            self.selectors.append(sel)
+            self.hashers.append(self._hasher(pb, ivs, i, sel))
+
+    @staticmethod
+    def _hasher(pb, ivs, i, sel):
+        return MiMCe7HashGadget(pb, ivs[i], [sel.left, sel.right])
+
+    def result(self):
+        return self.hashers[-1].result()
+
+    def generate_r1cs_constraints(self):
+        for s, h in zip(self.selectors, self.hashers):
+            s.generate_r1cs_constraints()
+            h.generate_r1cs_constraints()
+
+    def generate_r1cs_witness(self):
+        for s, h in zip(self.selectors, self.hashers):
+            s.generate_r1cs_witness()
+            h.generate_r1cs_witness()
+
+
+class PoseidonPathCompute(MerklePathCompute):
+    """markle_path_compute over Poseidon128<2, 1>: the hasher takes no IV"""
+
+    def __init__(self, pb, depth, address_bits, leaf, path):
+        MerklePathCompute.__init__(self, pb, depth, address_bits, [None] * depth, leaf, path)
+
+    @staticmethod
+    def _hasher(pb, ivs, i, sel):
+        return PoseidonGadget(pb, [sel.left, sel.right])
+
+
+def merkle_update_circuit(depth, hasher="mimc", old_leaf=None, new_leaf=None, address=0, path=None):
+    """"Replacing leaf `address` (old_leaf) by new_leaf takes the tree from old_root to new_root": two markle_path_compute over the SAME address
+    bits and path, each closed by  result * 1 = root.  Returns (r1cs, witness, (old_root, new_root)); both roots are public inputs.
+    Allocation order: old_root, new_root, depth address bits, depth path elements, old_leaf, new_leaf, (MiMC: 29 IVs,) the old chain's level
+    blocks, the new chain's.  Constraints in solved order: old chain, old closing, new chain, new closing -- 2 depth 736 + 2 (MiMC: 42 690 at
+    depth 29) or 2 depth 322 + 2 (Poseidon: 18 678).  Default witness: the leaf and path of merkle_membership_circuit, new_leaf = old_leaf + 1."""
+    if hasher not in ("mimc", "poseidon"):
+        raise ValueError("hasher must be 'mimc' or 'poseidon'")
+    item_a = 3703141493535563179657531719960160174296085208671919316200479060314459804651
+    item_b = 134551314051432487569247388144051420116740427803855572138106146683954151557
+    if old_leaf is None:
+        old_leaf = item_a
+    if new_leaf is None:
+        new_leaf = (old_leaf + 1) % FR
+    if path is None:
+        path = [item_b] + [merkle_unique(d, 1) for d in range(1, depth)]
+    bits = [(address >> i) & 1 for i in range(depth)]
+    if hasher == "mimc":
+        ivs_val = merkle_ivs(29)
+        roots = tuple(merkle_root(leaf, bits, path, ivs_val) for leaf in (old_leaf, new_leaf))
+    else:
+        roots = tuple(poseidon_merkle_root(leaf, bits, path) for leaf in (old_leaf, new_leaf))
+    pb = Protoboard()
+    root_vars = [pb.allocate(roots[0]), pb.allocate(roots[1])]
+    pb.set_input_sizes(2)
+    address_bits = pb.allocate_array(depth, bits)
+    path_vars = pb.allocate_array(depth, path)
+    leaf_vars = [pb.allocate(old_leaf), pb.allocate(new_leaf)]
+    if hasher == "mimc":
+        ivs = pb.allocate_array(29, ivs_val)
+        chains = [MerklePathCompute(pb, depth, address_bits, ivs, leaf, path_vars) for leaf in leaf_vars]
+    else:
+        chains = [PoseidonPathCompute(pb, depth, address_bits, leaf, path_vars) for leaf in leaf_vars]
+    for chain, root_var, root in zip(chains, root_vars, roots):
+        chain.generate_r1cs_witness()
+        chain.generate_r1cs_constraints()
+        pb.add_r1cs_constraint(V(chain.result()), 1, V(root_var))
+        assert pb.val(chain.result()) == root
+    r1cs, w = pb.to_r1cs()
+    return r1cs, w, roots
+
+
 def poseidon_preimage_circuit(n_inputs=2, seed=7):
     """Poseidon128<n_inputs, 1> over private inputs, the digest the single public input: 3 (48 + 57) + 1 + 1 constraints"""
     from .r1cs import SplitMix64

@@ -5,7 +5,9 @@ leaf(depth, offset) -- plus the bulk forms a GPU needs: extend, update_many, pro
 membership circuit (gadgets.merkle_membership_circuit) for k leaves straight into a device witness buffer, ready for
 prover.WitnessPlan.solve and ProverContext.submit_batch(device_ptr=...).  fill_full_witnesses writes the COMPLETE witness instead -- every node
 of a path is in the tree, so one lane per (row, level) computes the level's selector and hash variables and nothing is left for the planner:
-tree -> fill_full_witnesses -> submit_batch(device_ptr=...).  All hashing runs in HIP kernels; there is no CPU path.
+tree -> fill_full_witnesses -> submit_batch(device_ptr=...).  update_seq applies k leaf updates IN ORDER (an index may repeat) and writes per update
+the complete witness of the root-to-root transition circuit (gadgets.merkle_update_circuit): tree -> update_seq -> submit_batch(device_ptr=...).
+All hashing runs in HIP kernels; there is no CPU path.
 
 MerkleTree(n, hasher="poseidon", width=w) is the reference's MerkleTree over MerkleHasher_Poseidon (csrc/poseidon.hpp): n = w^depth leaf slots,
 proofs with w - 1 siblings per level; poseidon_hash / poseidon_permute / poseidon_constants expose the permutation itself.
@@ -23,7 +25,7 @@ MAX_DEPTH = 29
 _SYMBOLS = ("zk_mtree_create", "zk_mtree_free", "zk_mtree_size", "zk_mtree_append", "zk_mtree_append_resident", "zk_mtree_update",
             "zk_mtree_root", "zk_mtree_node", "zk_mtree_paths", "zk_mtree_fill_witnesses", "zk_mimc_constants", "zk_mimc_hash2",
             "zk_mtree_create_ex", "zk_mtree_info", "zk_poseidon_constants", "zk_poseidon_hash", "zk_poseidon_permute",
-            "zk_mtree_fill_full_witnesses")
+            "zk_mtree_fill_full_witnesses", "zk_mtree_update_seq")
 HASHERS = {"mimc": 0, "poseidon": 1}                          # ZK_MTREE_HASH_*
 
 
@@ -50,6 +52,21 @@ def membership_full_layout(depth, hasher="mimc"):
     level_var0 = 3 + 2 * depth + layout.n_iv
     stride = LEVEL_VARS[hasher]
     return layout, level_var0, stride, level_var0 + stride * depth
+
+
+class UpdateLayout(C.Structure):
+    """zk_mtree_update_layout: the variable indices of the update circuit's inputs in a witness row"""
+    _fields_ = [(n, C.c_uint32) for n in ("old_root_var", "new_root_var", "addr_var0", "path_var0", "old_leaf_var", "new_leaf_var", "iv_var0", "n_iv")]
+
+
+def update_layout(depth, hasher="mimc"):
+    """(UpdateLayout, level_var0, level_stride, row_elems) of the complete witness of gadgets.merkle_update_circuit: old_root, new_root, address
+    bits, path, old_leaf, new_leaf, (29 IVs,) then the level blocks of the old chain and those of the new chain"""
+    n_iv = 0 if hasher == "poseidon" else 29
+    layout = UpdateLayout(1, 2, 3, 3 + depth, 3 + 2 * depth, 4 + 2 * depth, 5 + 2 * depth if n_iv else 0, n_iv)
+    level_var0 = 5 + 2 * depth + n_iv
+    stride = LEVEL_VARS[hasher]
+    return layout, level_var0, stride, level_var0 + 2 * stride * depth
 
 
 def _lib():
@@ -292,6 +309,40 @@ class MerkleTree:
             raise ValueError("the device buffer is smaller than k rows")
         P._check(_lib().zk_mtree_fill_full_witnesses(self._h, P._p64(idx), C.c_uint32(len(idx)), C.c_void_p(ptr), C.c_uint64(row_elems), C.byref(layout),
                                                      C.c_uint32(level_var0), C.c_uint32(level_stride)))
+
+    def update_seq(self, indices, leaves, device_buffer=None, r1cs_or_layout=None, row_elems=None, level_var0=None, level_stride=None):
+        """leaves[j] replaces leaf indices[j], IN THE GIVEN ORDER: an index may repeat, and update j sees updates 0 .. j - 1.  Returns the k + 1
+        roots [before, after update 0, .., after update k - 1] as ints; the tree ends up as after k single update() calls.  With a
+        device_buffer (a prover.DeviceBuffer or a device pointer), row j receives the COMPLETE witness of gadgets.merkle_update_circuit for
+        update j -- "replacing leaf a_j (old value x) by y takes root R_j to R_{j+1}", byte for byte what WitnessPlan.solve would leave --
+        ready for submit_batch(device_ptr=...).  r1cs_or_layout: the constraint system of merkle_update_circuit(depth, hasher) (row = V + 1
+        elements), or an UpdateLayout together with row_elems; level_var0 and level_stride place the level blocks (default: update_layout)."""
+        lib = _lib()
+        idx = np.ascontiguousarray([int(i) for i in indices], dtype=np.uint64)
+        a = _leaf_limbs(leaves)
+        k = len(idx)
+        if k != len(a):
+            raise ValueError("indices and leaves differ in length")
+        layout, var0, stride, _ = update_layout(self.depth, self.hasher)
+        ptr = None
+        if device_buffer is not None:
+            if isinstance(r1cs_or_layout, UpdateLayout):
+                layout = r1cs_or_layout
+                if row_elems is None:
+                    raise ValueError("an UpdateLayout needs row_elems")
+            elif row_elems is None:
+                if r1cs_or_layout is None:
+                    raise ValueError("give the constraint system, or an UpdateLayout and row_elems")
+                row_elems = r1cs_or_layout.V + 1
+            ptr = device_buffer.ptr if isinstance(device_buffer, P.DeviceBuffer) else int(device_buffer)
+            if isinstance(device_buffer, P.DeviceBuffer) and k * int(row_elems) * 32 > device_buffer.nbytes:
+                raise ValueError("the device buffer is smaller than k rows")
+        level_var0 = var0 if level_var0 is None else int(level_var0)
+        level_stride = stride if level_stride is None else int(level_stride)
+        roots = np.zeros((k + 1, 4), dtype=np.uint64)
+        P._check(lib.zk_mtree_update_seq(self._h, P._p64(idx), P._p64(a), C.c_uint32(k), 1, C.c_void_p(ptr), C.c_uint64(row_elems or 0), C.byref(layout),
+                                         C.c_uint32(level_var0), C.c_uint32(level_stride), P._p64(roots)))
+        return F.limbs_to_ints(roots)
 
     def close(self):
         if getattr(self, "_h", None) is not None and P._lib is not None:

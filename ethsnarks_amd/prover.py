@@ -72,7 +72,7 @@ EXPORTS = [
     "zk_verify",
     "zk_vctx_create", "zk_vctx_destroy", "zk_verify_batch", "zk_verify_batch_json", "zk_pairing_check", "zk_pairing_tower_op",
     "zk_mtree_create", "zk_mtree_free", "zk_mtree_size", "zk_mtree_append", "zk_mtree_append_resident", "zk_mtree_update", "zk_mtree_root", "zk_mtree_node",
-    "zk_mtree_paths", "zk_mtree_fill_witnesses", "zk_mtree_fill_full_witnesses", "zk_mimc_constants", "zk_mimc_hash2",
+    "zk_mtree_paths", "zk_mtree_fill_witnesses", "zk_mtree_fill_full_witnesses", "zk_mtree_update_seq", "zk_mimc_constants", "zk_mimc_hash2",
     "zk_mtree_create_ex", "zk_mtree_info", "zk_poseidon_constants", "zk_poseidon_hash", "zk_poseidon_permute",
     "zk_jj_hash_to_point", "zk_jj_pedersen_basepoint", "zk_jj_point_op", "zk_jj_scalar_mul", "zk_pedersen_create", "zk_pedersen_free", "zk_pedersen_hash",
     "zk_pedersen_table", "zk_eddsa_create", "zk_eddsa_free", "zk_eddsa_verify_batch", "zk_eddsa_fill_witnesses", "zk_eddsa_fill_pure_witnesses",

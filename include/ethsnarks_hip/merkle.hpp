@@ -11,6 +11,10 @@
 //                                                      zk_wplan_solve and zk_prove_batch_submit_resident
 //   tree.fill_full_witnesses(indices, d_w, row_elems); the COMPLETE witness of the membership circuit instead (selector and hash variables of
 //                                                      every level, computed from the tree's nodes): nothing is left for zk_wplan_solve
+//   tree.update_seq(indices, leaves, d_w, row_elems);  ORDERED updates (an index may repeat; each sees its predecessors): returns the k + 1 roots
+//                                                      before / after every update, and with d_w != nullptr writes per update the complete
+//                                                      witness of the update circuit (two markle_path_compute over one path: old leaf ->
+//                                                      old root, new leaf -> new root); width 2 only
 //   ethsnarks::MerkleTreeHIP wide(14, 4, MerkleHasher::Poseidon);   the same tree over Poseidon128, node width 2, 3 or 4 (capacity width^depth
 //                                                      <= 2^29); a proof then carries `digits` and width - 1 siblings per level in `path`
 // Every failure is a mtree_error carrying the C ABI's code and zk_last_error()'s text.
@@ -116,6 +120,28 @@ public:
     }
     void fill_full_witnesses(const std::vector<uint64_t> &indices, void *d_w, uint64_t row_elems, const zk_mtree_layout &layout, uint32_t var0, uint32_t stride) const {
         if (!indices.empty()) check(zk_mtree_fill_full_witnesses(h_, indices.data(), (uint32_t)indices.size(), d_w, row_elems, &layout, var0, stride));
+    }
+
+    // ordered updates with the witnesses of the update circuit: old_root, new_root, address bits, path, old_leaf, new_leaf, (29 IVs,) then the
+    // level blocks of the old chain and those of the new chain
+    zk_mtree_update_layout update_layout() const {
+        const uint32_t n_iv = membership_layout().n_iv;
+        return zk_mtree_update_layout{1, 2, 3, 3 + depth_, 3 + 2 * depth_, 4 + 2 * depth_, n_iv ? 5 + 2 * depth_ : 0, n_iv};
+    }
+    uint32_t update_level_var0() const { return 5 + 2 * depth_ + membership_layout().n_iv; }
+    uint64_t update_row_elems() const { return (uint64_t)update_level_var0() + 2 * (uint64_t)level_stride() * depth_; }
+    // leaves[j] replaces leaf indices[j] in the given order; the k + 1 roots before and after every update.  d_w == nullptr: no witnesses
+    std::vector<zk_fr> update_seq(const std::vector<uint64_t> &indices, const std::vector<zk_fr> &leaves, void *d_w = nullptr, uint64_t row_elems = 0) {
+        return update_seq(indices, leaves, d_w, row_elems, update_layout(), update_level_var0(), level_stride());
+    }
+    std::vector<zk_fr> update_seq(const std::vector<uint64_t> &indices, const std::vector<zk_fr> &leaves, void *d_w, uint64_t row_elems,
+                                  const zk_mtree_update_layout &layout, uint32_t var0, uint32_t stride) {
+        if (indices.size() != leaves.size()) throw std::invalid_argument("update_seq: indices and leaves differ in length");
+        if (indices.size() > 0x7fffffffu) throw std::invalid_argument("update_seq: more than 2^31 - 1 updates in one call");
+        std::vector<zk_fr> roots(indices.size() + 1);
+        check(zk_mtree_update_seq(h_, indices.data(), leaves.empty() ? nullptr : leaves[0].data(), (uint32_t)indices.size(), 1, d_w, row_elems, &layout, var0, stride,
+                                  roots[0].data()));
+        return roots;
     }
 };
 

@@ -68,7 +68,8 @@ extern "C" {
  *    (zk_eddsa_sign_batch and zk_eddsa_sign_probe came later WITHOUT a bump: no struct changed layout and no function changed signature.  A
  *    client that needs the signer detects it by its symbol.  zk_eddsa_fill_hash_witnesses and zk_eddsa_hash_layout came the same way: a new
  *    function and a new struct beside the old ones, detected by the symbol.  zk_eddsa_fill_witnesses_wide likewise: a new function beside
- *    zk_eddsa_fill_witnesses, which keeps its signature; a client that wants several lanes per witness detects it by the symbol.)
+ *    zk_eddsa_fill_witnesses, which keeps its signature; a client that wants several lanes per witness detects it by the symbol.
+ *    zk_mtree_update_seq and zk_mtree_update_layout likewise: new beside the old ones, detected by the symbol.)
  * A client checks zk_abi_version() == ZK_ABI_VERSION once after loading the library, or passes the size of the zk_config
  * it was compiled with to zk_ctx_create_sized (members it does not know read as 0 = their defaults). */
 #define ZK_ABI_VERSION 9
@@ -433,6 +434,25 @@ int zk_dev_download(void *dst, const void *src, size_t bytes);
  *                              buffer is.  ZK_ERR_ARG, before any device work: node width 3 or 4, an empty tree, an index >= the size,
  *                              level_stride below 736 / 322, level blocks that leave the row or overlap an input variable of the layout,
  *                              n_iv != 0 (Poseidon) or n_iv < D (MiMC: the IVs are read).  k = 0 does nothing
+ *   zk_mtree_update_seq        ORDERED updates with root-to-root transition witnesses: leaves[j] replaces leaf indices[j] for j = 0 .. k - 1 IN THE
+ *                              GIVEN ORDER; an index may occur any number of times and every occurrence sees its predecessors.  The tree ends up node
+ *                              for node as after k single zk_mtree_update calls.  roots_canon (may be NULL) receives k + 1 roots: [0] the root
+ *                              before, [j + 1] the root after update j.  d_w != NULL: row j of the device witness buffer receives the COMPLETE
+ *                              witness of the update circuit (gadgets.merkle_update_circuit: two markle_path_compute over the same address bits
+ *                              and path, closed by result = old_root and result = new_root) for update j against the tree left by updates
+ *                              0 .. j - 1: ONE, the inputs at the variable indices of the zk_mtree_update_layout, the OLD chain's level d at
+ *                              level_var0 + d level_stride and the NEW chain's at level_var0 + (D + d) level_stride, each block as in
+ *                              zk_mtree_fill_full_witnesses.  In the allocation order (old_root, new_root, D address bits, D path elements,
+ *                              old_leaf, new_leaf, MiMC: 29 IVs; layout {1, 2, 3, 3 + D, 3 + 2 D, 4 + 2 D, 5 + 2 D, 29} or {.., 0, 0}, level_var0 =
+ *                              5 + 2 D + n_iv) all variables 0 .. level_var0 + 2 D level_stride - 1 are written, canonical Montgomery,
+ *                              byte-identical to what zk_wplan_solve leaves from the inputs alone; nothing else of the buffer is.  d_w == NULL:
+ *                              the updates and the roots only.  The k chains advance together, one level per step, so the call costs D
+ *                              dependent hashes whatever k (csrc/merkle.hpp).  ZK_ERR_ARG, before any device work: node width 3 or 4, an empty
+ *                              tree, an index >= the size, a leaf >= r, and with d_w: level_stride below 736 / 322, level blocks that leave the
+ *                              row or overlap an input variable, n_iv != 0 (Poseidon) or n_iv < D (MiMC); ZK_ERR_NOMEM for scratch that does not
+ *                              fit.  Either code leaves the tree exactly as it was (only the last step of the call writes nodes).  k = 0 returns
+ *                              roots_canon[0] and does nothing else.  (Added WITHOUT an ABI bump: detected by its symbol.)  MEASUREMENT ONLY:
+ *                              ZK_MTREE_USEQ_TIMING=1 in the environment makes a call print the time of its host predecessor pass on stderr
  *   zk_mimc_constants          host-only: the 91 round constants and 29 level IVs the kernels use, canonical (either may be NULL)
  *   zk_mimc_hash2              out[i] = mimc_hash([left[i], right[i]], iv[i]) on the device, canonical in and out; an operand >= r is ZK_ERR_ARG
  *
@@ -473,6 +493,10 @@ int zk_mtree_paths(const zk_mtree *t, const uint64_t *indices, uint32_t k, uint6
 int zk_mtree_fill_witnesses(const zk_mtree *t, const uint64_t *indices, uint32_t k, void *d_w, uint64_t row_elems, const zk_mtree_layout *layout);
 int zk_mtree_fill_full_witnesses(const zk_mtree *t, const uint64_t *indices, uint32_t k, void *d_w, uint64_t row_elems,
                                  const zk_mtree_layout *layout, uint32_t level_var0, uint32_t level_stride);
+typedef struct { uint32_t old_root_var, new_root_var, addr_var0, path_var0, old_leaf_var, new_leaf_var, iv_var0, n_iv; } zk_mtree_update_layout;
+int zk_mtree_update_seq(zk_mtree *t, const uint64_t *indices, const uint64_t *leaves, uint32_t k, int canonical,
+                        void *d_w, uint64_t row_elems, const zk_mtree_update_layout *layout,
+                        uint32_t level_var0, uint32_t level_stride, uint64_t *roots_canon /* (k + 1) x 4, may be NULL */);
 int zk_mimc_constants(uint64_t *round_constants_canon /* 91 x 4 */, uint64_t *ivs_canon /* 29 x 4 */);
 int zk_mimc_hash2(const uint64_t *left, const uint64_t *right, const uint64_t *iv, uint32_t n, int device, uint64_t *out);
 int zk_poseidon_constants(uint64_t *C_canon /* 65 x 4 */, uint64_t *M_canon /* 36 x 4, row major */);
