@@ -2504,6 +2504,136 @@ extern "C" int zk_msm_sort_probe(const uint64_t *scalars, uint32_t n, uint32_t b
     return rc;
 } ZK_GUARD
 
+// TEST INFRASTRUCTURE: one multi-exponentiation stage by stage (include/zkhip.h).  The work objects are driven exactly as a context drives
+// its own -- alloc, precompute, enqueue_sort, enqueue_accumulate, enqueue_tail -- and every buffer read back outlives those calls, so no
+// kernel and no launch code knows about the probe.  Every copy is bounded by what the caller's capacity check (before any launch) and the
+// allocation allow, never by a count that only the device supplied.
+namespace {
+template <class C> struct StageSide {
+    MsmWork<C> work, srt;                       // srt: the sort-only work of a borrowed sort (a context's mW)
+    typename C::Affine *d_bases = nullptr; fe *d_scalars = nullptr; uint32_t *d_pos = nullptr;
+    bool borrowed = false;
+    uint32_t n = 0, n_sort = 0;
+    uint64_t nbt = 0, piece_bound = 0, entries = 0, pieces = 0;
+    const MsmWork<C> &sorter() const { return borrowed ? srt : work; }
+    uint32_t acc_form() const { return work.sh.quad_acc == 4 ? 4u : (work.sh.acc_pairs && C::WAVES_PER_SIMD_PAIRS != C::WAVES_PER_SIMD) ? 2u : 1u; }
+    int alloc(const zk_msm_stage_in *in, uint32_t c, uint32_t plog) {
+        n = in->n; borrowed = in->n_src != 0; n_sort = borrowed ? in->n_src : in->n;
+        if (borrowed) {
+            ZK_TRY(srt.alloc(n_sort, c, nullptr, nullptr, /*sort_only=*/true, 1, plog));
+            if (in->shift_payload) srt.use_shift_payload();
+            ZK_TRY(work.alloc(n, c, nullptr, &srt.sh, false, 1, plog));
+        } else ZK_TRY(work.alloc(n, c, nullptr, nullptr, false, 1, plog));
+        const MsmShape &sh = work.sh;
+        nbt = (uint64_t)sh.nb << sh.plog;
+        const uint64_t bound = (uint64_t)n_sort * sh.W, by_min = (bound + sh.chunk.seg_min - 1) / sh.chunk.seg_min;
+        piece_bound = (sh.chunk.max_chunks(bound) < by_min ? sh.chunk.max_chunks(bound) : by_min) + nbt;     // <= the allocation: max_chunks(bound) + nbt + 1
+        return ZK_OK;
+    }
+    int upload(const zk_msm_stage_in *in) {
+        ZK_TRY(dev_upload(&d_bases, (const typename C::Affine *)in->bases, n));
+        ZK_TRY(dev_upload(&d_scalars, (const fe *)in->scalars, n_sort));
+        if (borrowed && in->pos) ZK_TRY(dev_upload(&d_pos, in->pos, n_sort));
+        ZK_HIP(hipMemset(work.pieces, 0xff, sizeof(typename C::XYZZ) * piece_bound));
+        return ZK_OK;
+    }
+    int launch(const zk_msm_stage_in *in, int canonical) {
+        ZK_TRY(work.precompute(d_bases, n, nullptr));
+        ZK_TRY((borrowed ? srt : work).enqueue_sort(d_scalars, nullptr, n_sort, canonical, nullptr));
+        return work.enqueue_accumulate(borrowed ? srt.view_for(in->offset, d_pos) : work.view(), nullptr);
+    }
+    // off[], sorted[] and the chunk pieces; the entry count bounds the copies only after it was checked against the allocation
+    int read_back(uint32_t *off, uint32_t *sorted, uint64_t *pieces_out) {
+        ZK_HIP(hipMemcpy(off, sorter().off, sizeof(uint32_t) * (nbt + 1), hipMemcpyDeviceToHost));
+        entries = off[nbt];
+        if (entries > (uint64_t)n_sort * work.sh.W) return fail(ZK_ERR_INTERNAL, "stage probe: off[nb_total] exceeds n * W");
+        if (entries) ZK_HIP(hipMemcpy(sorted, sorter().sorted, sizeof(uint32_t) * entries, hipMemcpyDeviceToHost));
+        const uint32_t seg = work.sh.chunk.len((uint32_t)entries);
+        pieces = entries ? (entries + seg - 1) / seg + nbt - 1 : 0;              // piece index = chunk + bucket
+        if (pieces > piece_bound) return fail(ZK_ERR_INTERNAL, "stage probe: the chunk rule gives more pieces than its own bound");
+        if (pieces) ZK_HIP(hipMemcpy(pieces_out, work.pieces, sizeof(typename C::XYZZ) * pieces, hipMemcpyDeviceToHost));
+        return ZK_OK;
+    }
+    void release() {
+        work.release(); srt.release();
+        if (d_bases) hipFree(d_bases);
+        if (d_scalars) hipFree(d_scalars);
+        if (d_pos) hipFree(d_pos);
+    }
+};
+static bool stage_in_ok(const zk_msm_stage_in *in, bool second) {
+    if (!in->bases || !in->scalars || !in->n) return false;
+    if (!in->n_src) return true;
+    if (second || in->n > in->n_src) return false;
+    if (!in->pos) return (uint64_t)in->offset + in->n <= in->n_src;
+    for (uint32_t i = 0; i < in->n_src; i++) if (in->pos[i] != 0xffffffffu && in->pos[i] >= in->n) return false;
+    return true;
+}
+template <class C>
+static int msm_stage_probe(const zk_msm_stage_in *a, const zk_msm_stage_in *b, int canonical, uint32_t cbits, uint32_t plog, uint32_t tail_lanes, zk_msm_stage_out *o) {
+    constexpr uint64_t AW = sizeof(typename C::Affine) / 8, XW = sizeof(typename C::XYZZ) / 8;
+    typedef typename C::XYZZ X;
+    StageSide<C> s[2];
+    int rc = s[0].alloc(a, cbits, plog);
+    if (rc == ZK_OK && b) rc = s[1].alloc(b, cbits, plog);
+    const MsmShape &sh = s[0].work.sh;
+    const uint64_t nbt = s[0].nbt, sets = sh.planes(), rowcol = ((1ull << sh.lo_bits()) + (1ull << sh.hi_bits())) * sets;
+    if (rc == ZK_OK && b && (s[1].work.sh.nb != sh.nb || s[1].work.sh.plog != sh.plog)) rc = fail(ZK_ERR_ARG, "stage probe: the second MSM has other buckets");
+    if (rc == ZK_OK && (o->table_cap < (uint64_t)sh.rows() * a->n * AW || o->off_cap < nbt + 1 || o->sorted_cap < (uint64_t)s[0].n_sort * sh.W ||
+                        o->pieces_cap < s[0].piece_bound * XW || o->heavy_cap < nbt || o->bucket_cap < nbt * XW || o->partial_a_cap < rowcol * XW ||
+                        o->partial_b_cap < sets * XW || o->result_cap < AW))
+        rc = fail(ZK_ERR_ARG, "stage probe: an output capacity is too small");
+    if (rc == ZK_OK && b && (o->off2_cap < nbt + 1 || o->sorted2_cap < (uint64_t)s[1].n_sort * sh.W || o->pieces2_cap < s[1].piece_bound * XW))
+        rc = fail(ZK_ERR_ARG, "stage probe: an output capacity of the second MSM is too small");
+    // ---- nothing was launched up to here
+    auto run = [&]() -> int {
+        ZK_TRY(s[0].upload(a));
+        if (b) ZK_TRY(s[1].upload(b));
+        MsmWork<C> &w = s[0].work;
+        ZK_HIP(hipMemset(w.bucket, 0xff, sizeof(X) * nbt));
+        ZK_HIP(hipMemset(w.partial_a, 0xff, sizeof(X) * rowcol));
+        ZK_HIP(hipMemset(w.partial_b, 0xff, sizeof(X) * sets));
+        if (b) ZK_TRY(s[1].launch(b, canonical));              // (its accumulation queued first, as the L-query's is before the H-query's tail)
+        ZK_TRY(s[0].launch(a, canonical));
+        ZK_TRY(w.enqueue_tail(nullptr, tail_lanes, b ? &s[1].work : nullptr));
+        if (hipDeviceSynchronize() != hipSuccess) return fail(ZK_ERR_HIP, "MSM kernels failed");
+        ZK_TRY(s[0].read_back(o->off, o->sorted, o->pieces));
+        if (b) ZK_TRY(s[1].read_back(o->off2, o->sorted2, o->pieces2));
+        uint32_t heavy = 0;
+        ZK_HIP(hipMemcpy(&heavy, w.heavy_count, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        const uint32_t lanes = tail_lanes == 4 || tail_lanes == 1 ? tail_lanes : sh.quad;
+        const uint32_t v[32] = {sh.c, sh.W, sh.nb, sh.plog, (uint32_t)sets, sh.lo_bits(), sh.hi_bits(), sh.quad, sh.quad_acc, sh.acc_pairs ? 1u : 0u, s[0].acc_form(),
+                                sh.rowcol_seg, sh.chunk.slots, sh.chunk.seg_min, sh.chunk.seg_max, (uint32_t)s[0].entries, MSM_HEAVY, MSM_TREE, lanes, sh.rows(),
+                                (uint32_t)s[0].pieces, heavy, s[0].borrowed ? s[0].srt.sort_kbits : 0u, b ? 1u : 0u,
+                                b ? s[1].work.sh.chunk.slots : 0u, b ? s[1].work.sh.chunk.seg_min : 0u, b ? s[1].work.sh.chunk.seg_max : 0u, (uint32_t)s[1].entries,
+                                b ? s[1].acc_form() : 0u, (uint32_t)s[1].pieces, MSM_HEAVY_GRID, 0};
+        memcpy(o->info, v, sizeof(v));
+        if (heavy > nbt) return fail(ZK_ERR_INTERNAL, "stage probe: heavy_count exceeds the bucket count");
+        if (heavy) ZK_HIP(hipMemcpy(o->heavy_list, w.heavy_list, sizeof(uint32_t) * heavy, hipMemcpyDeviceToHost));
+        ZK_HIP(hipMemcpy(o->table, w.table, sizeof(typename C::Affine) * (size_t)sh.rows() * a->n, hipMemcpyDeviceToHost));
+        ZK_HIP(hipMemcpy(o->bucket, w.bucket, sizeof(X) * nbt, hipMemcpyDeviceToHost));
+        ZK_HIP(hipMemcpy(o->partial_a, w.partial_a, sizeof(X) * rowcol, hipMemcpyDeviceToHost));
+        ZK_HIP(hipMemcpy(o->partial_b, w.partial_b, sizeof(X) * sets, hipMemcpyDeviceToHost));
+        const typename C::Affine r = C::to_affine(w.finish());
+        memcpy(o->result, &r, sizeof(r));
+        return ZK_OK;
+    };
+    if (rc == ZK_OK) rc = run();
+    s[0].release(); s[1].release();
+    return rc;
+}
+}  // namespace
+extern "C" int zk_msm_stage_probe(int g2, const zk_msm_stage_in *first, const zk_msm_stage_in *second, int canonical, uint32_t c, uint32_t plog,
+                                  uint32_t tail_lanes, int device, zk_msm_stage_out *out) try {
+    if (!first || !out || !out->table || !out->pieces || !out->bucket || !out->partial_a || !out->partial_b || !out->result || !out->off || !out->sorted || !out->heavy_list)
+        return fail(ZK_ERR_ARG, "null argument");
+    if (second && (!out->off2 || !out->sorted2 || !out->pieces2)) return fail(ZK_ERR_ARG, "null argument");
+    if (plog > 7) return fail(ZK_ERR_ARG, "stage probe: plog above 7");
+    if (!stage_in_ok(first, false) || (second && !stage_in_ok(second, true))) return fail(ZK_ERR_ARG, "stage probe: null bases or scalars, n = 0, or a borrowed sort whose offset / pos leave its n_src scalars or this MSM's n bases");
+    ZK_TRY(use_device(device));
+    return g2 ? msm_stage_probe<G2>(first, second, canonical, c, plog, tail_lanes, out) : msm_stage_probe<G1>(first, second, canonical, c, plog, tail_lanes, out);
+} ZK_GUARD
+
 // host-only: Fr elements between the canonical and the Montgomery (libff::Fp_model) representation, in place
 extern "C" int zk_fr_convert(uint64_t *io, uint32_t n, int to_montgomery) try {
     if (n && !io) return fail(ZK_ERR_ARG, "null argument");

@@ -68,7 +68,7 @@ EXPORTS = [
     "zk_wplan_create", "zk_wplan_create_hinted", "zk_wplan_create_wide", "zk_wplan_info", "zk_wplan_solve", "zk_wplan_free", "zk_wplan_probe_program", "zk_dev_alloc", "zk_dev_free", "zk_dev_upload", "zk_dev_download",
     "zk_chain_submit", "zk_chain_device", "zk_h_from_chains_submit", "zk_h_device", "zk_chain_wait", "zk_prove_submit_with_h", "zk_prove_submit_defer_h", "zk_prove_submit_h", "zk_prove_abort",
     "zk_prove_submit_pinned", "zk_prove_batch_submit_pinned", "zk_host_alloc", "zk_host_free", "zk_host_register", "zk_host_unregister",
-    "zk_prove_submit_resident", "zk_prove_stage", "zk_prove_stage_pinned", "zk_prove_submit_staged", "zk_ctx_info", "zk_ctx_table_info", "zk_ctx_hlagrange_info", "zk_hl_probe_dft", "zk_hl_probe_columns", "zk_ctx_probe_rows", "zk_msm_sort_probe", "zk_ctx_partials_device", "zk_prove_collect_device", "zk_prove_combine_device", "zk_launch_count", "zk_profile_begin", "zk_profile_end", "zk_device_info", "zk_device_pci_bus_id",
+    "zk_prove_submit_resident", "zk_prove_stage", "zk_prove_stage_pinned", "zk_prove_submit_staged", "zk_ctx_info", "zk_ctx_table_info", "zk_ctx_hlagrange_info", "zk_hl_probe_dft", "zk_hl_probe_columns", "zk_ctx_probe_rows", "zk_msm_sort_probe", "zk_msm_stage_probe", "zk_ctx_partials_device", "zk_prove_collect_device", "zk_prove_combine_device", "zk_launch_count", "zk_profile_begin", "zk_profile_end", "zk_device_info", "zk_device_pci_bus_id",
     "zk_verify",
     "zk_vctx_create", "zk_vctx_destroy", "zk_verify_batch", "zk_verify_batch_json", "zk_pairing_check", "zk_pairing_tower_op",
     "zk_mtree_create", "zk_mtree_free", "zk_mtree_size", "zk_mtree_append", "zk_mtree_append_resident", "zk_mtree_update", "zk_mtree_root", "zk_mtree_node",
@@ -966,6 +966,83 @@ def msm_sort_probe(scalars, n=None, c=0, plog=0, shift_payload=False, canonical=
                                  C.c_uint32(plog), int(shift_payload), device, _p32(off), C.c_uint64(off.size), _p32(out), C.c_uint64(out.size), _p32(info)))
     d = dict(zip(SORT_INFO, (int(v) for v in info)))
     return off[:d["nb_total"] + 1], out[:d["entries"]], d
+
+
+class ZkMsmStageIn(C.Structure):                                             # include/zkhip.h zk_msm_stage_in
+    _fields_ = [("bases", C.POINTER(C.c_uint64)), ("scalars", C.POINTER(C.c_uint64)), ("pos", C.POINTER(C.c_uint32)),
+                ("n", C.c_uint32), ("n_src", C.c_uint32), ("offset", C.c_uint32), ("shift_payload", C.c_int)]
+
+
+STAGE_POINTS = ("table", "pieces", "bucket", "partial_a", "partial_b", "result", "pieces2")
+STAGE_WORDS = ("off", "sorted", "heavy_list", "off2", "sorted2")
+
+
+class ZkMsmStageOut(C.Structure):                                            # include/zkhip.h zk_msm_stage_out
+    _fields_ = [(k, C.POINTER(C.c_uint64)) for k in STAGE_POINTS] + [(k, C.POINTER(C.c_uint32)) for k in STAGE_WORDS] + \
+               [(k + "_cap", C.c_uint64) for k in STAGE_POINTS + ("off", "sorted", "heavy", "off2", "sorted2")] + [("info", C.c_uint32 * 32)]
+
+
+STAGE_INFO = ("c", "W", "nb", "plog", "sets", "lo_bits", "hi_bits", "quad", "quad_acc", "acc_pairs", "acc_form", "rowcol_seg", "slots", "seg_min", "seg_max",
+              "entries", "MSM_HEAVY", "MSM_TREE", "tail_lanes", "rows", "pieces", "heavy_count", "sort_kbits", "second", "slots2", "seg_min2", "seg_max2",
+              "entries2", "acc_form2", "pieces2", "MSM_HEAVY_GRID")
+
+
+def msm_stage_in(bases, scalars, n_src=0, offset=0, pos=None, shift_payload=False):
+    """one MSM of the stage probe: (struct, arrays it points into).  bases (n, 8 | 16) u64, scalars (n or n_src, 4) u64, pos (n_src,) u32"""
+    bases, scalars = _c64(bases), _c64(scalars)
+    pos = None if pos is None else np.ascontiguousarray(pos, dtype=np.uint32)
+    s = ZkMsmStageIn(_p64(bases), _p64(scalars), _p32(pos) if pos is not None else None, bases.shape[0], n_src, offset, int(shift_payload))
+    return s, (bases, scalars, pos)
+
+
+def msm_stage_probe(first, second=None, g2=False, c=0, plog=0, tail_lanes=0, canonical=False, device=0):
+    """zk_msm_stage_probe (test infrastructure): one multi-exponentiation stage by stage.  first / second: dicts of msm_stage_in's arguments
+    (second: an MSM whose chunk pieces are folded into the first one's bucket reduction).  Returns (dict of raw arrays -- points as
+    (count, coordinates, 4) u64 limbs: table (rows, n, 2 | 4, 4), pieces, bucket, partial_a, partial_b as XYZZ (count, 4 | 8, 4), result
+    (2 | 4, 4); off, sorted, heavy_list [, off2, sorted2, pieces2] --, info dict of STAGE_INFO)."""
+    lib = load_library(_lib_path_loaded)
+    fe_a, fe_x = (4, 8) if g2 else (2, 4)                                 # field elements per affine / XYZZ point
+    a, keep_a = msm_stage_in(**first)
+    b, keep_b = msm_stage_in(**second) if second is not None else (None, None)
+    cc = max(2, min(20, c)) if c else 0
+    W = 254 // cc + 1 if cc else 128
+    nbt = (1 << ((cc or 17) - 1)) << plog
+    rows = -(-W >> plog) if cc else 128
+    rowcol = ((1 << ((cc or 17) // 2)) + (1 << (((cc or 17) - 1) - (cc or 17) // 2))) << plog if cc else 3 << 9 << plog
+    bufs, out = {}, ZkMsmStageOut()
+
+    def give(name, count, width, cap_name=None):
+        arr = np.empty((max(count, 1), width, 4) if width else (max(count, 1),), dtype=np.uint64 if width else np.uint32)
+        bufs[name] = arr
+        setattr(out, name, _p64(arr) if width else _p32(arr))
+        setattr(out, cap_name or name + "_cap", arr.size)
+
+    def side(s, tag):
+        n_sort = s.n_src or s.n
+        give("off" + tag, nbt + 1, 0)
+        give("sorted" + tag, n_sort * W, 0)
+        give("pieces" + tag, -(-n_sort * W // 4) + nbt, fe_x)                # (seg_min >= 4: MsmShape::set)
+
+    side(a, "")
+    if b is not None:
+        side(b, "2")
+    give("table", rows * a.n, fe_a)
+    give("heavy_list", nbt, 0, "heavy_cap")
+    give("bucket", nbt, fe_x)
+    give("partial_a", rowcol, fe_x)
+    give("partial_b", 1 << plog, fe_x)
+    give("result", 1, fe_a)
+    _check(lib.zk_msm_stage_probe(int(g2), C.byref(a), C.byref(b) if b is not None else None, int(canonical), C.c_uint32(c), C.c_uint32(plog),
+                                  C.c_uint32(tail_lanes), device, C.byref(out)))
+    del keep_a, keep_b
+    d = dict(zip(STAGE_INFO, (int(v) for v in out.info)))
+    H, L = 1 << d["hi_bits"], 1 << d["lo_bits"]
+    res = {"table": bufs["table"][:d["rows"] * a.n].reshape(d["rows"], a.n, fe_a, 4), "off": bufs["off"][:d["nb"] * d["sets"] + 1], "sorted": bufs["sorted"][:d["entries"]],
+           "pieces": bufs["pieces"][:d["pieces"]], "heavy_list": bufs["heavy_list"][:d["heavy_count"]], "bucket": bufs["bucket"][:d["nb"] * d["sets"]],
+           "partial_a": bufs["partial_a"][:(H + L) * d["sets"]], "partial_b": bufs["partial_b"][:d["sets"]], "result": bufs["result"][0]}
+    if b is not None:
+        res.update(off2=bufs["off2"][:d["nb"] * d["sets"] + 1], sorted2=bufs["sorted2"][:d["entries2"]], pieces2=bufs["pieces2"][:d["pieces2"]])
+    return res, d
 
 
 def field_mul(a, b, field="fr", device=0):

@@ -329,6 +329,52 @@ int zk_ctx_probe_rows(zk_ctx *ctx, const uint64_t *witnesses, uint32_t k, int ca
  * WITHOUT an ABI bump: detected by its symbol.) */
 int zk_msm_sort_probe(const uint64_t *scalars, uint32_t n, uint32_t batch, uint32_t stride, int canonical, uint32_t c, uint32_t plog,
                       int shift_payload, int device, uint32_t *off, uint64_t off_cap, uint32_t *sorted, uint64_t sorted_cap, uint32_t info[16]);
+/* stage probe: TEST INFRASTRUCTURE.  ONE multi-exponentiation on the default stream through the members a context drives (MsmWork::alloc,
+ * precompute, enqueue_sort, enqueue_accumulate, enqueue_tail), a synchronisation, and what every stage left in the work buffers: RAW device
+ * values (loose domain, no canon).  No kernel and no launch code knows about the probe.
+ * One MSM (zk_msm_stage_in): n bases (affine, 8 / 16 x u64, Montgomery, (0, 0) = infinity) and its scalars (4 x u64, Montgomery unless
+ * canonical).  n_src = 0: the MSM sorts its own n scalars.  n_src != 0, the BORROWED sort: a sort-only work sorts n_src scalars (with
+ * (row << kbits) | i entries if shift_payload != 0, as the shared witness sort of a context does) and the MSM's n <= n_src bases are driven
+ * through view_for(offset, pos): scalar i belongs to base pos[i] (0xffffffff or >= n: absent) or, pos = NULL, to base i - offset.
+ * `second` (optional; own sort only): another MSM with the same c, plog and bucket count whose chunk pieces are folded into the first one's
+ * bucket reduction (enqueue_tail's `also`), as the H- and the L-query of a proof are.
+ *   c: window bits, 0 = the library's choice, clamped to 2 .. 20;  plog: 2^plog bucket planes, <= 7;  tail_lanes: 0 (the shape's) / 1 / 4.
+ *   ZK_MSM_QUAD, ZK_MSM_QUAD_ACC, ZK_ACC_PAIRS, ZK_ROWCOL_SEG, ZK_SEG_MIN and ZK_SEG_MAX in the environment are read as the proving path
+ *   reads them.
+ * Outputs (zk_msm_stage_out; every capacity counts elements of the pointer's type and is checked BEFORE anything is launched; AW = 8 / 16
+ * and XW = 16 / 32 u64 per affine / XYZZ point of G1 / G2; sets = 2^plog, nbt = sets * 2^(c-1), n_sort = n_src ? n_src : n):
+ *   table      rows x n affine points, rows = ceil(W / sets)                       cap >= rows * n * AW
+ *   off        nbt + 1 words;  sorted: off[nbt] words                              cap >= nbt + 1;  cap >= n_sort * W
+ *   pieces     info[20] XYZZ points: piece index 0 .. chunks + nbt - 2.  Slots outside every bucket's piece range were never written and
+ *              hold the probe's fill pattern (all bits set), as do all of pieces, bucket, partial_a and partial_b before the launches
+ *                                                                                  cap >= (min(n_sort W / seg_max + slots + 1, ceil(n_sort W / seg_min)) + nbt) * XW
+ *   heavy_list info[21] words (heavy_count), in the order the device queued them   cap >= nbt
+ *   bucket     nbt XYZZ points;  partial_a: sets x (H + L) XYZZ points, H = 2^hi_bits row sums then L = 2^lo_bits column sums per set;
+ *              partial_b: sets XYZZ points;  result: finish() + to_affine, one affine point
+ *   off2 / sorted2 / pieces2: the second MSM's, same rules with its n (only read when `second` is given)
+ *   info = {c, W, 2^(c-1), plog, sets, lo_bits, hi_bits, quad, quad_acc, acc_pairs, accumulation kernel lanes form (1 / 2 / 4), rowcol_seg,
+ *           chunk.slots, seg_min, seg_max, entries = off[nbt], MSM_HEAVY, MSM_TREE, lanes the tail ran with, rows, pieces copied, heavy_count,
+ *           kbits of the borrowed sort, 1 if a second MSM was folded in, then slots, seg_min, seg_max, entries, accumulation form and pieces
+ *           copied of the second MSM, MSM_HEAVY_GRID, 0}
+ * ZK_ERR_ARG (nothing launched): a null pointer, n = 0, a capacity too small, plog > 7, a borrowed sort with n > n_src, with pos = NULL and
+ * offset + n > n_src, or with a pos[i] that is neither 0xffffffff nor below n; a second MSM with n_src != 0 or, from the work objects,
+ * with other buckets.  ZK_ERR_INTERNAL: heavy_count or off[nbt] exceed their buffers -- nothing past an allocation is read back.  (A new
+ * function WITHOUT an ABI bump: detected by its symbol.) */
+typedef struct zk_msm_stage_in {
+    const uint64_t *bases, *scalars;
+    const uint32_t *pos;            /* n_src words or NULL */
+    uint32_t n, n_src, offset;
+    int shift_payload;
+} zk_msm_stage_in;
+typedef struct zk_msm_stage_out {
+    uint64_t *table, *pieces, *bucket, *partial_a, *partial_b, *result, *pieces2;
+    uint32_t *off, *sorted, *heavy_list, *off2, *sorted2;
+    uint64_t table_cap, pieces_cap, bucket_cap, partial_a_cap, partial_b_cap, result_cap, pieces2_cap;
+    uint64_t off_cap, sorted_cap, heavy_cap, off2_cap, sorted2_cap;
+    uint32_t info[32];
+} zk_msm_stage_out;
+int zk_msm_stage_probe(int g2, const zk_msm_stage_in *first, const zk_msm_stage_in *second, int canonical, uint32_t c, uint32_t plog,
+                       uint32_t tail_lanes, int device, zk_msm_stage_out *out);
 
 /* inputs: nIn Fr elements = witness[1..nIn] (Montgomery unless canonical); returns the JSON length
  * (excluding NUL) through *len; ZK_ERR_BUFFER if cap is too small (len still set) */
