@@ -1198,9 +1198,17 @@ static int enqueue_rows(zk_ctx *c, hipStream_t st) {
     return ZK_OK;
 }
 
+// TEST INFRASTRUCTURE (zk_ctx_probe_h): host buffers that receive what each step of an H pipeline left, through stream-ordered copies enqueued
+// BETWEEN its launches (the steps overwrite each other's buffers).  The proving path passes none: same kernels, arguments and order.
+struct HSnap { fe *first, *coset, *last, *hpart, *tail; };
+static int h_snapshot(const HSnap *snap, fe *HSnap::*which, const fe *d_src, size_t n, hipStream_t st) {
+    if (snap && snap->*which) ZK_HIP(hipMemcpyAsync(snap->*which, d_src, 32 * n, hipMemcpyDeviceToHost, st));
+    return ZK_OK;
+}
+
 // ---- "Compute the polynomial H" (tcc:460-475) on s_main; result in d_t (natural order), h[m-1] copied to h_tail
 // for the k = cur_batch proofs in flight: polynomials laid out [A: k x m][B: k x m][C: k x m] in d_a, h of proof p at d_t + p m
-static int enqueue_compute_h(zk_ctx *c, hipStream_t st) {
+static int enqueue_compute_h(zk_ctx *c, hipStream_t st, const HSnap *snap = nullptr) {
     const uint32_t m = c->m, k = c->cur_batch;
     fe *a = c->d_a, *b = c->d_a + (size_t)m * k, *cc = c->d_a + 2 * (size_t)m * k;
     ZK_TRY(enqueue_rows(c, st));
@@ -1213,9 +1221,12 @@ static int enqueue_compute_h(zk_ctx *c, hipStream_t st) {
     (void)cc;
     NttFuse cscale; cscale.post_alt = c->tab.inv_m_zinv; cscale.alt_from = 2 * k;                     // vectors [2k, 3k) are the C polynomials
     ZK_TRY(ntt_run(c->tab, a, c->d_t, true, nullptr, c->tab.inv_then_coset, st, 3 * k, m, cscale));   // iFFT of A, B (x g^i / m: cosetFFT pre-scale) and of C (x 1 / (m Z(g)))
+    if (snap) ZK_TRY(h_snapshot(snap, &HSnap::first, c->d_t, 3 * (size_t)m * k, st));
     ZK_TRY(ntt_run(c->tab, c->d_t, a, false, nullptr, nullptr, st, 2 * k, m));                        // FFT: A, B on the coset
+    if (snap) ZK_TRY(h_snapshot(snap, &HSnap::coset, a, 2 * (size_t)m * k, st));
     NttFuse last; last.in2 = b; last.sub = c->d_t + 2 * (size_t)m * k;
     ZK_TRY(ntt_run(c->tab, a, c->d_t, true, nullptr, c->tab.icoset_zinv, st, k, m, last));            // icosetFFT of A B, / Z(g), - C / Z(g)
+    if (snap) ZK_TRY(h_snapshot(snap, &HSnap::last, c->d_t, (size_t)m * k, st));
     if (k == 1) ZK_HIP(hipMemcpyAsync(c->h_tail, c->d_t + (m - 1), 32, hipMemcpyDeviceToHost, st));
     else ZK_HIP(hipMemcpy2DAsync(c->h_tail, 32, c->d_t + (m - 1), 32 * (size_t)m, 32, k, hipMemcpyDeviceToHost, st));
     ZK_HIP(hipGetLastError());
@@ -1225,16 +1236,20 @@ static int enqueue_compute_h(zk_ctx *c, hipStream_t st) {
 // ---- the same for a context whose H-query lies in coset-Lagrange bases (hlagrange.hpp): FOUR transforms.  The H scalars are the
 // products p_j = A(g w^j) B(g w^j), canonical, in d_t (proof p at d_t + p m); the C row evaluations are scalars of nothing -- their part of h
 // is in the L-query's bases -- and only enter the degree check: h[m-1] as a dot product over p and c, copied to h_tail as above.
-static int enqueue_compute_h4(zk_ctx *c, hipStream_t st) {
+static int enqueue_compute_h4(zk_ctx *c, hipStream_t st, const HSnap *snap = nullptr) {
     const uint32_t m = c->m, k = c->cur_batch;
     fe *a = c->d_a, *b = c->d_a + (size_t)m * k, *cc = c->d_a + 2 * (size_t)m * k;
     ZK_TRY(enqueue_rows(c, st));
     NttFuse bscale; bscale.post_alt = c->d_bscale; bscale.alt_from = k;                                 // vectors [k, 2k) are the B polynomials: x 1 / R as well
     ZK_TRY(ntt_run(c->tab, a, c->d_t, true, nullptr, c->tab.inv_then_coset, st, 2 * k, m, bscale));   // iFFT of A, B (x g^i / m: cosetFFT pre-scale)
+    if (snap) ZK_TRY(h_snapshot(snap, &HSnap::first, c->d_t, 2 * (size_t)m * k, st));
     ZK_TRY(ntt_run(c->tab, c->d_t, a, false, nullptr, nullptr, st, 2 * k, m));                        // FFT: A, B on the coset
+    if (snap) ZK_TRY(h_snapshot(snap, &HSnap::coset, a, 2 * (size_t)m * k, st));
     const uint32_t grid = zk_div_up(m, HL_PROD_THREADS * HL_PROD_PER);
     ZK_LAUNCH_SYNC(k_hl_product, dim3(grid, k), HL_PROD_THREADS, st, (const fe *)a, (const fe *)b, (const fe *)cc, (const fe *)c->tab.tw_fwd, c->d_t, c->d_hpart, m, m);
+    if (snap) { ZK_TRY(h_snapshot(snap, &HSnap::last, c->d_t, (size_t)m * k, st)); ZK_TRY(h_snapshot(snap, &HSnap::hpart, c->d_hpart, 2 * (size_t)grid * k, st)); }
     ZK_LAUNCH_SYNC(k_hl_tail, k, HL_PROD_THREADS, st, (const fe *)c->d_hpart, grid, c->hl_kp, c->hl_kc, c->d_tail);
+    if (snap) ZK_TRY(h_snapshot(snap, &HSnap::tail, c->d_tail, k, st));
     ZK_HIP(hipMemcpyAsync(c->h_tail, c->d_tail, 32 * (size_t)k, hipMemcpyDeviceToHost, st));
     ZK_HIP(hipGetLastError());
     return ZK_OK;
@@ -2411,6 +2426,36 @@ extern "C" int zk_ntt(uint64_t *data, uint32_t logm, int inverse, int coset, int
     return rc;
 } ZK_GUARD
 
+// TEST INFRASTRUCTURE: ONE ntt_run over the production tables with the batch, stride and fused steps of the caller's choice (include/zkhip.h)
+extern "C" int zk_ntt_probe(const uint64_t *in, const uint64_t *in2, const uint64_t *sub, uint64_t *out, uint32_t logm, uint32_t batch, uint32_t stride,
+                            int inverse, int pre, int post, int post_alt, uint32_t alt_from, int device) try {
+    if (!in || !out) return fail(ZK_ERR_ARG, "transform probe: null argument");
+    if (logm > 28) return fail(ZK_ERR_ARG, "transform probe: logm above 28");
+    if (!batch) return fail(ZK_ERR_ARG, "transform probe: batch = 0");
+    if (stride < (1u << logm)) return fail(ZK_ERR_ARG, "transform probe: stride below m");
+    if (pre < 0 || pre > 1 || post < 0 || post > 5 || post_alt < 0 || post_alt > 5) return fail(ZK_ERR_ARG, "transform probe: unknown scaling table");
+    if (sub && !post) return fail(ZK_ERR_ARG, "transform probe: sub needs post (k_ntt_pass)");
+    ZK_TRY(use_device(device));
+    NttTables tab; fe *d_in = nullptr, *d_out = nullptr, *d_in2 = nullptr, *d_sub = nullptr;
+    const size_t n = (size_t)batch * stride;                    // every array is copied whole, gaps between the vectors included
+    int rc = ntt_tables_create(tab, logm, nullptr);
+    if (rc == ZK_OK) rc = dev_upload(&d_in, (const fe *)in, n);
+    if (rc == ZK_OK) rc = dev_upload(&d_out, (const fe *)out, n);   // the caller's output comes back as it was wherever the transform does not write
+    if (rc == ZK_OK && in2) rc = dev_upload(&d_in2, (const fe *)in2, n);
+    if (rc == ZK_OK && sub) rc = dev_upload(&d_sub, (const fe *)sub, n);
+    if (rc == ZK_OK) {
+        const fe *scale[6] = {nullptr, tab.inv_m, tab.icoset, tab.inv_then_coset, tab.inv_m_zinv, tab.icoset_zinv};
+        NttFuse fuse; fuse.in2 = d_in2; fuse.sub = d_sub; fuse.post_alt = scale[post_alt]; fuse.alt_from = alt_from;
+        rc = ntt_run(tab, d_in, d_out, inverse != 0, pre ? tab.coset_fwd : nullptr, scale[post], nullptr, batch, stride, fuse);
+    }
+    if (rc == ZK_OK && hipDeviceSynchronize() != hipSuccess) rc = fail(ZK_ERR_HIP, "NTT kernels failed");
+    if (rc == ZK_OK && hipMemcpy(out, d_out, 32 * n, hipMemcpyDeviceToHost) != hipSuccess) rc = ZK_ERR_HIP;
+    fe *bufs[] = {d_in, d_out, d_in2, d_sub};
+    for (fe *p : bufs) if (p) hipFree(p);
+    ntt_tables_free(tab);
+    return rc;
+} ZK_GUARD
+
 extern "C" int zk_witness_map(zk_ctx *c, const uint64_t *witness, int canonical, uint64_t *h_out) try {
     if (!c || !witness || !h_out) return fail(ZK_ERR_ARG, "null argument");
     if (c->in_flight) return fail(ZK_ERR_ARG, "a proof is in flight on this context (collect it first): its witness and H buffers are in use");
@@ -2435,6 +2480,34 @@ extern "C" int zk_ctx_probe_rows(zk_ctx *c, const uint64_t *witnesses, uint32_t 
     ZK_TRY(enqueue_rows(c, c->s_main));
     ZK_HIP(hipStreamSynchronize(c->s_main));
     ZK_HIP(hipMemcpy(out, c->d_a, 3 * 32 * (size_t)c->m * k, hipMemcpyDeviceToHost));
+    return ZK_OK;
+} ZK_GUARD
+
+// TEST INFRASTRUCTURE: the context's own H pipeline on a batch, and what each of its steps left (include/zkhip.h)
+extern "C" int zk_ctx_probe_h(zk_ctx *c, const uint64_t *witnesses, uint32_t k, int canonical, uint64_t *first, uint64_t *coset, uint64_t *last,
+                              uint64_t *hpart, uint64_t *tail, uint64_t *h_tail, uint32_t info[8]) try {
+    if (!c || !witnesses || !first || !coset || !last || !hpart || !tail || !h_tail || !info) return fail(ZK_ERR_ARG, "null argument");
+    if (c->in_flight) return fail(ZK_ERR_ARG, "a proof is in flight on this context (collect it first): its witness and H buffers are in use");
+    if (!k || k > c->max_batch) return fail(ZK_ERR_ARG, "batch size exceeds zk_config.max_batch of this context");
+    ZK_TRY(use_device(c->device));
+    const uint32_t m = c->m, grid = c->lag ? zk_div_up(m, HL_PROD_THREADS * HL_PROD_PER) : 0;
+    const size_t mk = (size_t)m * k;
+    // the copies land in buffers of the probe's own and reach the caller's only after everything succeeded
+    std::vector<fe> b_first((c->lag ? 2 : 3) * mk), b_coset(2 * mk), b_last(mk), b_hpart(2 * (size_t)grid * k), b_tail(c->lag ? k : 0);
+    HSnap snap{b_first.data(), b_coset.data(), b_last.data(), c->lag ? b_hpart.data() : nullptr, c->lag ? b_tail.data() : nullptr};
+    c->cur_batch = k;
+    int rc = upload_witness(c, witnesses, canonical);
+    if (rc == ZK_OK) rc = c->lag ? enqueue_compute_h4(c, c->s_main, &snap) : enqueue_compute_h(c, c->s_main, &snap);
+    const hipError_t synced = hipStreamSynchronize(c->s_main);      // on every path: copies into the buffers above may be pending
+    if (rc != ZK_OK) return rc;
+    ZK_HIP(synced);
+    memcpy(first, b_first.data(), 32 * b_first.size());
+    memcpy(coset, b_coset.data(), 32 * b_coset.size());
+    memcpy(last, b_last.data(), 32 * b_last.size());
+    if (c->lag) { memcpy(hpart, b_hpart.data(), 32 * b_hpart.size()); memcpy(tail, b_tail.data(), 32 * b_tail.size()); }
+    memcpy(h_tail, c->h_tail, 32 * (size_t)k);
+    const uint32_t inf[8] = {c->lag ? 1u : 0u, m, k, grid, 0, 0, 0, 0};
+    memcpy(info, inf, sizeof(inf));
     return ZK_OK;
 } ZK_GUARD
 

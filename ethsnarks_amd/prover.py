@@ -68,7 +68,7 @@ EXPORTS = [
     "zk_wplan_create", "zk_wplan_create_hinted", "zk_wplan_create_wide", "zk_wplan_info", "zk_wplan_solve", "zk_wplan_free", "zk_wplan_probe_program", "zk_dev_alloc", "zk_dev_free", "zk_dev_upload", "zk_dev_download",
     "zk_chain_submit", "zk_chain_device", "zk_h_from_chains_submit", "zk_h_device", "zk_chain_wait", "zk_prove_submit_with_h", "zk_prove_submit_defer_h", "zk_prove_submit_h", "zk_prove_abort",
     "zk_prove_submit_pinned", "zk_prove_batch_submit_pinned", "zk_host_alloc", "zk_host_free", "zk_host_register", "zk_host_unregister",
-    "zk_prove_submit_resident", "zk_prove_stage", "zk_prove_stage_pinned", "zk_prove_submit_staged", "zk_ctx_info", "zk_ctx_table_info", "zk_ctx_hlagrange_info", "zk_hl_probe_dft", "zk_hl_probe_columns", "zk_ctx_probe_rows", "zk_msm_sort_probe", "zk_msm_stage_probe", "zk_ctx_partials_device", "zk_prove_collect_device", "zk_prove_combine_device", "zk_launch_count", "zk_profile_begin", "zk_profile_end", "zk_device_info", "zk_device_pci_bus_id",
+    "zk_prove_submit_resident", "zk_prove_stage", "zk_prove_stage_pinned", "zk_prove_submit_staged", "zk_ctx_info", "zk_ctx_table_info", "zk_ctx_hlagrange_info", "zk_hl_probe_dft", "zk_hl_probe_columns", "zk_ctx_probe_rows", "zk_msm_sort_probe", "zk_msm_stage_probe", "zk_ntt_probe", "zk_ctx_probe_h", "zk_ctx_partials_device", "zk_prove_collect_device", "zk_prove_combine_device", "zk_launch_count", "zk_profile_begin", "zk_profile_end", "zk_device_info", "zk_device_pci_bus_id",
     "zk_verify",
     "zk_vctx_create", "zk_vctx_destroy", "zk_verify_batch", "zk_verify_batch_json", "zk_pairing_check", "zk_pairing_tower_op",
     "zk_mtree_create", "zk_mtree_free", "zk_mtree_size", "zk_mtree_append", "zk_mtree_append_resident", "zk_mtree_update", "zk_mtree_root", "zk_mtree_node",
@@ -603,6 +603,23 @@ class ProverContext:
         _check(_lib.zk_ctx_probe_rows(self._h, _p64(w), C.c_uint32(k), int(canonical), _p64(out)))
         return out
 
+    def probe_h(self, witnesses, canonical=False):
+        """zk_ctx_probe_h (test infrastructure): the context's own H pipeline on k witnesses, and what each step left, as raw limbs:
+        dict(four, m, k, grid, first (3 | 2, k, m, 4), coset (2, k, m, 4), last (k, m, 4), hpart (k, grid, 2, 4) and tail (k, 4) -- None with six
+        transforms --, h_tail (k, 4)).  include/zkhip.h documents the representation of every buffer."""
+        w, k = self._wk(witnesses)
+        m = self.r1cs.domain_size
+        first, coset, last = (np.zeros((g, k, m, 4), dtype=np.uint64) for g in (3, 2, 1))
+        hpart = np.zeros((k * -(-m // 256), 2, 4), dtype=np.uint64)       # all of d_hpart (one pair per 256 elements): the grid comes back in info
+        tail, h_tail = np.zeros((k, 4), dtype=np.uint64), np.zeros((k, 4), dtype=np.uint64)
+        info = np.zeros(8, dtype=np.uint32)
+        _check(_lib.zk_ctx_probe_h(self._h, _p64(w), C.c_uint32(k), int(canonical), _p64(first), _p64(coset), _p64(last), _p64(hpart), _p64(tail),
+                                   _p64(h_tail), _p32(info)))
+        four, grid = bool(info[0]), int(info[3])
+        assert (int(info[1]), int(info[2])) == (m, k) and k * grid <= hpart.shape[0], list(info)
+        return dict(four=four, m=m, k=k, grid=grid, first=first if not four else first[:2], coset=coset, last=last[0],
+                    hpart=hpart[:k * grid].reshape(k, grid, 2, 4) if four else None, tail=tail if four else None, h_tail=h_tail)
+
     def close(self):
         if getattr(self, "_h", None) is not None and _lib is not None:
             _lib.zk_ctx_destroy(self._h)
@@ -933,6 +950,27 @@ def ntt(data, logm, inverse=False, coset=False, device=0):
     a = _c64(data).copy()
     _check(load_library(_lib_path_loaded).zk_ntt(_p64(a), C.c_uint32(logm), int(inverse), int(coset), device))
     return a
+
+
+NTT_PRE = ("none", "coset_fwd")                                                                   # include/zkhip.h zk_ntt_probe
+NTT_POST = ("none", "inv_m", "icoset", "inv_then_coset", "inv_m_zinv", "icoset_zinv")
+
+
+def ntt_probe(data, logm, out=None, inverse=False, pre="none", post="none", post_alt="none", alt_from=0xffffffff, in2=None, sub=None, device=0):
+    """zk_ntt_probe (test infrastructure): ONE call of the transform driver as a proof makes it.  data, in2, sub, out: (batch, stride, 4) u64
+    raw limbs, stride >= 2^logm; `out` (default: zeros) is what the output holds before the call -- the words behind every vector come back
+    as they were.  pre / post / post_alt: names of NTT_PRE / NTT_POST.  Returns the output array."""
+    a = _c64(data)
+    assert a.ndim == 3 and a.shape[2] == 4, a.shape
+    batch, stride = a.shape[0], a.shape[1]
+    o = np.zeros_like(a) if out is None else _c64(out).copy()
+    assert o.shape == a.shape
+    extra = [None if x is None else _c64(x) for x in (in2, sub)]
+    assert all(x is None or x.shape == a.shape for x in extra)
+    _check(load_library(_lib_path_loaded).zk_ntt_probe(_p64(a), *(None if x is None else _p64(x) for x in extra), _p64(o), C.c_uint32(logm), C.c_uint32(batch),
+                                                       C.c_uint32(stride), int(inverse), NTT_PRE.index(pre), NTT_POST.index(post), NTT_POST.index(post_alt),
+                                                       C.c_uint32(alt_from), device))
+    return o
 
 
 def msm(bases, scalars, g2=False, c=0, device=0):

@@ -69,7 +69,8 @@ extern "C" {
  *    client that needs the signer detects it by its symbol.  zk_eddsa_fill_hash_witnesses and zk_eddsa_hash_layout came the same way: a new
  *    function and a new struct beside the old ones, detected by the symbol.  zk_eddsa_fill_witnesses_wide likewise: a new function beside
  *    zk_eddsa_fill_witnesses, which keeps its signature; a client that wants several lanes per witness detects it by the symbol.
- *    zk_mtree_update_seq and zk_mtree_update_layout likewise: new beside the old ones, detected by the symbol.)
+ *    zk_mtree_update_seq and zk_mtree_update_layout likewise: new beside the old ones, detected by the symbol.  The test probes
+ *    zk_ctx_probe_rows, zk_msm_sort_probe, zk_msm_stage_probe, zk_ntt_probe and zk_ctx_probe_h likewise.)
  * A client checks zk_abi_version() == ZK_ABI_VERSION once after loading the library, or passes the size of the zk_config
  * it was compiled with to zk_ctx_create_sized (members it does not know read as 0 = their defaults). */
 #define ZK_ABI_VERSION 9
@@ -375,6 +376,41 @@ typedef struct zk_msm_stage_out {
 } zk_msm_stage_out;
 int zk_msm_stage_probe(int g2, const zk_msm_stage_in *first, const zk_msm_stage_in *second, int canonical, uint32_t c, uint32_t plog,
                        uint32_t tail_lanes, int device, zk_msm_stage_out *out);
+/* transform probe: TEST INFRASTRUCTURE.  Builds the production scaling and twiddle tables for m = 2^logm, uploads the caller's arrays, calls
+ * the transform driver (csrc/ntt.hpp ntt_run) ONCE with the batch, stride and fused steps a proof gives it, synchronises and copies the output
+ * back.  zk_ntt is the case batch = 1, stride = 0, nothing fused.
+ *   in, out, in2, sub: batch x stride elements each (4 x u64, RAW words as the kernels read and leave them: Montgomery in every production
+ *     call; the loose representatives [0, 2r) are accepted on input as by the butterflies).  Vector v lies at element v * stride; stride >= m.
+ *     Every array is copied WHOLE, the stride - m words behind each vector included: `out` is uploaded before the call and downloaded after
+ *     it, so whatever the caller left in the gaps of `out` comes back unless a kernel wrote there.
+ *   inverse: the inverse twiddles (no 1 / m by itself: that is a post table).  pre: 0 none, 1 coset_fwd (g^i).
+ *   post, post_alt: 0 none, 1 inv_m (1 / m), 2 icoset (g^-i / m), 3 inv_then_coset (g^i / m), 4 inv_m_zinv (1 / (m Z(g))),
+ *     5 icoset_zinv (g^-i / (m Z(g)));  g = 5, Z(g) = g^m - 1.  Vectors v >= alt_from are scaled by post_alt (if not 0) instead of post.
+ *   in2 (or NULL): the transform's input is in[i] * in2[i] (Montgomery product).  sub (or NULL): out[i] = v * post[i] - sub[i].
+ *   Output words: a scaled vector is the strict Montgomery product, canonical [0, r); an unscaled one is reduced to [0, r) by the last pass.
+ * ZK_ERR_ARG, nothing launched and `out` not written: in or out NULL, logm > 28, batch = 0, stride < m, a table number out of range, sub
+ * without post.  (A new function WITHOUT an ABI bump: detected by its symbol.) */
+int zk_ntt_probe(const uint64_t *in, const uint64_t *in2, const uint64_t *sub, uint64_t *out, uint32_t logm, uint32_t batch, uint32_t stride,
+                 int inverse, int pre, int post, int post_alt, uint32_t alt_from, int device);
+/* H probe: TEST INFRASTRUCTURE.  Uploads the k witnesses as zk_ctx_probe_rows does and runs the context's OWN H pipeline on its main stream --
+ * the six-transform one, or the four-transform one when the context keeps the H-query in coset-Lagrange bases -- with device-to-host copies
+ * enqueued between its launches.  The kernels, their arguments and their order are those of a proof; a proof passes no snapshot buffers.
+ * All outputs are RAW device words, 4 x u64 per element, vector p of a group at element p * m.  R = 2^256 mod r; "Montgomery" = value * R.
+ *   first   after the first transform.  six: [A: k][B: k][C: k] x m -- a_i g^i, b_i g^i (coefficients of the interpolants times the coset
+ *           shift) and c_i / Z(g), Montgomery.  four: [A: k][B: k] x m -- a_i g^i Montgomery, b_i g^i CANONICAL (the post-scale of B carries
+ *           1 / R); the third group of `first` is not written.  The caller gives 3 k m elements either way.
+ *   coset   after the second transform: [A: k][B: k] x m, A(g w^j) and B(g w^j) in the representations above, reduced to [0, r).
+ *   last    six: h, k x m, Montgomery, h = (icosetFFT(A B) - C) / Z(g), coefficient m - 1 included.  four: p_j = A(g w^j) B(g w^j), k x m,
+ *           CANONICAL (the H scalars as the bucket sort reads them).
+ *   hpart   four only: 2 x grid x k elements; pair (2 (p grid + x), + 1) is workgroup x's share of proof p's degree check, over j in
+ *           [2048 x, 2048 (x + 1)): sum_j w^j p_j CANONICAL, then sum_j w^j c_j Montgomery (c_j = the C row evaluations).  grid = ceil(m / 2048).
+ *   tail    four only: k elements, h[m-1] of every proof, Montgomery:  (g^-(m-1) sum_j w^j p_j - sum_j w^j c_j) / (m Z(g)).
+ *   h_tail  k elements, always: the pinned words the degree check of a proof reads (Montgomery h[m-1]; zero iff the witness satisfies).
+ *   info = {1 four transforms / 0 six, m, k, grid of k_hl_product (0 with six transforms), 0, 0, 0, 0}
+ * ZK_ERR_ARG, nothing written to any output: a null pointer (hpart and tail must be given even with six transforms, where they stay
+ * unwritten), a proof in flight, k = 0, k > zk_config.max_batch.  (A new function WITHOUT an ABI bump: detected by its symbol.) */
+int zk_ctx_probe_h(zk_ctx *ctx, const uint64_t *witnesses, uint32_t k, int canonical, uint64_t *first /* 3 k m x 4 */, uint64_t *coset /* 2 k m x 4 */,
+                   uint64_t *last /* k m x 4 */, uint64_t *hpart /* 2 grid k x 4 */, uint64_t *tail /* k x 4 */, uint64_t *h_tail /* k x 4 */, uint32_t info[8]);
 
 /* inputs: nIn Fr elements = witness[1..nIn] (Montgomery unless canonical); returns the JSON length
  * (excluding NUL) through *len; ZK_ERR_BUFFER if cap is too small (len still set) */
